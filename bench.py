@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — denoising-steps/sec of the diffusynth sampling hot path on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N>1 runs one process per GPU over RCCL.  Either the driver launches the ranks itself (``python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N``: RANK / WORLD_SIZE are in the environment), or a plain ``python bench.py --gpus N``
@@ -24,12 +24,17 @@ BASELINE configs[3]'s per-GPU share (64 per GPU, CFG 6, 100-step DDIM).
 Default tier = "bf16x3": the tier whose results meet north_star's 1e-3 against the fp32 reference
 (model/diffusion.py:187-258 runs fp32 eager): fp32 tensors, every dense contraction as
 x_hi w_hi + x_lo w_hi + x_hi w_lo on the bf16 matrix cores with fp32 accumulation.  The plain bf16 tier
-(9e-3 off the reference: BASELINE configs[1] names it) and the all-fp32 tier are reported under ``secondary``.
+(9e-3 off the reference: BASELINE configs[1] names it) and the all-fp32 tier are reported under ``secondary`` (--full).
 Rank 0 prints ONE JSON line; it also carries
-  roofline      — dominant kernel (3x3 MFMA conv): its matrix-core work / HIP-event time measured inside the timed region,
   step_roofline — whole-step fraction of the HBM / MFMA rooflines (SURVEY §8d byte / FLOP model),
+and, with --full only (a plain run sets up, warms up, times the K steps and prints the line: roofline and cpu_baseline are null
+there and secondary is absent):
+  roofline      — dominant kernel (3x3 MFMA conv): its matrix-core work / HIP-event time measured inside the timed region,
   secondary     — (N=1) the bf16 and fp32 tiers on the same workload with their measured errors, configs[1], batch 1, the tail,
   cpu_baseline  — (N=1) the CPU oracle (a port of the reference's CPU path) timed around ITS sample() on this host.
+
+--dump-outputs DIR writes, after the timed call, the final latents it returned (the last step's output, all ranks gathered) as
+DIR/latents.npy in float32; the inputs (weights, conditions, noise) are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -57,6 +62,7 @@ PMC_TRAFFIC_FILE = "r05_pmc_hbm_traffic.json"
 TIER_WORDS = {"bf16": "bf16", "fp32": "fp32",
               "bf16x3": "bf16x3 (fp32 tensors, dense convolutions as 3 bf16 MFMA terms with fp32 accumulation: meets 1e-3 vs the fp32 reference)"}
 EVENT_EVERY = 4      # per-launch HIP events on every 4th step of the timed sample() call
+DUMP_LIMIT = 64 * 10**6   # bytes written by --dump-outputs at most; a larger output is replaced by a fixed, seeded sample of it
 
 
 def parse():
@@ -71,9 +77,13 @@ def parse():
                     help="bf16x3 (default): the tier that meets 1e-3 vs the fp32 reference; bf16: 9e-3 off; fp32: fp32 MFMAs")
     ap.add_argument("--height", type=int, default=256)
     ap.add_argument("--width", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] / fp32-tier / bf16-error fields")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip per-launch HIP events in the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the kernel roofline (per-launch HIP events in the timed region), the secondary tiers / configs "
+                         "and the CPU baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the timed call's final latents to DIR/latents.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the configs[1] / fp32-tier / bf16-error fields")
+    ap.add_argument("--no-kernel-events", action="store_true", help="(--full) skip per-launch HIP events in the timed region")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher rehearsal: rendezvous, the one broadcast, barrier and max-over-ranks reduction only; no model, "
                          "no measurement (value is null).  The only mode that runs without a GPU (tests/test_dist_cpu.py)")
@@ -167,7 +177,7 @@ def cpu_baseline(H, W):
 
 
 def run_sample(net, device, rank, world, B, cfg, sampler_name, conditioned, cond1, uncond1, H, W, K, warm, events):
-    """One warm-up sample() call of ``warm`` steps, then ONE timed sample() call of K steps.  Returns (seconds, plan)."""
+    """One warm-up sample() call of ``warm`` steps, then ONE timed sample() call of K steps.  Returns (seconds, plan, final latents)."""
     from diffusynth_amd import dist as D
     from diffusynth_amd.sampler import DiffSynthSampler
 
@@ -203,7 +213,21 @@ def run_sample(net, device, rank, world, B, cfg, sampler_name, conditioned, cond
     elapsed = D.max_over_ranks(time.perf_counter() - t0, device)
     assert len(imgs) == K + 1 and torch.isfinite(imgs[-1]).all(), "non-finite latents"
     assert plan is not None or not events, "the timed call's plan was not found: no kernel events, no roofline"
-    return elapsed, plan
+    return elapsed, plan, imgs[-1]
+
+
+def dump_outputs(d, outputs):
+    """Write each output as d/<name>.npy in float32; above DUMP_LIMIT bytes in all, each is cut to a fixed, seeded sample of its
+    elements (the same positions for the same arguments) saved as d/<name>_sample.npy."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
+    total = sum(x.nbytes for x in arrays.values())
+    for name, x in arrays.items():
+        if total > DUMP_LIMIT:
+            n = x.size * DUMP_LIMIT // total
+            idx = np.sort(np.random.default_rng(0).choice(x.size, n, replace=False))
+            name, x = name + "_sample", x.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), x)
 
 
 def kernel_roofline(plan, dtype, elapsed, K, traffic_key):
@@ -417,8 +441,12 @@ def main():
         c0 = synth_input("bench_cond", (512,)) if rank == 0 else None
         u0 = synth_input("bench_uncond", (512,)) if (rank == 0 and cfg != 1.0) else None
         cond, uncond = D.broadcast_conditions(c0, u0, device)
-    use_events = not a.no_kernel_events
-    elapsed, plan = run_sample(net, device, rank, world, B, cfg, sampler_name, conditioned, cond, uncond, H, W, K, a.warmup, use_events)
+    use_events = a.full and not a.no_kernel_events
+    elapsed, plan, latents = run_sample(net, device, rank, world, B, cfg, sampler_name, conditioned, cond, uncond, H, W, K, a.warmup, use_events)
+    if a.dump_outputs:
+        latents = D.gather_latents(latents)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"latents": latents})
     evals = 2 if cfg != 1.0 else 1
     roof = None
     if use_events and plan is not None and plan.prof:
@@ -455,13 +483,13 @@ def main():
                                    f"{evals} evaluation(s) per step; peaks {PEAK_TFLOPS[a.dtype]:.0f} TFLOP/s, 8 TB/s"},
         "roofline": roof,
     }
-    if world == 1 and not a.no_secondary and a.workload == "config3":
+    if a.full and world == 1 and not a.no_secondary and a.workload == "config3":
         sec = {}
         head = a.dtype
 
         def tier_run(tier, Bx, cfgx, snx, cdx, cnd, unc, k, warm):
             net.set_compute_dtype(tier)
-            ex, _ = run_sample(net, device, 0, 1, Bx, cfgx, snx, cdx, cnd, unc, H, W, k, warm, False)
+            ex, _, _ = run_sample(net, device, 0, 1, Bx, cfgx, snx, cdx, cnd, unc, H, W, k, warm, False)
             return {"value": round(Bx * k / ex, 2), "unit": "denoising-steps/s", "ms_per_step": round(ex / k * 1e3, 3)}
 
         # measured price of each 16-bit tier against the all-fp32 tier on identical inputs (global-max norm)
@@ -495,7 +523,7 @@ def main():
         del vae
         net.set_compute_dtype(head)
         out["secondary"] = sec
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(H, W)
         out["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
     else:

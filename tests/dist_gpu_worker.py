@@ -67,7 +67,7 @@ def worker(rank, world, port, q):
             ok = ok and d3 < 5e-5 and d3r < 5e-5          # (measured 1.7e-5 / 2.0e-5 after three CFG steps)
             detail += f"; bf16x3 shard vs unsharded: max-norm rel {d3:.2e}, rms rel {d3r:.2e}"
         # the bench's own sharded path (Philox noise) in the HEADLINE tier, three steps: ranks must produce different, finite samples
-        el, _ = bench.run_sample(net, dev, rank, world, 2, 6.0, "ddpm", True, cond, uncond, H, W, 3, 1, False)
+        el, _, _ = bench.run_sample(net, dev, rank, world, 2, 6.0, "ddpm", True, cond, uncond, H, W, 3, 1, False)
         t = D.max_over_ranks(el, dev)
         ok = ok and t >= el
         D.barrier()

@@ -32,10 +32,10 @@ for r in $(seq 1 $R); do
   case $MODE in
     bench)
       for v in "$@"; do printf "%-52s " "$v"
-        run_variant "$v" timeout -k 10 300 python bench.py --no-cpu-baseline --no-secondary --steps 10 --warmup 2 $EXTRA 2>/dev/null | tail -1 | python3 -c "$JSON_LINE"; done;;
+        run_variant "$v" timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-secondary --steps 10 --warmup 2 $EXTRA 2>/dev/null | tail -1 | python3 -c "$JSON_LINE"; done;;
     small)
       for wl in config2 config1; do for v in "$@"; do printf "%-8s %-44s " $wl "$v"
-        run_variant "$v" timeout -k 10 200 python bench.py --no-cpu-baseline --no-secondary --workload $wl --steps 20 $EXTRA 2>/dev/null | tail -1 | python3 -c "$JSON_LINE"; done; done;;
+        run_variant "$v" timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-secondary --workload $wl --steps 20 $EXTRA 2>/dev/null | tail -1 | python3 -c "$JSON_LINE"; done; done;;
     conv)
       for L in $CONV_LAYERS; do IFS=: read cin cout h w act res <<< "$L"; for v in "$@"; do printf "%-44s " "$v"
         run_variant "$v" timeout -k 10 120 python tools/conv_microbench.py --cin $cin --cout $cout --h $h --w $w --batch 128 --tile 11 --act $act --res $res --iters 10 $EXTRA 2>&1 | tail -1; done; done;;

@@ -5,7 +5,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/b16prof
 rm -rf "$OUT" && mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT" -o run --output-format csv -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-secondary --workload config2 --steps 20 --warmup 3 --dtype $DT > "$OUT/bench.json" 2> "$OUT/err.txt"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-secondary --workload config2 --steps 20 --warmup 3 --dtype $DT > "$OUT/bench.json" 2> "$OUT/err.txt"
 find "$OUT" -name "*kernel_trace.csv" -delete
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, json

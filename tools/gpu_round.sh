@@ -7,10 +7,10 @@ ROOT=$(pwd); OUT=$ROOT/gpurun_out/$TAG; rm -rf "$OUT"; mkdir -p "$OUT"
 timeout -k 10 900 python -m pytest tests -m gpu -x -q "$@" > "$OUT/pytest.txt" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/pytest.txt"
 tail -5 "$OUT/pytest.txt"
 grep -q "pytest rc=0" "$OUT/pytest.txt" || exit 1
-timeout -k 10 400 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { tail -20 "$OUT/bench_default.err"; exit 1; }
+timeout -k 10 400 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { tail -20 "$OUT/bench_default.err"; exit 1; }
 tail -1 "$OUT/bench_default.json" | cut -c1-1500
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run --output-format csv -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-secondary --steps 10 > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-secondary --steps 10 > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
 find "$OUT" -name "*kernel_trace.csv" -delete
 cd "$ROOT"
 python3 - "$TAG" <<'PY'

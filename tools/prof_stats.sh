@@ -2,7 +2,7 @@
 # kernel-time breakdown of the default bench (GPU box): bash tools/prof_stats.sh [bench args]
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/stats_tmp; rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT" -o run --output-format csv -- python3 "$ROOT/bench.py" --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/err.txt"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/err.txt"
 cd "$ROOT"; rm -f "$OUT"/*kernel_trace.csv "$OUT"/*/*kernel_trace.csv
 python3 - <<'PY'
 import csv, glob, sys

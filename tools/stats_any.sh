@@ -3,7 +3,7 @@
 TAG=$1; shift
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/$TAG; rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run --output-format csv -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-secondary "$@" > "$OUT/bench.json" 2> "$OUT/err.txt"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-secondary "$@" > "$OUT/bench.json" 2> "$OUT/err.txt"
 find "$OUT" -name "*kernel_trace.csv" -delete
 cd "$ROOT"
 python3 - "$TAG" <<'PY'

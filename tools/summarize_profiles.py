@@ -75,10 +75,10 @@ bd = last_json(os.path.join(src, "bench_default.json"))
 wl = bd["config"]["workload"]
 key = "config%d/%s/B%d/%s" % (int(wl.split("configs[")[1][0]) + 1, bd["dtype"], bd["config"]["global_batch"] // bd["n_gpus"],
                               wl.split("latent (4,")[1].split(")")[0].replace(",", "x"))
-out = {"note": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python bench.py --no-cpu-baseline "
+out = {"note": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python bench.py --full --no-cpu-baseline "
                "--no-secondary --steps 4 --warmup 3` (the default workload); per-launch averages in bytes. FETCH_SIZE is doubled (gfx950 "
                "reports half of a wide coalesced read, MI355X_MICROARCH.md §HBM); counter unit = KiB.",
-       "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --no-cpu-baseline --no-secondary --steps 4 --warmup 3 (tools/profile_round.sh)",
+       "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --full --no-cpu-baseline --no-secondary --steps 4 --warmup 3 (tools/profile_round.sh)",
        "workload_key": key, "kernels": kern}
 with open(os.path.join(dst, f"{tag}_pmc_hbm_traffic.json"), "w") as f:
     json.dump(out, f, indent=1)
@@ -112,7 +112,7 @@ if mp:
     top = dict(sorted(rows.items(), key=lambda kv: -kv[1]["total_ms"])[:24])
     with open(os.path.join(dst, f"{tag}_pmc_mfma_clock.json"), "w") as f:
         json.dump({"note": "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY "
-                           "SQ_ACTIVE_INST_ANY SQ_INSTS_VALU GRBM_GUI_ACTIVE -- python3 bench.py --no-cpu-baseline --no-secondary --steps 4 --warmup 3. "
+                           "SQ_ACTIVE_INST_ANY SQ_INSTS_VALU GRBM_GUI_ACTIVE -- python3 bench.py --full --no-cpu-baseline --no-secondary --steps 4 --warmup 3. "
                            "mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8); clock_ghz = GRBM_GUI_ACTIVE / 8 / duration "
                            "(reads high on dispatches shorter than ~0.3 ms, MI355X_MICROARCH.md); wave_cycles_split = share of SQ_WAVE_CYCLES spent issuing / "
                            "stalled at issue (pipe busy, dependencies) / parked on s_waitcnt or a barrier. Profiled runs clock lower than un-profiled ones.",
