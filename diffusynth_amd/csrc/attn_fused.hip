@@ -204,8 +204,7 @@ __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_ctx_kernel(
 // blocks per sample: the whole grid is resident at once (2 blocks per CU; 1 for the 384-channel variant) — a second,
 // partial round of blocks would double the kernel's duration
 static inline int out_blocks(int ngroups, int B, int C) {
-    static const int cap96 = getenv("DS_ATTN_CAP") ? atoi(getenv("DS_ATTN_CAP")) : 512;
-    int nb = (C == 384 ? 256 : (C == 96 ? cap96 : 512)) / B;
+    int nb = (C == 384 ? 256 : 512) / B;
     if (nb > ngroups) nb = ngroups;
     if (nb < 1) nb = 1;
     const int per = (ngroups + nb - 1) / nb;
@@ -464,20 +463,16 @@ namespace {
 // against 32 / 52 / 92 / 222 us of the first generation at C = 96, output pass 42 / 62 / 129 / 233 against 35 / 67 / 151 / 272
 static inline bool ctx2_exists(int C, int N) { return C == 96 || C == 192 || (C == 384 && N >= 1024); }
 static inline bool use_ctx2(const ds_attn_fused_params* p) {
-    static const bool off = getenv("DS_ATTN_V1") != nullptr || getenv("DS_ATTN_CTX1") != nullptr;      // A/B switches
-    static const bool no384 = getenv("DS_ATTN_CTX2_NO384") != nullptr;
-    if (off || p->gen == 1 || !ctx2_exists(p->C, p->N) || (p->C == 384 && no384)) return false;
+    if (p->gen == 1 || !ctx2_exists(p->C, p->N)) return false;
     return p->gen == 2 || p->B >= 96;
 }
 static inline bool use_out2(const ds_attn_fused_params* p) {
-    static const bool off = getenv("DS_ATTN_V1") != nullptr;
-    static const bool only96 = getenv("DS_ATTN_OUT2_96") != nullptr;      // A/B switch: first-generation output pass at C = 192
-    if (off || p->gen == 1 || !p->mfold || !(p->C == 96 || (p->C == 192 && !only96))) return false;
+    if (p->gen == 1 || !p->mfold || !(p->C == 96 || p->C == 192)) return false;
     return p->gen == 2 || p->B >= (p->C == 96 ? 32 : 96);
 }
 
 // pixels per group: 64 where the image is large enough to keep every CU busy with fewer, longer iterations
-static inline int group_t(int C, int N) { static const int f = getenv("DS_ATTN_T1") ? 1 : 0; return (C == 96 && N >= 4096 && !f) ? 2 : 1; }
+static inline int group_t(int C, int N) { return (C == 96 && N >= 4096) ? 2 : 1; }
 
 }  // namespace
 

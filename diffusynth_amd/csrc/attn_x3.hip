@@ -901,12 +901,8 @@ extern "C" int ds_attn_x3_context(const ds_attn_x3_params* p, void* stream) {
     else if (p->C == 192) {
         // two launches: k / v for two heads per block (x split twice) and q for all four (once) — as one k / v / q launch the weights of
         // ONE head fill LDS (77 KB), x is staged and split by four head groups, and the kernel is bound by its vector-instruction count
-        static const bool one = getenv("DS_X3_ATTN_192_ONE") != nullptr;      // A/B switch
-        if (one) rc = launch_pass1<12, 1, true, true>(p, st);
-        else {
-            rc = launch_pass1<12, 2, true, false>(p, st);
-            if (!rc) rc = launch_pass1<12, 4, false, true>(p, st);
-        }
+        rc = launch_pass1<12, 2, true, false>(p, st);
+        if (!rc) rc = launch_pass1<12, 4, false, true>(p, st);
     } else {
         rc = launch_pass1<24, 1, true, false>(p, st);
         if (!rc) rc = launch_pass1<24, 2, false, true>(p, st);

@@ -62,7 +62,7 @@ __device__ __attribute__((aligned(16))) float g_gelu_lut[GELU_TAB_N];
 // launch was 2 % SLOWER than the half-empty tiles).  With 512 registers nothing spills; a lone block runs its loop at 0.7 x the paired
 // rate, and half of these launches have only 256 blocks anyway (4 N-blocks x 64 sample pairs at batch 128).
 template <int TWL, bool HP, bool PAIR = false>
-__global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3_halo3_kernel(const ds_conv_params p, const int lut_on) {
+__global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3_halo3_kernel(const ds_conv_params p) {
     static_assert(!PAIR || (HP && TWL == 3), "two samples per block: the 8 x 32 tile of the split-precision instantiation");
     using G = HG<TWL>;
     constexpr int TW = G::TW, TH = G::TH, HCP = G::HCP, NPX = G::NPX, H_IT = G::H_IT, HH0 = G::HH0, HH1 = G::HH1;
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
         }
     }
 #endif
-    const bool use_lut = !HP && G::LUT && lut_on && p.act == DS_ACT_GELU && !raw;
+    const bool use_lut = !HP && G::LUT && p.act == DS_ACT_GELU && !raw;
     static_assert(GELU_TAB_N * 4 <= 2 * NT * 16 && GELU_TAB_N % 4 == 0, "the table is staged as two 16-byte vectors per thread");
     u32x4 lutv = {0u, 0u, 0u, 0u}, lutv2 = {0u, 0u, 0u, 0u};
     if (use_lut) {
@@ -782,8 +782,7 @@ int ds_conv3x3_halo3_launch(const ds_conv_params* p, hipStream_t st) {
     DS_REQUIRE((long long)p->H * p->W * p->out_C * (out_mode == 2 ? 4 : 2) < (1ll << 31), "conv3x3_halo3: one output sample must stay below 2 GiB (32-bit buffer offsets)");
     const int twl = halo3_twl(p->W), TW = 1 << twl, TH = BM >> twl;
     // r05: two samples per block where an image fills at most half of the 8 x 32 tile (the deepest level at 128 x 64 latents: 16 x 8)
-    static const bool no_pair = getenv("DS_NO_HALO3_PAIR") != nullptr;                    // A/B switch
-    const bool pair = !no_pair && p->flags != 0 && twl == 3 && 2 * p->H <= TH && p->W <= TW && p->ksplit <= 1 && !p->res_steps && p->B >= 2;
+    const bool pair = p->flags != 0 && twl == 3 && 2 * p->H <= TH && p->W <= TW && p->ksplit <= 1 && !p->res_steps && p->B >= 2;
     dim3 grid(((p->H + TH - 1) / TH) * ((p->W + TW - 1) / TW), p->cout_pad / BN, pair ? (p->B + 1) / 2 : p->B * (p->ksplit > 1 ? p->ksplit : 1));
 #if DS_BOUNDS
     {
@@ -819,14 +818,10 @@ int ds_conv3x3_halo3_launch(const ds_conv_params* p, hipStream_t st) {
         }
     }
     int lds = twl == 3 ? HG<3>::LDS : (twl == 4 ? HG<4>::LDS : HG<5>::LDS);
-    static const bool no_lut = getenv("DS_HALO3_NOLUT") != nullptr;      // (A/B: the polynomial GELU)
-#if DS_STAMP
-    if (getenv("DS_HALO3_ONEBLOCK")) lds = 100 * 1024;      // diagnostic: one block per CU (lone-wave K loop timing)
-#endif
 #define DS_H3_LAUNCH(TWL_, HP_, PAIR_)                                                                        \
     do {                                                                                               \
         DS_SET_MAX_LDS((conv3x3_halo3_kernel<TWL_, HP_, PAIR_>), 100 * 1024, "conv3x3_halo3");                \
-        hipLaunchKernelGGL((conv3x3_halo3_kernel<TWL_, HP_, PAIR_>), grid, dim3(NT), lds, st, *p, no_lut ? 0 : 1); \
+        hipLaunchKernelGGL((conv3x3_halo3_kernel<TWL_, HP_, PAIR_>), grid, dim3(NT), lds, st, *p);            \
     } while (0)
     if (pair) {
         lds += 64;                      // (the parked GroupNorm pair of the second sample)

@@ -304,7 +304,7 @@ constexpr int ST_XS = ST_HR * ST_ROWB;                  // 61 952
 constexpr int ST_LDS = ST_XS + 49 * 32 * 4 + 64;
 static_assert(LT_SR == 8, "the strip kernel's thread map is the tile kernel's at eight rows per thread");
 
-__global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv_params p, int strips_w, int ncblk, int hparts, int rows_per_part, int order) {
+__global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv_params p, int strips_w, int ncblk, int hparts, int rows_per_part) {
     extern __shared__ __attribute__((aligned(16))) char dsm[];
     char* const xs = dsm;                                                               // ring [22 rows][22 px][8 x 16 B]
     float* const wsm = reinterpret_cast<float*>(dsm + ST_XS);                           // [49][32]
@@ -312,13 +312,9 @@ __global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv
     const int tid = threadIdx.x;
     const int nwg = gridDim.x;
     int wid = blockIdx.x;
-    if ((order & 1) && (nwg & 7) == 0) wid = (wid & 7) * (nwg >> 3) + (wid >> 3);       // XCD-chunked: consecutive items on one XCD
-    int sw, cblk, hp, b;
-    if (order & 2) {                       // strip fastest: the strips of one (sample, channel block) are neighbours in the order
-        sw = wid % strips_w; cblk = (wid / strips_w) % ncblk; hp = (wid / (strips_w * ncblk)) % hparts; b = wid / (strips_w * ncblk * hparts);
-    } else {                               // channel block fastest (the tile kernel's order)
-        cblk = wid % ncblk; sw = (wid / ncblk) % strips_w; hp = (wid / (strips_w * ncblk)) % hparts; b = wid / (strips_w * ncblk * hparts);
-    }
+    if ((nwg & 7) == 0) wid = (wid & 7) * (nwg >> 3) + (wid >> 3);       // XCD-chunked: consecutive items on one XCD
+    // channel block fastest (the tile kernel's order)
+    const int cblk = wid % ncblk, sw = (wid / ncblk) % strips_w, hp = (wid / (strips_w * ncblk)) % hparts, b = wid / (strips_w * ncblk * hparts);
     const int bix = (hp * strips_w + sw) * ncblk + cblk;      // slot in the sample's statistics partials (order-independent sum)
     const int w0 = sw * ST_W, c0 = cblk * 32;
     const int hbeg = hp * rows_per_part, hend = min(p.H, hbeg + rows_per_part);
@@ -415,7 +411,7 @@ __global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv
     for (int t = 0; t < ntile; ++t) {
         const int htop = hbeg + t * ST_R;
         const bool more = t + 1 < ntile;
-        if (more && stager && !(order & 8)) load_rows(hv, htop + ST_R + 3, N16{});          // rows 6 .. 21 of the next tile  (order bits 2..4: timing ablations, wrong results)
+        if (more && stager) load_rows(hv, htop + ST_R + 3, N16{});          // rows 6 .. 21 of the next tile
         // byte offsets of this thread's 14 input rows in the ring
         int roff[LT_SR + 6];
 #pragma unroll
@@ -430,9 +426,8 @@ __global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv
         for (int o = 0; o < LT_SR; ++o)
 #pragma unroll
             for (int v = 0; v < 4; ++v) acc[o][v] = init[v];
-        const int ndw = (order & 16) ? 1 : 7;
 #pragma unroll 1
-        for (int dw = 0; dw < ndw; ++dw) {   // not unrolled: keeps only one tap column of weights + inputs live
+        for (int dw = 0; dw < 7; ++dw) {   // not unrolled: keeps only one tap column of weights + inputs live
             float wv[7][4];
 #pragma unroll
             for (int dh = 0; dh < 7; ++dh) {
@@ -464,7 +459,7 @@ __global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv
 #pragma unroll
         for (int o = 0; o < LT_SR; ++o) {
             const int h = htop + strip * LT_SR + o;
-            if (h < hend && w < p.W && !((order & 4) && acc[o][0] != 12345.f)) {
+            if (h < hend && w < p.W) {
                 if (p.out_split) {
                     bf16* o2 = reinterpret_cast<bf16*>(p.out) + ((size_t)b * p.H * p.W + (size_t)(h * p.W + w)) * (2 * C) + c;
                     uint2 hi, lo;
@@ -1159,9 +1154,8 @@ __global__ __launch_bounds__(192) void gn_apply_lazy_fast_kernel(const ds_gn_app
 }  // namespace
 
 static bool dw_use_mfma(const ds_dwconv_params* p) {
-    static const bool off = getenv("DS_DW_NO_MFMA") != nullptr;   // A/B switch: the LDS-tile stencil kernel
     const long long s0 = (long long)p->H * p->W * p->C0 * 2, s1 = (long long)p->H1 * p->W1 * p->C1 * 2;      // (28-bit halo offsets inside a sample)
-    return p->dtype == DS_BF16 && p->wexp != nullptr && p->C0 % MF_CB == 0 && p->C1 % MF_CB == 0 && !off && s0 < (1ll << 28) && s1 < (1ll << 28);
+    return p->dtype == DS_BF16 && p->wexp != nullptr && p->C0 % MF_CB == 0 && p->C1 % MF_CB == 0 && s0 < (1ll << 28) && s1 < (1ll << 28);
 }
 
 static int lt_nv(const ds_dwconv_params* p) { return (p->dtype == DS_F32 && p->C0 % 32 == 0 && p->C1 % 32 == 0) ? 8 : 4; }
@@ -1174,23 +1168,21 @@ static bool dw_use_lds(const ds_dwconv_params* p) {
 }
 
 // r05: the strip kernel (LDS ring walking down a 16-column strip) for the split-precision tier's depthwise layers.  Chosen by shape AND batch
-// (it needs >= DS_DW_STRIP_MIN_ITEMS blocks, default 512 = two per CU; images of 256 rows may be cut into 2 - 4 row ranges to get there):
-// its outputs are the tile kernel's bit for bit, its statistics partials are grouped differently — like the split-K choices of this tier
-// (DESIGN §3), never taken in the fp32 parity tier unless DS_DW_STRIP=2 asks for it (tests).  DS_DW_STRIP=0: off.
+// (it needs >= 512 blocks = two per CU; images of 256 rows may be cut into 2 - 4 row ranges to get there): its outputs are the tile
+// kernel's bit for bit, its statistics partials are grouped differently — like the split-K choices of this tier, never taken
+// in the fp32 parity tier unless ds_dwconv_params.strip = 1 asks for it (tests).
+constexpr int ST_MIN_ITEMS = 512;
 struct DwStrip { int on, strips_w, ncblk, hparts, rows_per_part; };
 static DwStrip dw_strip(const ds_dwconv_params* p) {
-    static const int mode = getenv("DS_DW_STRIP") ? atoi(getenv("DS_DW_STRIP")) : 1;
-    static const int min_items = getenv("DS_DW_STRIP_MIN_ITEMS") ? atoi(getenv("DS_DW_STRIP_MIN_ITEMS")) : 512;
     DwStrip g{0, 0, 0, 1, 0};
     const bool forced = p->strip == 1;
-    if (p->strip == 2 || (mode == 0 && !forced) || p->dtype != DS_F32 || lt_nv(p) != 8 || !dw_use_lds(p) || (!p->out_split && mode != 2 && !forced) ||
-        p->W < 16 || p->H < 2 * ST_R)
+    if (p->strip == 2 || p->dtype != DS_F32 || lt_nv(p) != 8 || !dw_use_lds(p) || (!p->out_split && !forced) || p->W < 16 || p->H < 2 * ST_R)
         return g;
     g.strips_w = (p->W + ST_W - 1) / ST_W;
     g.ncblk = (p->C0 + p->C1) / 32;
     const long n0 = (long)p->B * g.ncblk * g.strips_w;
-    while (n0 * g.hparts < 2 * min_items && p->H / (2 * g.hparts) >= 2 * ST_R) g.hparts *= 2;
-    if (n0 * g.hparts < min_items && !forced) return g;
+    while (n0 * g.hparts < 2 * ST_MIN_ITEMS && p->H / (2 * g.hparts) >= 2 * ST_R) g.hparts *= 2;
+    if (n0 * g.hparts < ST_MIN_ITEMS && !forced) return g;
     g.rows_per_part = ((p->H + g.hparts - 1) / g.hparts + ST_R - 1) / ST_R * ST_R;
     g.hparts = (p->H + g.rows_per_part - 1) / g.rows_per_part;
     g.on = 1;
@@ -1258,18 +1250,12 @@ extern "C" int ds_dwconv7(const ds_dwconv_params* p, void* stream) {
         return DS_OK;
     }
     if (const DwStrip g = dw_strip(p); g.on) {
-        // bit 0: XCD-chunked item order (consecutive items = the channel blocks of one strip on ONE XCD: the 64-byte halves of an output line
-        // two channel blocks share merge in that L2; +2 % on 8 of 9 layer shapes, same box), bit 1: strip fastest instead of channel block
-        // fastest (no consistent gain); bits 2 - 4 (honoured by -DDS_DW_ABL builds only) are timing ablations with WRONG results (no output stores / no refill loads / one tap column
-        // instead of seven) — r05 at C = 96, 256 x 64, batch 128: 555 us whole; arithmetic alone 347 (784 v_pk_fma_f32 per thread and tile:
-        // ~12 k cycles per pair of co-resident tiles against 6.3 k of issue slots), stores alone 264, loads alone 157, none of them 111
-#ifdef DS_DW_ABL          // diagnostic builds only (tools/build_variants.py abl=-DDS_DW_ABL=1): the product library ignores the ablation bits
-        static const int order = getenv("DS_DW_STRIP_ORDER") ? atoi(getenv("DS_DW_STRIP_ORDER")) : 1;
-#else
-        static const int order = (getenv("DS_DW_STRIP_ORDER") ? atoi(getenv("DS_DW_STRIP_ORDER")) : 1) & 3;
-#endif
+        // XCD-chunked item order (consecutive items = the channel blocks of one strip on ONE XCD: the 64-byte halves of an output line two
+        // channel blocks share merge in that L2; +2 % on 8 of 9 layer shapes, same box; strip fastest instead of channel block fastest: no
+        // consistent gain).  r05 timing ablations at C = 96, 256 x 64, batch 128: 555 us whole; arithmetic alone 347 (784 v_pk_fma_f32 per
+        // thread and tile: ~12 k cycles per pair of co-resident tiles against 6.3 k of issue slots), stores alone 264, loads alone 157, none 111
         DS_SET_MAX_LDS(dwconv7_strip_kernel, ST_LDS, "dwconv7_strip");
-        hipLaunchKernelGGL(dwconv7_strip_kernel, dim3(blocks * p->B), dim3(ST_NT), ST_LDS, st, *p, g.strips_w, g.ncblk, g.hparts, g.rows_per_part, order);
+        hipLaunchKernelGGL(dwconv7_strip_kernel, dim3(blocks * p->B), dim3(ST_NT), ST_LDS, st, *p, g.strips_w, g.ncblk, g.hparts, g.rows_per_part);
         DS_CHECK_LAUNCH("dwconv7_strip");
         return DS_OK;
     }
@@ -1387,7 +1373,7 @@ extern "C" int ds_gn_apply(const ds_gn_apply_params* p, void* stream) {
         h.publish(st);
     }
 #endif
-    if (p->gn_part && p->dtype == DS_BF16 && p->act == DS_ACT_NONE && !p->cbias && 192 % (p->C / 8) == 0 && !getenv("DS_NO_GN_FAST")) {
+    if (p->gn_part && p->dtype == DS_BF16 && p->act == DS_ACT_NONE && !p->cbias && 192 % (p->C / 8) == 0) {
         const int rows = 192 / (p->C / 8);
         int bx = (p->HW + rows * 4 - 1) / (rows * 4);
         const int cap = 4096 / p->B > 0 ? 4096 / p->B : 1;
@@ -1410,8 +1396,7 @@ extern "C" int ds_gn_apply(const ds_gn_apply_params* p, void* stream) {
     }
     // (every tier, every G since r04: the per-channel (scale, shift) table kernel — its SiLU is exp2f + v_rcp_f32, ~1 ulp each, where the
     // element-wise kernel below uses libm's expf and a true divide: the fp32 tier's bits differ from r03's by that much)
-    static const bool no_table = getenv("DS_NO_GN_TABLE") != nullptr;
-    if (p->gn_ab && p->C / V <= 256 && p->C * 8 <= 48 * 1024 && !no_table) {
+    if (p->gn_ab && p->C / V <= 256 && p->C * 8 <= 48 * 1024) {
         const int CV = p->C / V, threads = CV * (256 / CV), rows = threads / CV;
         int bx = (p->HW + rows * 8 - 1) / (rows * 8);                        // >= 8 pixels per thread
         const int cap = 8192 / p->B > 0 ? 8192 / p->B : 1;

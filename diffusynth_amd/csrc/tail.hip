@@ -210,96 +210,16 @@ __global__ void decoder_tail_kernel(const T* x, int Cs, int HW, float* out, size
 }
 
 // ------------------------------------------------------------------------------------------------ iSTFT
-// One block per (frame, sample): rebuild the Hermitian spectrum from ISTFT+ (mag = expm1(c0),
-// phase = atan2(sin, cos); the DC row is zero: tools.py:185-191), 1024-point radix-2 inverse FFT in LDS,
-// multiply by the periodic Hann window, store the frame.
+// Rebuild the Hermitian spectrum from ISTFT+ (mag = expm1(c0), phase = atan2(sin, cos); the DC row is zero: tools.py:185-191),
+// 1024-point inverse FFT in LDS, multiply by the periodic Hann window, store the frame.
 constexpr int NFFT = 1024;
 constexpr int IF_FR = 4;      // frames per block
 // One block = IF_FR consecutive frames of one sample.  The representation is [3][F][T] (time fastest): a block that owns
 // ONE frame reads its 3 x 512 values with a stride of T floats (a 64-byte line per 4 useful bytes).  With four frames per
-// block a thread fetches one 16-byte piece (4 frames of one bin) per channel, the twiddle factors e^{2 pi i j / 1024} are
-// tabulated once per block in LDS instead of one sincospif per butterfly, and the four FFTs share every index computation.
-__global__ __launch_bounds__(256) void istft_frames_kernel(const float* enc, int F, int T, float* frames) {
-    __shared__ float re[IF_FR][NFFT], im[IF_FR][NFFT];
-    __shared__ float twc[NFFT / 2], tws[NFFT / 2];
-    const int t0 = blockIdx.x * IF_FR, b = blockIdx.y, tid = threadIdx.x;
-    const float* e0 = enc + (size_t)b * 3 * F * T;
-    for (int j = tid; j < NFFT / 2; j += 256) sincospif(2.0f * (float)j / (float)NFFT, &tws[j], &twc[j]);
-    // (every offset below is a multiple of 4 floats when T % 4 == 0, so the 16-byte loads are aligned iff enc is: a view with an odd
-    // storage offset takes the scalar path)
-    const bool vec_ok = (T % 4 == 0) && t0 + IF_FR <= T && (reinterpret_cast<uintptr_t>(enc) & 15) == 0;
-    // bins 1..F from rows 0..F-1; bin 0 = 0; bins F+1..2F-1 by conjugate symmetry.  Stored bit-reversed.
-    for (int kk = tid + 1; kk <= F; kk += 256) {
-        float c0[IF_FR], c1[IF_FR], c2[IF_FR];
-        const size_t o = (size_t)(kk - 1) * T + t0;
-        if (vec_ok) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(e0 + o), c = *reinterpret_cast<const f32x4*>(e0 + (size_t)F * T + o),
-                        s = *reinterpret_cast<const f32x4*>(e0 + 2 * (size_t)F * T + o);
-#pragma unroll
-            for (int f = 0; f < IF_FR; ++f) { c0[f] = a[f]; c1[f] = c[f]; c2[f] = s[f]; }
-        } else {
-#pragma unroll
-            for (int f = 0; f < IF_FR; ++f) {
-                const bool ok = t0 + f < T;
-                c0[f] = ok ? e0[o + f] : 0.f;
-                c1[f] = ok ? e0[(size_t)F * T + o + f] : 1.f;
-                c2[f] = ok ? e0[2 * (size_t)F * T + o + f] : 0.f;
-            }
-        }
-        const int r = __brev((unsigned)kk) >> 22, rm = __brev((unsigned)(NFFT - kk)) >> 22;   // 10-bit reversal
-#pragma unroll
-        for (int f = 0; f < IF_FR; ++f) {
-            // mag * exp(i atan2(sin, cos)) = mag * (cos, sin) / |(cos, sin)| — no atan2f / cosf / sinf (three libm calls per bin were half of
-            // this kernel's 168 us); atan2(0, 0) = 0 in the reference's formula: (mag, 0)
-            const float mag = expm1f(c0[f]);
-            // (the pair is first scaled by an exact power of two so that max(|cos|, |sin|) lies in [0.5, 1): c^2 + s^2 neither underflows —
-            // v_rsq_f32 returns +inf for a denormal argument, and a pair of 1e-23s used to lose its phase to n2 == 0 — nor overflows)
-            const float pm = fmaxf(fabsf(c1[f]), fabsf(c2[f]));
-            const bool z0 = !(pm > 0.f) || !(pm < 3.0e38f);               // 0 (and nothing finite): the reference's phase is 0 (resp. undefined)
-            const int pe = z0 ? 0 : __builtin_amdgcn_frexp_expf(pm);
-            const float pa = ldexpf(c1[f], -pe), pb = ldexpf(c2[f], -pe);
-            const float n2 = pa * pa + pb * pb;                           // in [0.25, 2)
-            float ri = __builtin_amdgcn_rsqf(n2);
-            ri = ri * (1.5f - 0.5f * n2 * ri * ri);                       // one Newton step: v_rsq_f32 alone is ~1 ulp
-            const float xr = z0 ? mag : mag * (pa * ri), xi = z0 ? 0.f : mag * (pb * ri);
-            re[f][r] = xr;
-            im[f][r] = xi;
-            if (kk < F) {                    // the mirrored bin NFFT - kk (kk = F is its own mirror)
-                re[f][rm] = xr;
-                im[f][rm] = -xi;
-            }
-        }
-    }
-    if (tid < IF_FR) {
-        re[tid][0] = 0.f;                    // DC (bit reversal of 0)
-        im[tid][0] = 0.f;
-    }
-    __syncthreads();
-    for (int len = 2, shift = 9; len <= NFFT; len <<= 1, --shift) {
-        const int half = len >> 1;
-        for (int j = tid; j < NFFT / 2; j += 256) {
-            const int grp = j / half, pos = j - grp * half;
-            const int i0 = grp * len + pos, i1 = i0 + half;
-            const float c = twc[pos << shift], s = tws[pos << shift];      // e^{+2 pi i pos/len}: inverse transform
-#pragma unroll
-            for (int f = 0; f < IF_FR; ++f) {
-                const float tr = re[f][i1] * c - im[f][i1] * s, ti = re[f][i1] * s + im[f][i1] * c;
-                const float ur = re[f][i0], ui = im[f][i0];
-                re[f][i0] = ur + tr; im[f][i0] = ui + ti;
-                re[f][i1] = ur - tr; im[f][i1] = ui - ti;
-            }
-        }
-        __syncthreads();
-    }
-    for (int n = tid; n < NFFT; n += 256) {
-        const float w = 0.5f - 0.5f * (n < NFFT / 2 ? twc[n] : -twc[n - NFFT / 2]);   // periodic Hann from the same table
-#pragma unroll
-        for (int f = 0; f < IF_FR; ++f)
-            if (t0 + f < T) frames[((size_t)b * T + t0 + f) * NFFT + n] = re[f][n] * (1.0f / NFFT) * w;
-    }
-}
-
-// ---- r04: the same frames by a radix-4 Stockham transform.  The radix-2 kernel above is bound by its LDS traffic: ten passes of 4-byte
+// block a thread fetches one 16-byte piece (4 frames of one bin) per channel, the twiddle factors are tabulated once per block
+// in LDS, and the four FFTs share every index computation.
+//
+// r04: a radix-4 Stockham transform.  The radix-2 kernel it replaced was bound by its LDS traffic: ten passes of 4-byte
 // reads / writes, 200 LDS operations per thread and frame, 164 us at 64 x 256 frames.  Here a thread owns ONE radix-4 butterfly per frame and
 // pass: five passes between two buffers (autosort: natural order in, natural order out, no bit reversal), 8-byte complex elements, reads
 // contiguous across the wave, three twiddles from one table entry (w, w^2, w^3) — 40 LDS operations per thread and frame.
@@ -337,9 +257,13 @@ __global__ __launch_bounds__(256) void istft_frames_r4_kernel(const float* enc, 
         }
 #pragma unroll
         for (int f = 0; f < IF_FR; ++f) {
+            // mag * exp(i atan2(sin, cos)) = mag * (cos, sin) / |(cos, sin)| — no atan2f / cosf / sinf (three libm calls per bin were half of
+            // the first kernel's 168 us); atan2(0, 0) = 0 in the reference's formula: (mag, 0)
             const float mag = expm1f(c0[f]);
-            const float pm = fmaxf(fabsf(c1[f]), fabsf(c2[f]));           // (power-of-two prescale: see the radix-2 kernel above)
-            const bool z0 = !(pm > 0.f) || !(pm < 3.0e38f);
+            // (the pair is first scaled by an exact power of two so that max(|cos|, |sin|) lies in [0.5, 1): c^2 + s^2 neither underflows —
+            // v_rsq_f32 returns +inf for a denormal argument, and a pair of 1e-23s used to lose its phase to n2 == 0 — nor overflows)
+            const float pm = fmaxf(fabsf(c1[f]), fabsf(c2[f]));
+            const bool z0 = !(pm > 0.f) || !(pm < 3.0e38f);               // 0 (and nothing finite): the reference's phase is 0 (resp. undefined)
             const int pe = z0 ? 0 : __builtin_amdgcn_frexp_expf(pm);
             const float pa = ldexpf(c1[f], -pe), pb = ldexpf(c2[f], -pe);
             const float n2 = pa * pa + pb * pb;
@@ -481,8 +405,7 @@ extern "C" int ds_vq_nearest(const float* z, const float* cb, const float* esq, 
     DS_REQUIRE(D == 4, "vq_nearest: embedding_dim %d unsupported (4 only)", D);
     const size_t npix = (size_t)B * HW;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    static const bool scalar = getenv("DS_VQ_SCALAR") != nullptr;          // A/B switch: the r01 kernel
-    if (ncodes <= VQ_MAXC && !scalar) {
+    if (ncodes <= VQ_MAXC) {
         // matrix-core search: the codebook is re-packed per call (it is a module parameter: no caching across calls), 3 us
         const int ntiles = (ncodes + 15) / 16;
         hipLaunchKernelGGL(vq_pack_kernel, dim3((ntiles * 64 + 255) / 256), dim3(256), 0, st, cb, esq, ncodes, ntiles);
@@ -594,12 +517,8 @@ extern "C" int ds_istft_plus(const float* enc, int B, int F, int T, int hop, flo
     DS_REQUIRE(2 * F == NFFT, "istft_plus: n_fft = 2*F must be %d (got F=%d)", NFFT, F);
     DS_REQUIRE(NFFT % hop == 0, "istft_plus: hop %d must divide n_fft", hop);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    static const bool r2 = getenv("DS_ISTFT_R2") != nullptr;              // A/B switch: the radix-2 kernel
-    if (r2) hipLaunchKernelGGL(istft_frames_kernel, dim3((T + IF_FR - 1) / IF_FR, B), dim3(256), 0, st, enc, F, T, ws);
-    else {
-        DS_SET_MAX_LDS(istft_frames_r4_kernel, R4_LDS, "istft_frames_r4");
-        hipLaunchKernelGGL(istft_frames_r4_kernel, dim3((T + IF_FR - 1) / IF_FR, B), dim3(256), R4_LDS, st, enc, F, T, ws);
-    }
+    DS_SET_MAX_LDS(istft_frames_r4_kernel, R4_LDS, "istft_frames_r4");
+    hipLaunchKernelGGL(istft_frames_r4_kernel, dim3((T + IF_FR - 1) / IF_FR, B), dim3(256), R4_LDS, st, enc, F, T, ws);
     DS_CHECK_LAUNCH("istft_frames");
     const int L = hop * (T - 1);
     hipLaunchKernelGGL(istft_ola_kernel, dim3((L + 255) / 256, B), dim3(256), 0, st, ws, T, hop, audio, L);

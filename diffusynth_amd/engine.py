@@ -18,6 +18,7 @@ from . import _lib as L
 
 _ESIZE = {L.DS_F32: 4, L.DS_BF16: 2}
 _TDT = {L.DS_F32: torch.float32, L.DS_BF16: torch.bfloat16}
+KSPLIT_FILL = 256        # split K until this many blocks exist (256 CUs)
 
 
 def _up(x, m):
@@ -144,7 +145,6 @@ class _EngineBase:
     """Shared by the U-Net and the VQGAN-decoder engines: dtype bookkeeping and weight packing."""
 
     def _init_common(self, module, compute_dtype):
-        import os
         L.load()
         self.m = module
         self.dt = L.DS_BF16 if compute_dtype == "bf16" else L.DS_F32
@@ -158,22 +158,7 @@ class _EngineBase:
             raise RuntimeError("parameters must live on a HIP device ('cuda'); diffusynth_amd has no CPU path")
         self.plans = {}
         self._keep = []          # packed tensors
-        self.use_halo = os.environ.get("DS_NO_HALO", "0") != "1"    # A/B switch: LDS-halo 3x3 kernel (conv3x3_halo3.hip); off = generic implicit GEMM
-        self.cond_async = os.environ.get("DS_NO_COND_ASYNC", "0") != "1"  # A/B switch: conditioning GEMVs on a side stream
         self.side_stream = None
-        self.use_smalln = os.environ.get("DS_NO_SMALLN", "0") != "1"  # A/B switch: few-output 3x3 (final conv) on its own kernel
-        self.use_x3 = os.environ.get("DS_NO_X3", "0") != "1"        # A/B switch: 1x1 convolutions of the split-precision tier on bf16 MFMAs (conv1x1_x3.hip)
-        self.use_quad = os.environ.get("DS_NO_QUAD", "0") != "1"    # A/B switch: 4x4 stride-2 / transposed convolutions on the halo pipeline
-        self.use_f32n4 = os.environ.get("DS_NO_F32N4", "0") != "1"  # A/B switch: fp32 few-output 3x3 (final conv of the fp32 tiers) on conv3x3_f32_n4.hip
-        self.use_init7 = os.environ.get("DS_NO_INIT7", "0") != "1"  # A/B switch: the 7x7 init convolution on its own kernel (conv7x7_c4.hip)
-        self.use_resfuse = os.environ.get("DS_NO_RESFUSE", "0") != "1"  # A/B switch: res_conv 1x1 fused into the second 3x3's K loop
-        self.use_splitk = os.environ.get("DS_NO_SPLITK", "0") != "1"
-        self.ksplit_fill = int(os.environ.get("DS_KSPLIT_FILL", "256"))   # split K until this many blocks exist (256 CUs); A/B knob
-        self.use_fused_attn = os.environ.get("DS_NO_FUSED_ATTN", "0") != "1"
-        self.use_cfg_pair = os.environ.get("DS_NO_CFG_PAIR", "0") != "1"   # A/B switch: shared prefix of a classifier-free-guidance batch computed once
-        self.use_x3_attn = os.environ.get("DS_NO_X3_ATTN", "0") != "1"   # A/B switch: fused split-precision attention (attn_x3.hip) in the bf16x3 tier
-        self.lazy_gn = os.environ.get("DS_NO_LAZY_GN", "0") != "1"
-        self.use_dw_mfma = os.environ.get("DS_NO_DW_MFMA", "0") != "1"    # consumers reduce GroupNorm partials themselves
         self._tb_total = 0
         self._lab_total = 0
         self._pack_tmp = []      # packing inputs kept alive until _pack_done(): ONE stream sync per model, not one per tensor
@@ -241,7 +226,7 @@ class _EngineBase:
         cw.Cout, cw.cout_pad, cw.cin_pad, cw.KH, cw.KW, cw.bn, cw.transposed = Cout, _up(Cout, bn), cin_pad, KH, KW, bn, transposed
         cw.cin_real = Cin
         cw.k_order = 1 if (halo and self.dt == L.DS_BF16 and KH == 3 and KW == 3 and not transposed and cin_pad % 32 == 0
-                           and bn in (96, 192) and self.use_halo) else 0
+                           and bn in (96, 192)) else 0
         n = L.load().ds_pack_conv_elems(cin_pad, KH, KW, cw.cout_pad, 1 if transposed else 0)
         cw.w = torch.empty(n, dtype=_TDT[self.dt], device=self.dev)
         g = self._f32(gamma) if gamma is not None else None
@@ -256,15 +241,15 @@ class _EngineBase:
         cw.w_init7 = None
         cw.w_f32n4 = None
         cw.w_x3, cw.x3_cout_pad = None, 0
-        if (self.dt == L.DS_F32 and self.use_f32n4 and gamma is None and KH == 3 and KW == 3 and not transposed and Cout <= 4 and cin_pad == Cin
+        if (self.dt == L.DS_F32 and gamma is None and KH == 3 and KW == 3 and not transposed and Cout <= 4 and cin_pad == Cin
                 and Cin % 32 == 0):
             # few-output 3x3 of the fp32 / split-precision tiers (the final 96 -> 4 convolution): vector-ALU kernel, weights through scalar loads
             cw.w_f32n4 = torch.empty(L.load().ds_conv3x3_f32_n4_weight_floats(Cin), dtype=torch.float32, device=self.dev)
             L.call("ds_pack_conv3x3_f32_n4", w.data_ptr(), L.ptr(cw.bias), Cout, Cin, cw.w_f32n4.data_ptr(), L.current_stream())
-        if self.split3 and self.use_x3 and KH == 1 and KW == 1 and not transposed and cin_pad == Cin and Cin % 32 == 0 and Cout % 8 == 0:
+        if self.split3 and KH == 1 and KW == 1 and not transposed and cin_pad == Cin and Cin % 32 == 0 and Cout % 8 == 0:
             # 1x1 convolutions of the split-precision tier (to_qkv, to_out, res_conv): pre-split weights for ds_conv1x1_x3
             cw.w_x3, cw.x3_cout_pad = pack_x3_1x1(weight.to(self.dev), gamma.to(self.dev) if gamma is not None else None)
-        if (self.dt == L.DS_BF16 and self.use_smalln and gamma is None and KH == 3 and KW == 3 and not transposed and Cout <= 16
+        if (self.dt == L.DS_BF16 and gamma is None and KH == 3 and KW == 3 and not transposed and Cout <= 16
                 and cin_pad == Cin and Cin % 32 == 0):
             # few-output 3x3 (the final 96 -> 4 convolution): chunk-major tiles with 16 output rows for conv3x3_smalln.hip
             n16 = L.load().ds_pack_conv_elems(Cin, 3, 3, 16, 0)
@@ -282,7 +267,7 @@ class _EngineBase:
             L.call("ds_pack_conv_weight", C.byref(pps), L.current_stream())
             self._pack_tmp.append(ws)
         wshape = tuple(weight.shape)
-        if ((self.dt == L.DS_BF16 or (self.split3 and Cout % 8 == 0)) and self.use_quad and gamma is None and cin_pad == Cin and Cin % 32 == 0 and wshape[2:] == (4, 4)
+        if ((self.dt == L.DS_BF16 or (self.split3 and Cout % 8 == 0)) and gamma is None and cin_pad == Cin and Cin % 32 == 0 and wshape[2:] == (4, 4)
                 and ((transposed and (Cin // 32) % 6 == 0 and Cout % 96 == 0) or (not transposed and (Cin // 32) % 3 == 0))):
             # Downsample / Upsample of the U-Net: also packed as quad tiles for the halo kernel (conv_quad_halo3.hip); in the split-precision
             # tier as [W_hi | W_hi | W_lo] over 3 Cin input channels (the kernel then reads hi / lo planes: DS_CONV_F_SPLIT_IN)
@@ -307,6 +292,8 @@ class _EngineBase:
 
 
 class UnetEngine(_EngineBase):
+    use_cfg_pair = True      # shared prefix of a classifier-free-guidance batch computed once (tests switch it off to compare)
+
     def __init__(self, module, compute_dtype="fp32"):
         self._init_common(module, compute_dtype)
         self.cfg = module.config
@@ -325,7 +312,7 @@ class UnetEngine(_EngineBase):
             self._pack_tmp.append(w)
             d["dw"], d["dw_bias"] = dw, self._f32(blk.ds_conv.bias)
             d["dw_exp"] = None
-            if self.dt == L.DS_BF16 and C_ % 32 == 0 and self.use_dw_mfma:
+            if self.dt == L.DS_BF16 and C_ % 32 == 0:
                 we = torch.empty(C_ * 6 * 64 * 8, dtype=torch.bfloat16, device=self.dev)
                 L.call("ds_pack_dw_weight_mfma", w.data_ptr(), C_, we.data_ptr(), L.current_stream())
                 d["dw_exp"] = we
@@ -345,7 +332,7 @@ class UnetEngine(_EngineBase):
             d["res"] = self._pack_conv(blk.res_conv.weight, blk.res_conv.bias)
             c2 = d["conv2"]
             cx = blk.res_conv.weight.shape[1]
-            if c2.k_order == 1 and cx % 96 == 0 and self.use_resfuse:      # (the fused steps come in threes: the weight ring's phase)
+            if c2.k_order == 1 and cx % 96 == 0:      # (the fused steps come in threes: the weight ring's phase)
                 # components:128,139 fused into conv2's launch: the 1x1 tiles ([cx/32][cout_pad][32]) precede the 3x3 tiles
                 # (a second copy: the unfused fallback — split-K at small batch — keeps reading cw.w)
                 w = self._f32(blk.res_conv.weight)
@@ -374,7 +361,7 @@ class UnetEngine(_EngineBase):
         d["l_off"] = self._lab_total
         d["fused"] = None
         Cc = d["C"]
-        if self.dt == L.DS_BF16 and self.cfg["attn_type"] == "linear_add" and Cc in (96, 192, 384) and self.use_fused_attn:
+        if self.dt == L.DS_BF16 and self.cfg["attn_type"] == "linear_add" and Cc in (96, 192, 384):
             wq = self._f32(a.to_qkv.weight).reshape(384, Cc).contiguous()
             wo = self._f32(a.to_out[0].weight).reshape(Cc, 128).contiguous()
             g = self._f32(pre.norm.weight)
@@ -384,7 +371,7 @@ class UnetEngine(_EngineBase):
             self._pack_tmp += [wq, wo, g]
             d["fused"] = (wq16, wo16)
         d["x3"] = None
-        if self.split3 and self.cfg["attn_type"] == "linear_add" and Cc in (96, 192, 384) and self.use_x3_attn:
+        if self.split3 and self.cfg["attn_type"] == "linear_add" and Cc in (96, 192, 384):
             # split-precision tier: the whole block on attn_x3.hip (no qkv tensor): to_qkv * PreNorm gain as hi / lo bf16 planes, to_out in fp32
             wq = self._f32(a.to_qkv.weight).reshape(384, Cc).contiguous()
             g = self._f32(pre.norm.weight)
@@ -411,7 +398,7 @@ class UnetEngine(_EngineBase):
         P = {}
         P["init"] = self._pack_conv(m.init_conv.weight, m.init_conv.bias, cin_pad=self.cin0)
         w0 = m.init_conv.weight
-        if (self.dt == L.DS_BF16 and self.use_init7 and tuple(w0.shape[2:]) == (7, 7) and w0.shape[0] == 96 and w0.shape[1] <= 4
+        if (self.dt == L.DS_BF16 and tuple(w0.shape[2:]) == (7, 7) and w0.shape[0] == 96 and w0.shape[1] <= 4
                 and self.cin0 in (4, 8)):
             # the init convolution on its own kernel: four real channels = 8 bytes per pixel, a K step = one kernel row read straight from a halo
             wf = self._f32(w0)
@@ -420,7 +407,7 @@ class UnetEngine(_EngineBase):
             self._pack_tmp.append(wf)
             P["init"].w_init7 = w7
         P["init"].w_init7x3 = None
-        if (self.split3 and self.use_init7 and tuple(w0.shape[2:]) == (7, 7) and w0.shape[0] == 96 and w0.shape[1] <= 4 and self.cin0 == 4):
+        if (self.split3 and tuple(w0.shape[2:]) == (7, 7) and w0.shape[0] == 96 and w0.shape[1] <= 4 and self.cin0 == 4):
             # split-precision tier: the same kernel with the fp32 input split into hi / lo bf16 on its way to LDS, fp32 output
             wf = self._f32(w0)
             w7 = torch.empty(2 * L.load().ds_conv7x7_c4_weight_elems(), dtype=torch.bfloat16, device=self.dev)
@@ -542,9 +529,7 @@ class _PlanBuilder:
         One of the tiling decisions that look at the batch (the others: the split-K of Down / Upsample and conv1x1_x3, the attention
         segments), 16-bit tiers only; fp32 never splits (batch-invariant bit for bit).  The batch looked at is the plan's FULL batch
         (self.Btile), not the half batch of a paired plan's shared prefix."""
-        e, B = self.e, self.Btile
-        if not e.use_splitk:
-            return 1
+        B = self.Btile
         twl = 3
         while (1 << twl) < W and twl < 5:
             twl += 1
@@ -555,14 +540,14 @@ class _PlanBuilder:
         # the smallest factor that fills the chip, else the largest possible (r04: 3 and 6 — every channel count is a multiple of 96, so chunk
         # counts of 3, 9, 18 had no power-of-two slice: a 96 -> 192 layer at 256 x 64, batch 1, ran as 128 blocks of 81 steps)
         ok = [c for c in (2, 3, 4, 6, 8) if ncc % c == 0 and ncc // c >= (1 if split else 2)]
-        if not split or os.environ.get("DS_KSPLIT_POW2", "0") == "1":      # (the bf16 tier gains nothing from the 3s: same-box A/B, batch 1 and 16)
+        if not split:      # (the bf16 tier gains nothing from the 3s: same-box A/B, batch 1 and 16)
             ok = [c for c in ok if c in (2, 4, 8)]
         ks = 1
         for c in ok:
             ks = c
-            if pn * B * c >= e.ksplit_fill:
+            if pn * B * c >= KSPLIT_FILL:
                 break
-        if pn * B >= e.ksplit_fill:
+        if pn * B >= KSPLIT_FILL:
             ks = 1
         return ks
 
@@ -661,23 +646,22 @@ class _PlanBuilder:
                 p.ksplit, p.slab = ks, slab[0]
         elif tile == L.TILE_QUAD_HALO3:
             # Down / Upsample on the halo pipeline (r04): K slices of whole groups of six chunks (the kernel's loop period)
-            if e.use_splitk:
-                twl = 3
-                while (1 << twl) < Wo and twl < 5:
-                    twl += 1
-                nblk = (-(-Ho // (256 >> twl))) * (-(-Wo // (1 << twl))) * (cw.quad_cout_pad // 96) * self.Btile
-                nch = (1 if cw.transposed else 4) * ((3 * src0.C // 32) if e.split3 else src0.C // 32)
-                ks = 1
-                if nblk < e.ksplit_fill:
-                    for c in ((2, 3, 4, 6, 8) if e.split3 else (2, 4, 8)):
-                        if nch % c == 0 and (nch // c) % 6 == 0:
-                            ks = c
-                            if nblk * c >= e.ksplit_fill:
-                                break
-                if ks > 1:
-                    slab = self.raw(ks * B * oh * ow * _up(cw.Cout, 8) * 4)
-                    p.ksplit, p.slab = ks, slab[0]
-        elif e.dt == L.DS_BF16 and e.use_splitk and tile in (L.TILE_64x192, L.TILE_128x192, L.TILE_256x96):
+            twl = 3
+            while (1 << twl) < Wo and twl < 5:
+                twl += 1
+            nblk = (-(-Ho // (256 >> twl))) * (-(-Wo // (1 << twl))) * (cw.quad_cout_pad // 96) * self.Btile
+            nch = (1 if cw.transposed else 4) * ((3 * src0.C // 32) if e.split3 else src0.C // 32)
+            ks = 1
+            if nblk < KSPLIT_FILL:
+                for c in ((2, 3, 4, 6, 8) if e.split3 else (2, 4, 8)):
+                    if nch % c == 0 and (nch // c) % 6 == 0:
+                        ks = c
+                        if nblk * c >= KSPLIT_FILL:
+                            break
+            if ks > 1:
+                slab = self.raw(ks * B * oh * ow * _up(cw.Cout, 8) * 4)
+                p.ksplit, p.slab = ks, slab[0]
+        elif e.dt == L.DS_BF16 and tile in (L.TILE_64x192, L.TILE_128x192, L.TILE_256x96):
             # same idea for the generic kernel (4x4 stride-2, transposed and 1x1 layers of the small-spatial levels):
             # their K loops are long (up to 192 steps) and their grids small
             bm_, bn_ = {L.TILE_64x192: (64, 192), L.TILE_128x192: (128, 192), L.TILE_256x96: (256, 96)}[tile]
@@ -695,18 +679,17 @@ class _PlanBuilder:
                 and src0.C % 32 == 0 and C1 % 32 == 0 and res_fuse is None and slab is None):
             # split-precision tier: 1x1 convolution of fp32 tensors as three bf16 MFMA products (conv1x1_x3.hip)
             p.dtype, p.flags, p.wpk, p.cout_pad, p.wk_order, p.tile = L.DS_BF16, 8 | 4, cw.w_x3.data_ptr(), cw.x3_cout_pad, 0, 0
-            if e.use_splitk:
-                # K slices at small batches (r04): res_conv of a 64 x 16-level block at batch 1 was 16 blocks of 24 - 36 serial chunks
-                nblk, nq, ks = (-(-(Ho * Wo) // 256)) * (cw.x3_cout_pad // 96) * self.Btile, (src0.C + C1) // 32, 1
-                if nblk < e.ksplit_fill:
-                    for c in (2, 3, 4, 6, 8):
-                        if nq // c >= 3 and (c - 1) * (-(-nq // c)) < nq:
-                            ks = c
-                            if nblk * c >= e.ksplit_fill:
-                                break
-                if ks > 1:
-                    slab = self.raw(ks * B * Ho * Wo * _up(cw.Cout, 8) * 4)
-                    p.ksplit, p.slab = ks, slab[0]
+            # K slices at small batches (r04): res_conv of a 64 x 16-level block at batch 1 was 16 blocks of 24 - 36 serial chunks
+            nblk, nq, ks = (-(-(Ho * Wo) // 256)) * (cw.x3_cout_pad // 96) * self.Btile, (src0.C + C1) // 32, 1
+            if nblk < KSPLIT_FILL:
+                for c in (2, 3, 4, 6, 8):
+                    if nq // c >= 3 and (c - 1) * (-(-nq // c)) < nq:
+                        ks = c
+                        if nblk * c >= KSPLIT_FILL:
+                            break
+            if ks > 1:
+                slab = self.raw(ks * B * Ho * Wo * _up(cw.Cout, 8) * 4)
+                p.ksplit, p.slab = ks, slab[0]
             if want_stats:
                 parts = self.lib.ds_conv1x1_x3_stats_parts(C.byref(p))
                 st = self.raw(B * parts * 2 * 4)
@@ -741,16 +724,12 @@ class _PlanBuilder:
     def dup(self, a):
         """Both halves of a full-batch activation = the half-batch activation ``a`` (incl. its GroupNorm partials); self.B is the full batch."""
         nb = (self.B // 2) * a.H * a.W * a.C * self.e.es
-        if a.nbytes >= 2 * nb and os.environ.get("DS_DUP_COPY", "0") != "1":
-            # r05: `a` was carved at full size and holds the prefix in its first half: one read + one write instead of one + two
-            out = _Act(a.off, a.nbytes, a.C, a.H, a.W)
-            out.split = getattr(a, "split", False)
-            self.op("ds_dup_batch", a.off, a.off, nb)
-            a.nbytes = 0                                  # (ownership of the bytes moved to `out`: free(a) releases nothing)
-        else:
-            out = self.act(a.C, a.H, a.W)
-            out.split = getattr(a, "split", False)
-            self.op("ds_dup_batch", a.off, out.off, nb)
+        # r05: `a` was carved at full size (act() while alloc_B is set) and holds the prefix in its first half: one read + one write
+        assert a.nbytes >= 2 * nb, "dup() of a tensor not carved at the full batch"
+        out = _Act(a.off, a.nbytes, a.C, a.H, a.W)
+        out.split = getattr(a, "split", False)
+        self.op("ds_dup_batch", a.off, a.off, nb)
+        a.nbytes = 0                                  # (ownership of the bytes moved to `out`: free(a) releases nothing)
         if a.stats is not None:
             st, parts = a.stats
             ns = self.raw(self.B * parts * 2 * 4)
@@ -802,41 +781,26 @@ class _PlanBuilder:
         p.stats_part = st[0]
         h.stats = (st, parts)
         self.op("ds_dwconv7", p)
-        if e.lazy_gn:
-            src1_, st1 = self.stats_src(h, dim * H * W)
-            g = self.conv(d["conv1"], h, pad=1, gn_src=src1_, act=L.ACT_GELU, want_stats=True, out_split=sp)
-            self.free(h)
-            self.free_raw(st1)
-            src2_, st2 = self.stats_src(g, d["conv1"].Cout * H * W)
-            c2 = d["conv2"]
-            if (d["res"] is not None and c2.res_steps and
-                    self.halo_ksplit(c2, H, W, g.C) == 1):
-                out = self.conv(c2, g, pad=1, gn_src=src2_, want_stats=want_stats, res_fuse=(s0, s1, off1))
-                self.free(g)
-                self.free_raw(st2)
-                return out
-            if d["res"] is not None:
-                out = self.conv(d["res"], s0, s1, off1)
-                res = out
-            else:
-                out, res = None, s0
-            out = self.conv(d["conv2"], g, pad=1, gn_src=src2_, res=res, want_stats=want_stats, out=out)
+        src1_, st1 = self.stats_src(h, dim * H * W)
+        g = self.conv(d["conv1"], h, pad=1, gn_src=src1_, act=L.ACT_GELU, want_stats=True, out_split=sp)
+        self.free(h)
+        self.free_raw(st1)
+        src2_, st2 = self.stats_src(g, d["conv1"].Cout * H * W)
+        c2 = d["conv2"]
+        if (d["res"] is not None and c2.res_steps and
+                self.halo_ksplit(c2, H, W, g.C) == 1):
+            out = self.conv(c2, g, pad=1, gn_src=src2_, want_stats=want_stats, res_fuse=(s0, s1, off1))
             self.free(g)
             self.free_raw(st2)
             return out
-        ab1 = self.finalize(h, dim * H * W)
-        g = self.conv(d["conv1"], h, pad=1, gn_ab=ab1[0], act=L.ACT_GELU, want_stats=True, out_split=sp)
-        self.free(h)
-        self.free_raw(ab1)
-        ab2 = self.finalize(g, d["conv1"].Cout * H * W)
         if d["res"] is not None:
             out = self.conv(d["res"], s0, s1, off1)           # 1x1 res_conv straight into the output buffer
             res = out
         else:
             out, res = None, s0
-        out = self.conv(d["conv2"], g, pad=1, gn_ab=ab2[0], res=res, want_stats=want_stats, out=out)
+        out = self.conv(d["conv2"], g, pad=1, gn_src=src2_, res=res, want_stats=want_stats, out=out)
         self.free(g)
-        self.free_raw(ab2)
+        self.free_raw(st2)
         return out
 
     def resnet(self, d, x, want_stats):
@@ -908,11 +872,11 @@ class _PlanBuilder:
 
     def attention(self, d, x, planes=None):
         """Residual(PreNorm(LinearCrossAttention[Add])) — components:22-29,142-152,171-207,252-293.
-        planes (split-precision tier, form B only): "both" = the output additionally as hi / lo planes (out.planes), "only" = as planes alone
+        planes (split-precision tier): "both" = the output additionally as hi / lo planes (out.planes), "only" = as planes alone
         (returned activation has .split set) — what the Down / Upsample that follows reads; ignored elsewhere."""
         e, B = self.e, self.B
         N, Cc = x.H * x.W, x.C
-        lazy = e.lazy_gn and (d["fused"] is not None or d.get("x3") is not None) and x.stats[0] != "direct"
+        lazy = (d["fused"] is not None or d.get("x3") is not None) and x.stats[0] != "direct"
         if lazy:
             xsrc, xst = self.stats_src(x, Cc * N)
             abx = (None, 0)
@@ -960,16 +924,10 @@ class _PlanBuilder:
             out = self.act(Cc, x.H, x.W)
             g = L.GnApplyParams(x=y.off, res=x.off, out=out.off, gn_ab=None, gamma=d["on"][0].data_ptr(),
                                 beta=d["on"][1].data_ptr(), cbias=None, cb_stride=0, B=B, HW=N, C=Cc, G=1, act=L.ACT_NONE, dtype=e.dt)
-            if e.lazy_gn:       # the apply pass reduces the output pass' partials itself
-                ysrc, yst = self.stats_src(y, Cc * N)
-                g.gn_part, g.gn_parts, g.gn_count, g.gn_eps = ysrc[0], ysrc[1], float(ysrc[2]), ysrc[3]
-                self.op("ds_gn_apply", g)
-                self.free_raw(yst)
-            else:
-                aby = self.finalize(y, Cc * N)
-                g.gn_ab = aby[0]
-                self.op("ds_gn_apply", g)
-                self.free_raw(aby)
+            ysrc, yst = self.stats_src(y, Cc * N)        # the apply pass reduces the output pass' partials itself
+            g.gn_part, g.gn_parts, g.gn_count, g.gn_eps = ysrc[0], ysrc[1], float(ysrc[2]), ysrc[3]
+            self.op("ds_gn_apply", g)
+            self.free_raw(yst)
             self.free(y)
             return out
         qkv = self.conv(d["qkv"], x, gn_ab=abx[0])
@@ -1005,29 +963,24 @@ class _PlanBuilder:
         """The block in the split-precision tier (attn_x3.hip): x (fp32) is the only activation stream — k / v / q projections, both
         softmaxes, ctx and to_out as three-term bf16 MFMA products, and the output GroupNorm + residual applied while y is computed a
         second time (ds_attn_x3_output form B: no y tensor, no apply pass; +1.15 % on the step against form A + ds_gn_apply, same box —
-        after the statistics-only pass lost the 644 bytes of scratch that made it slower than the pass that writes y).
-        DS_X3_ATTN_APPLY_PASS=1 switches back to form A."""
+        after the statistics-only pass lost the 644 bytes of scratch that made it slower than the pass that writes y)."""
         e, B = self.e, self.B
         N, Cc = x.H * x.W, x.C
         lib = self.lib
-        formb = os.environ.get("DS_X3_ATTN_APPLY_PASS", "0") != "1"
         nseg = lib.ds_attn_x3_segments(B, N, Cc)
         part = self.raw(lib.ds_linattn_part_floats(B, 4, nseg) * 4)
         ctx = self.raw(B * 4 * 1024 * 4)
         qpl = self.raw(lib.ds_attn_x3_qplane_bytes(B, N)) if Cc != 96 else None      # (C = 96: q is projected inside the fused pass 2)
         mf = self.raw(lib.ds_attn_x3_mfold_bytes(B, Cc))
-        if not formb or os.environ.get("DS_X3_ATTN_NO_PLANES", "0") == "1":
-            planes = None
-        out = self.act(Cc, x.H, x.W) if (formb and planes != "only") else None
+        out = self.act(Cc, x.H, x.W) if planes != "only" else None
         pl = self.act(Cc, x.H, x.W) if planes else None            # (2C bf16 per pixel = the bytes of C fp32)
         if pl is not None:
             pl.split = True
-        y = None if formb else self.act(Cc, x.H, x.W)
         lab = self.lab_all[0] if self.lab_all else None
         fp = L.AttnX3Params(x=x.off, B=B, N=N, C=Cc, nseg=nseg, wqkv_hl=d["x3"][0].data_ptr(), t1=d["qkv"].t1.data_ptr(),
                             t2=d["qkv"].t2.data_ptr(), gn_ab=abx[0], label_q=(lab + 4 * d["l_off"]) if lab else None,
                             lq_stride=e._lab_total, scale=32 ** -0.5, part=part[0], ctx=ctx[0], qplanes=(qpl[0] if qpl else None), mfold=mf[0],
-                            wout=d["x3"][1].data_ptr(), bias_out=d["out"].bias.data_ptr(), y=(y.off if y else None), stats_part=None,
+                            wout=d["x3"][1].data_ptr(), bias_out=d["out"].bias.data_ptr(), y=None, stats_part=None,
                             out=(out.off if out is not None else None), on_gamma=d["on"][0].data_ptr(), on_beta=d["on"][1].data_ptr(), on_eps=1e-5,
                             out_planes=(pl.off if pl is not None else None))
         if lazy:
@@ -1044,28 +997,11 @@ class _PlanBuilder:
         for r in (part, ctx, qpl, mf):
             if r is not None:
                 self.free_raw(r)
-        if formb:
-            self.free_raw(st)
-            if planes == "only":
-                return pl
-            if pl is not None:
-                out.planes = pl
-            return out
-        y.stats = (st, parts)
-        out = self.act(Cc, x.H, x.W)
-        g = L.GnApplyParams(x=y.off, res=x.off, out=out.off, gn_ab=None, gamma=d["on"][0].data_ptr(),
-                            beta=d["on"][1].data_ptr(), cbias=None, cb_stride=0, B=B, HW=N, C=Cc, G=1, act=L.ACT_NONE, dtype=e.dt)
-        if e.lazy_gn:       # the apply pass reduces the output pass' partials itself
-            ysrc, yst = self.stats_src(y, Cc * N)
-            g.gn_part, g.gn_parts, g.gn_count, g.gn_eps = ysrc[0], ysrc[1], float(ysrc[2]), ysrc[3]
-            self.op("ds_gn_apply", g)
-            self.free_raw(yst)
-        else:
-            aby = self.finalize(y, Cc * N)
-            g.gn_ab = aby[0]
-            self.op("ds_gn_apply", g)
-            self.free_raw(aby)
-        self.free(y)
+        self.free_raw(st)
+        if planes == "only":
+            return pl
+        if pl is not None:
+            out.planes = pl
         return out
 
     # ---------------------------------------------------------------- whole graph
@@ -1229,7 +1165,7 @@ class _PlanBuilder:
         # The conditioning GEMVs (0.36 ms at U-Net batch 128: five latency-bound launches) depend on (time, condition) only: at
         # large batches they run on a side stream under the layout change + init convolution of the trunk.
         side = None
-        if e.cond_async and self.n_cond > 0 and B * self.H * self.W >= 65536:
+        if self.n_cond > 0 and B * self.H * self.W >= 65536:
             if e.side_stream is None:
                 e.side_stream = torch.cuda.Stream()
             side = e.side_stream

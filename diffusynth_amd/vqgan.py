@@ -10,7 +10,6 @@ is a plan over the same HIP kernels as the U-Net (implicit-GEMM convolutions inc
 4x4, linear attention, GroupNorm(16) + swish / ReLU passes) plus the tail activation kernel.
 """
 import ctypes as C
-import os
 
 import torch
 from torch import nn
@@ -281,6 +280,11 @@ def get_VQGAN(model_Config, load_pretrain=False, model_name=None, device="cuda")
 # =============================================================================== decoder engine
 class DecoderEngine(_EngineBase):
     """Plan executor for the VQGAN Decoder and (decoder=False) Encoder layer stacks."""
+    # the specialised kernels of the bf16 tier (tests switch one off to compare it with the generic path)
+    use_vq_attn = True       # the attention block on vq_attn.hip
+    use_c80 = True           # the 80-channel block body on conv3x3_c80.hip
+    use_up80 = True          # the 80-channel transposed convolution on convt4x4_c80.hip
+    use_dec_final = True     # the decoder's last block + output activations on dec_final.hip
 
     def __init__(self, module, compute_dtype, decoder=True):
         self._init_common(module, compute_dtype)
@@ -316,14 +320,14 @@ class DecoderEngine(_EngineBase):
         if kind == "conv1x1":
             d = {"conv": self._pack_conv(m.weight, None, cin_pad=self.cin0 if i == 0 else None), "in_nchw": None}
             cout, cin = int(m.weight.shape[0]), int(m.weight.shape[1])
-            if i == 0 and self.dt == L.DS_BF16 and cin in (4, 8) and cout % 8 == 0 and os.environ.get("DS_NO_IN_CONV", "0") != "1":
+            if i == 0 and self.dt == L.DS_BF16 and cin in (4, 8) and cout % 8 == 0:
                 # layout change + 1x1 convolution of the NCHW latent in one pass (ds_conv1x1_in_nchw)
                 d["in_nchw"] = self._f32(m.weight).reshape(cout, cin).contiguous()
             return d
         if kind == "attn":
             d = {"qkv": self._pack_conv(m.to_qkv.weight, None), "out": self._pack_conv(m.to_out.weight, m.to_out.bias), "nin": None}
             dim = int(m.to_qkv.weight.shape[1])
-            if self.dt == L.DS_BF16 and dim in (80, 160) and tuple(m.to_qkv.weight.shape[:2]) == (96, dim) and os.environ.get("DS_NO_VQ_ATTN", "0") != "1":
+            if self.dt == L.DS_BF16 and dim in (80, 160) and tuple(m.to_qkv.weight.shape[:2]) == (96, dim) and self.use_vq_attn:
                 # the whole block on csrc/vq_attn.hip: context from x, then ONE per-sample 1x1 convolution (q enters linearly)
                 wqkv = self._f32(m.to_qkv.weight).reshape(96, dim)
                 bias = self._f32(m.to_out.bias)
@@ -335,12 +339,11 @@ class DecoderEngine(_EngineBase):
                               "wout": self._f32(m.to_out.weight).reshape(dim, 32).contiguous(), "wnin": wnin, "bias": bias.contiguous()}
             if hasattr(m, "nin_shortcut"):
                 d["nin"] = self._pack_conv(m.nin_shortcut.weight, m.nin_shortcut.bias)
-                if os.environ.get("DS_NO_ATTN_MERGE", "0") != "1":
-                    # nin_shortcut(x) + to_out(a) = ONE 1x1 convolution over the channel concat (x | a) with the weights side by side: one
-                    # launch, and the dim-channel tensor is written once instead of written, re-read and re-written
-                    wm = torch.cat([m.nin_shortcut.weight.detach().float(), m.to_out.weight.detach().float()], 1)
-                    bm = m.nin_shortcut.bias.detach().float() + m.to_out.bias.detach().float()
-                    d["merged"] = self._pack_conv(wm, bm)
+                # nin_shortcut(x) + to_out(a) = ONE 1x1 convolution over the channel concat (x | a) with the weights side by side: one
+                # launch, and the dim-channel tensor is written once instead of written, re-read and re-written
+                wm = torch.cat([m.nin_shortcut.weight.detach().float(), m.to_out.weight.detach().float()], 1)
+                bm = m.nin_shortcut.bias.detach().float() + m.to_out.bias.detach().float()
+                d["merged"] = self._pack_conv(wm, bm)
             return d
         if kind == "res":
             small = m.conv1.weight.shape[0] < 8
@@ -350,15 +353,15 @@ class DecoderEngine(_EngineBase):
                 d["nin"] = self._pack_conv(m.nin_shortcut.weight, m.nin_shortcut.bias, small_out=small)
             cout, cin = m.conv1.weight.shape[:2]
             d["c80"] = None
-            if (self.dt == L.DS_BF16 and cout == 80 and cin == 80 and d["nin"] is None and not self.bn and os.environ.get("DS_NO_C80", "0") != "1"):
-                # the whole 80-channel block body as one kernel (conv3x3_c80.hip): GroupNorm + activation on load, residual in the epilogue
+            if (self.dt == L.DS_BF16 and cout == 80 and cin == 80 and d["nin"] is None and not self.bn and self.use_c80):
+                # the 80-channel block body: 3x3 + bias + residual as one kernel (conv3x3_c80.hip) behind the GroupNorm apply pass
                 wf = self._f32(m.conv1.weight)
                 wp = torch.empty(L.load().ds_conv3x3_c80_weight_elems(), dtype=torch.bfloat16, device=self.dev)
                 L.call("ds_pack_conv3x3_c80", wf.data_ptr(), 80, 80, wp.data_ptr(), L.current_stream())
                 self._pack_tmp.append(wf)
                 d["c80"] = (wp, self._f32(m.conv1.bias))
             if (small and cout == 3 and self.is_decoder and self.dt == L.DS_BF16 and d["nin"] is not None and cin % 8 == 0 and cin <= 96
-                    and not self.bn and os.environ.get("DS_NO_DEC_FINAL", "0") != "1"):
+                    and not self.bn and self.use_dec_final):
                 # the decoder's last block + output activations as one kernel (dec_final.hip): 3x3 weight as 16-row chunk-major tiles, Cin padded to 96
                 w = self._f32(m.conv1.weight)
                 n16 = L.load().ds_pack_conv_elems(96, 3, 3, 16, 0)
@@ -374,7 +377,7 @@ class DecoderEngine(_EngineBase):
         if kind == "up":
             d = {"conv": self._pack_conv(m._conv2d.weight, m._conv2d.bias, transposed=True), "up80": None}
             w = m._conv2d.weight
-            if (self.dt == L.DS_BF16 and tuple(w.shape) in ((80, 80, 4, 4), (160, 80, 4, 4)) and not self.bn and os.environ.get("DS_NO_UP80", "0") != "1"):
+            if (self.dt == L.DS_BF16 and tuple(w.shape) in ((80, 80, 4, 4), (160, 80, 4, 4)) and not self.bn and self.use_up80):
                 # ConvTranspose2d(80 | 160, 80, 4, 2, 1) on its own kernel (convt4x4_c80.hip): K steps of two (tap, 16-channel group) pairs
                 wf = self._f32(w)
                 cin = int(w.shape[0])
@@ -468,7 +471,7 @@ class _DecoderPlan(_PlanBuilder):
         # the Encoder's blocks are built with act_type="act_type" (VQGAN.py:441) => swish whatever the config says
         act = L.ACT_RELU if (e.cfg["act_type"] == "relu" and e.is_decoder) else L.ACT_SILU
         if d.get("c80") is not None and x.C == 80:
-            # statistics, then ONE kernel: act(GroupNorm(x)) while the halo is staged, 3x3, + bias + x
+            # statistics, act(GroupNorm(x)) in one apply pass, then ONE kernel: 3x3 + bias + x (conv3x3_c80.hip)
             B, G = self.B, e.cfg["num_groups"]
             ab = self.raw(B * G * 2 * 4)
             self._stats_op(x, G, 1e-6, ab)
@@ -477,17 +480,12 @@ class _DecoderPlan(_PlanBuilder):
             self.conv_meta[len(self.ops)] = (16, 2.0 * B * x.H * x.W * 80 * 9 * 80, f"3x3 80->80 @{x.H}x{x.W}")
             slots = self.lib.ds_conv3x3_c80_stats_slots(B, x.H, x.W)      # per-channel statistics of the output: the next Normalize reads them
             ws = self.raw(B * slots * 80 * 2 * 4)
-            if os.environ.get("DS_C80_FUSED_ACT", "0") == "1":
-                # (A/B: the norm + activation applied while the kernel stages its halo — one launch, but bound by that arithmetic)
-                self.op("ds_conv3x3_c80", x.off, B, x.H, x.W, wp.data_ptr(), bias.data_ptr(), out.off, ab[0], G, d["norm"][0].data_ptr(),
-                        d["norm"][1].data_ptr(), act, 1, ws[0])
-            else:
-                hact = self.act(80, x.H, x.W)
-                gp = L.GnApplyParams(x=x.off, res=None, out=hact.off, gn_ab=ab[0], gamma=d["norm"][0].data_ptr(), beta=d["norm"][1].data_ptr(),
-                                     cbias=None, cb_stride=0, B=B, HW=x.H * x.W, C=80, G=G, act=act, dtype=e.dt)
-                self.op("ds_gn_apply", gp)
-                self.op("ds_conv3x3_c80_res", hact.off, x.off, B, x.H, x.W, wp.data_ptr(), bias.data_ptr(), out.off, ws[0])
-                self.free(hact)
+            hact = self.act(80, x.H, x.W)
+            gp = L.GnApplyParams(x=x.off, res=None, out=hact.off, gn_ab=ab[0], gamma=d["norm"][0].data_ptr(), beta=d["norm"][1].data_ptr(),
+                                 cbias=None, cb_stride=0, B=B, HW=x.H * x.W, C=80, G=G, act=act, dtype=e.dt)
+            self.op("ds_gn_apply", gp)
+            self.op("ds_conv3x3_c80_res", hact.off, x.off, B, x.H, x.W, wp.data_ptr(), bias.data_ptr(), out.off, ws[0])
+            self.free(hact)
             self.free_raw(ab)
             out.stats = (ws, slots, "chan_ws")          # (released with the tensor if no Normalize consumes it)
             return out

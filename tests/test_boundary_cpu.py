@@ -54,6 +54,24 @@ def test_library_exports_every_declared_symbol():
     assert b"conv_igemm" in lib.ds_last_error_string()
 
 
+def test_no_environment_switches():
+    """One code path per layer and tier: the compiled library reads no environment variable, and the Python package reads only its
+    configuration (plan-cache size, the diagnostic-library choice, the paired-CFG self-check, the distributed launcher's variables)."""
+    csrc = os.path.join(ROOT, "diffusynth_amd", "csrc")
+    for name in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, name)) as f:
+            assert not re.search(r"\bgetenv\b", f.read()), f"{name} reads the environment"
+    keep = {"engine.py": {"DS_MAX_PLANS"}, "_lib.py": {"DS_LIB"}, "unet.py": {"DS_CHECK_PAIRED"}}
+    pkg = os.path.join(ROOT, "diffusynth_amd")
+    for name in sorted(os.listdir(pkg)):
+        if not name.endswith(".py") or name == "dist.py":
+            continue
+        with open(os.path.join(pkg, name)) as f:
+            for k, line in enumerate(f, 1):
+                if re.search(r"\b(environ|getenv)\b", line):
+                    read = set(re.findall(r"\b(?:environ\.get|environ\[|getenv)\(?\s*[\"'](\w+)[\"']", line))
+                    assert read and read <= keep.get(name, set()), f"{name}:{k} reads the environment: {line.strip()}"
+
 def test_host_side_tiling_policies():
     """The batch-dependent tiling decisions of the bf16 tier live behind host-only C entry points (no device work): the attention segment
     count follows the kernel generation chosen for the batch, the depthwise kernel's GroupNorm partials follow its chunking, and both

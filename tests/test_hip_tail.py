@@ -296,21 +296,21 @@ def test_vq_attn_fused_matches_torch(dim, hw, B, skip):
     assert (ab[:, :, 1].cpu().double() - rstd * gr.mean(dim=2)).abs().max() < 1e-3
 
 
-def test_decoder_fused_attention_matches_unfused(vae):
-    """The bf16 decoder with its LinearAttention blocks on csrc/vq_attn.hip against the same decoder on the unfused chain (DS_NO_VQ_ATTN=1: to_qkv,
+def test_decoder_fused_attention_matches_unfused(vae, monkeypatch):
+    """The bf16 decoder with its LinearAttention blocks on csrc/vq_attn.hip against the same decoder on the unfused chain (use_vq_attn off: to_qkv,
     context, output, merged to_out | nin_shortcut): two bf16 evaluations of the same network."""
-    import os
+    from diffusynth_amd.vqgan import DecoderEngine
     g = load_golden("tail")
     q = torch.from_numpy(g["dec_q"]).cuda()
     vae._decoder.set_compute_dtype("bf16")
     y1 = vae._decoder(q)
-    os.environ["DS_NO_VQ_ATTN"] = "1"
     try:
-        vae._decoder.set_compute_dtype("fp32")
-        vae._decoder.set_compute_dtype("bf16")          # rebuilds the engine (packing reads the switch)
-        y0 = vae._decoder(q)
+        with monkeypatch.context() as mp:
+            mp.setattr(DecoderEngine, "use_vq_attn", False)
+            vae._decoder.set_compute_dtype("fp32")
+            vae._decoder.set_compute_dtype("bf16")          # rebuilds the engine (packing reads the attribute)
+            y0 = vae._decoder(q)
     finally:
-        del os.environ["DS_NO_VQ_ATTN"]
         vae._decoder.set_compute_dtype("fp32")
     err = rel_err(y1.cpu(), y0.cpu())
     print(f"decoder bf16, fused vs unfused attention: rel err {err:.2e}; vs fp32 reference {rel_err(y1.cpu(), g['dec_y']):.2e} / {rel_err(y0.cpu(), g['dec_y']):.2e}")
@@ -358,43 +358,42 @@ def test_vq_stats_matches_torch():
         assert abs(got[0] - mse) / mse < 1e-5 and abs(got[1] - perp) / perp < 1e-4 and abs(got[2] - want_loss) / want_loss < 1e-5, (got, mse, perp)
 
 
-def test_decoder_upsample_kernel_matches_generic(vae):
+def test_decoder_upsample_kernel_matches_generic(vae, monkeypatch):
     """The decoder (bf16) with its 80-channel block and last Upsample on their own kernels (ds_conv3x3_c80, ds_convt4x4_c80) against the same
-    decoder with those layers on the generic kernels (DS_NO_UP80=1, DS_NO_C80=1)."""
-    import os
+    decoder with those layers on the generic kernels (use_up80 and use_c80 off)."""
+    from diffusynth_amd.vqgan import DecoderEngine
     q = synth_input("t_u8_q", (2, 4, 32, 16)).cuda()
     dec = vae._decoder
     dec.set_compute_dtype("bf16")
     try:
         y_new = dec(q)
-        os.environ["DS_NO_UP80"] = "1"
-        os.environ["DS_NO_C80"] = "1"
-        dec.set_compute_dtype("fp32")
-        dec.set_compute_dtype("bf16")                 # (re-pack: the switch is read when the layers are packed)
-        y_old = dec(q)
+        with monkeypatch.context() as mp:
+            mp.setattr(DecoderEngine, "use_up80", False)
+            mp.setattr(DecoderEngine, "use_c80", False)
+            dec.set_compute_dtype("fp32")
+            dec.set_compute_dtype("bf16")                 # (re-pack: the attributes are read when the layers are packed)
+            y_old = dec(q)
     finally:
-        os.environ.pop("DS_NO_UP80", None)
-        os.environ.pop("DS_NO_C80", None)
         dec.set_compute_dtype("fp32")
     assert torch.isfinite(y_new).all()
     assert (y_new - y_old).abs().max().item() < 3e-2 * y_old.abs().max().item()
 
 
-def test_decoder_fused_final_block_matches_unfused(vae):
-    """The bf16 decoder with its last block on ds_dec_final vs the same decoder with DS_NO_DEC_FINAL=1 semantics (a second engine built
-    with the switch on): both are bf16 evaluations of the same network — they agree to bf16 rounding."""
-    import os
+def test_decoder_fused_final_block_matches_unfused(vae, monkeypatch):
+    """The bf16 decoder with its last block on ds_dec_final vs the same decoder with use_dec_final off (a second engine built
+    without it): both are bf16 evaluations of the same network — they agree to bf16 rounding."""
+    from diffusynth_amd.vqgan import DecoderEngine
     g = load_golden("tail")
     q = torch.from_numpy(g["dec_q"]).cuda()
     vae._decoder.set_compute_dtype("bf16")
     y1 = vae._decoder(q)
-    os.environ["DS_NO_DEC_FINAL"] = "1"
     try:
-        vae._decoder.set_compute_dtype("fp32")
-        vae._decoder.set_compute_dtype("bf16")          # rebuilds the engine (packing reads the switch)
-        y0 = vae._decoder(q)
+        with monkeypatch.context() as mp:
+            mp.setattr(DecoderEngine, "use_dec_final", False)
+            vae._decoder.set_compute_dtype("fp32")
+            vae._decoder.set_compute_dtype("bf16")          # rebuilds the engine (packing reads the attribute)
+            y0 = vae._decoder(q)
     finally:
-        del os.environ["DS_NO_DEC_FINAL"]
         vae._decoder.set_compute_dtype("fp32")
     err = rel_err(y1.cpu(), y0.cpu())
     print(f"decoder bf16, fused vs unfused last block: rel err {err:.2e}")

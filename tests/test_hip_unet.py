@@ -327,10 +327,11 @@ def test_interpolate_matches_reference(unet):
 
 
 @pytest.mark.parametrize("tier", ["fp32", "bf16x3", "bf16"])
-def test_cfg_paired_halves_is_bit_identical(unet, tier):
+def test_cfg_paired_halves_is_bit_identical(unet, tier, monkeypatch):
     """Classifier-free guidance evaluates model(cat([x, x]), cat([t, t]), cat([uncond, cond])) (DiffSynthSampler.py:311-320).  Told that
     the halves are paired, the plan computes what does not depend on the condition (init convolution, first block) once at half the batch:
     the output must be the same bits as the plain call, and the sampler's CFG trajectory must not change."""
+    from diffusynth_amd.engine import UnetEngine
     B, H, W = 3, 32, 40
     x = synth_input("pair_x", (B, 4, H, W)).cuda()
     t = torch.tensor([900, 17, 500], device="cuda")
@@ -342,19 +343,16 @@ def test_cfg_paired_halves_is_bit_identical(unet, tier):
         paired = unet(xx, tt, c, paired_halves=True).clone()
         assert torch.equal(plain, paired)
         assert not torch.equal(plain[:B], plain[B:])                      # (the halves do differ: different conditions)
-        import os
         s = _sampler(3, H, B)
         s.activate_classifier_free_guidance(4.0, c[0])
         a, _ = s.sample(unet, (B, 4, H, W), return_tensor=True, condition=c[B:], sampler="ddim", seed=3)
-        os.environ["DS_NO_CFG_PAIR"] = "1"
-        try:
-            unet.set_compute_dtype("fp32" if tier != "fp32" else "bf16")   # (new engine: the switch is read when the engine is built)
+        with monkeypatch.context() as mp:
+            mp.setattr(UnetEngine, "use_cfg_pair", False)
+            unet.set_compute_dtype("fp32" if tier != "fp32" else "bf16")   # (new engine, built without the shared prefix)
             unet.set_compute_dtype(tier)
             s = _sampler(3, H, B)
             s.activate_classifier_free_guidance(4.0, c[0])
             b, _ = s.sample(unet, (B, 4, H, W), return_tensor=True, condition=c[B:], sampler="ddim", seed=3)
-        finally:
-            del os.environ["DS_NO_CFG_PAIR"]
         assert torch.equal(a[-1], b[-1])
     finally:
         unet.set_compute_dtype("bf16" if tier == "fp32" else "fp32")

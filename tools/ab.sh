@@ -1,10 +1,11 @@
 #!/bin/bash
-# Same-box A/B of library variants and / or environment switches (boxes of the pool differ by 3-5 %: never compare across gpurun calls).
+# Same-box A/B of library variants (boxes of the pool differ by 3-5 %: never compare across runs on different boxes).
 #
 #   bash tools/ab.sh [-m MODE] [-r ROUNDS] [-a "extra args"] VARIANT [VARIANT ...]
 #
-# VARIANT = [ENV=val[,ENV2=val2...]:][lib.so]     "libdiffusynth_hip_prev.so"   "DS_NO_CFG_PAIR=1:"   "DS_KSPLIT_FILL=512,DS_X=1:libfoo.so"
-#           (no library name = the product build libdiffusynth_hip.so; libraries are file names under diffusynth_amd/, see build_variants.py)
+# VARIANT = [ENV=val[,ENV2=val2...]:][lib.so]     "libdiffusynth_hip_prev.so"   "DS_MAX_PLANS=1:"   "DS_MAX_PLANS=1:libfoo.so"
+#           (no library name = the product build libdiffusynth_hip.so; libraries are file names under diffusynth_amd/, see build_variants.py;
+#           an earlier commit's library, built under another name, is how a retired code path is measured again)
 # MODE    = bench  headline bench (default; -a e.g. "--dtype bf16", "--workload config2 --steps 20")
 #           conv   conv_microbench.py over the representative 3x3 layers at U-Net batch 128 (-a e.g. "--tile 11 --iters 10"; LAYERS= overrides)
 #           dw     dw_microbench.py over the eleven depthwise layer shapes (-a e.g. "--dtype fp32split")
@@ -14,7 +15,7 @@
 MODE=bench; R=2; EXTRA=""
 while getopts "m:r:a:" o; do case $o in m) MODE=$OPTARG;; r) R=$OPTARG;; a) EXTRA=$OPTARG;; *) exit 2;; esac; done
 shift $((OPTIND - 1))
-[ $# -ge 1 ] || { sed -n 2,15p "$0"; exit 2; }
+[ $# -ge 1 ] || { sed -n 2,14p "$0"; exit 2; }
 JSON_LINE='import json,sys
 d=json.loads(sys.stdin.read()); r=d.get("roofline") or {}
 print("%.1f steps/s  %.3f ms/step" % (d["value"], d["ms_per_step"]) + ("  dominant kernel %.1f us, frac %.4f" % (r["avg_launch_us"], r["frac"]) if r else ""))'

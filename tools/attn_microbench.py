@@ -18,11 +18,11 @@ def main():
     ap.add_argument("--n", type=int, default=16384)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--nseg", type=int, default=0)
-    ap.add_argument("--gen", type=int, default=0, help="1 / 2: force the first / second kernel generation (default: second unless DS_ATTN_V1 / DS_ATTN_CTX1 is set)")
+    ap.add_argument("--gen", type=int, default=2, choices=[1, 2], help="1 / 2: force the first / second kernel generation")
     ap.add_argument("--iters", type=int, default=20)
     a = ap.parse_args()
     B, N, Cc = a.batch, a.n, a.c
-    gen = a.gen if a.gen else (1 if (os.environ.get("DS_ATTN_V1") or os.environ.get("DS_ATTN_CTX1")) else 2)      # (forced: the A/B is about the kernels)
+    gen = a.gen      # (forced: the A/B is about the kernels)
     nseg = a.nseg or (max(1, min((1024 if Cc == 384 else 2048) // B, 64, (N + 31) // 32)) if gen == 2 and (Cc in (96, 192) or N >= 1024) else max(1, min(N // 128, 32)))
     torch.manual_seed(0)
     x = torch.randn(B, N, Cc, device="cuda").bfloat16()
