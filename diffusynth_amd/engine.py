@@ -15,14 +15,11 @@ import os
 import torch
 
 from . import _lib as L
+from . import conv_policy as policy
+from .conv_policy import up as _up
 
 _ESIZE = {L.DS_F32: 4, L.DS_BF16: 2}
 _TDT = {L.DS_F32: torch.float32, L.DS_BF16: torch.bfloat16}
-KSPLIT_FILL = 256        # split K until this many blocks exist (256 CUs)
-
-
-def _up(x, m):
-    return (x + m - 1) // m * m
 
 
 class _Arena:
@@ -67,9 +64,20 @@ class _Act:
 
 
 class _ConvW:
-    """Packed convolution: weights (+ optional GroupNorm fold tables) for one tile family."""
+    """Packed convolution: the generic kernel's weights (+ GroupNorm fold tables) and every other form the layer's shape and tier
+    qualify for (conv_policy.*_fits; None where not).  conv() picks one of them per launch."""
     __slots__ = ("w", "bias", "t1", "t2", "ncls", "Cout", "cout_pad", "cin_pad", "cin_real", "KH", "KW", "bn", "transposed", "k_order",
-                 "res_steps", "res_bias", "w_fused", "w_quad", "quad_cout_pad", "w_split", "w_n16", "w_x3", "x3_cout_pad", "w_init7", "w_f32n4", "w_init7x3")
+                 "w_f32n4", "w_x3", "x3_cout_pad", "w_n16", "w_split", "w_quad", "quad_cout_pad", "w_init7", "w_init7x3",
+                 "w_fused", "res_steps", "res_bias")
+
+    def __init__(self, s):
+        self.Cout, self.cin_pad, self.cin_real, self.transposed = s.Cout, s.cin_pad, s.Cin, s.transposed
+        self.KH, self.KW = (2, 2) if s.transposed else s.k
+        self.bn, self.cout_pad, self.k_order = s.bn, s.cout_pad, s.k_order
+        self.w = self.bias = self.t1 = self.t2 = None
+        self.w_f32n4 = self.w_x3 = self.w_n16 = self.w_split = self.w_quad = self.w_init7 = self.w_init7x3 = None
+        self.ncls, self.x3_cout_pad, self.quad_cout_pad = 1, 0, 0
+        self.w_fused, self.res_steps, self.res_bias = None, 0, None       # the block's 1x1 res_conv in front (UnetEngine._pack_block)
 
 
 def split3_weight(w, gamma=None):
@@ -206,85 +214,59 @@ class _EngineBase:
     def _f32(self, t):
         return t.detach().to(device=self.dev, dtype=torch.float32).contiguous()
 
-    def _pack_conv(self, weight, bias, cin_pad=None, gamma=None, beta=None, transposed=False, small_out=False, halo=False):
-        """halo=True: the layer is a single-source 3x3 stride-1 convolution of a ConvNeXt block, i.e. it will run on the
-        hand-scheduled LDS-halo kernel (bf16), whose weights are packed chunk-major (k_order 1)."""
-        w = self._f32(weight)
-        if transposed:
-            Cin, Cout = w.shape[0], w.shape[1]
-            KH = KW = 2
-        else:
-            Cout, Cin, KH, KW = w.shape
-        cin_pad = Cin if cin_pad is None else cin_pad
-        if small_out:
-            bn = 32
-        elif Cout % 192 == 0:
-            bn = 192
-        else:
-            bn = 96
-        cw = _ConvW()
-        cw.Cout, cw.cout_pad, cw.cin_pad, cw.KH, cw.KW, cw.bn, cw.transposed = Cout, _up(Cout, bn), cin_pad, KH, KW, bn, transposed
-        cw.cin_real = Cin
-        cw.k_order = 1 if (halo and self.dt == L.DS_BF16 and KH == 3 and KW == 3 and not transposed and cin_pad % 32 == 0
-                           and bn in (96, 192)) else 0
-        n = L.load().ds_pack_conv_elems(cin_pad, KH, KW, cw.cout_pad, 1 if transposed else 0)
-        cw.w = torch.empty(n, dtype=_TDT[self.dt], device=self.dev)
-        g = self._f32(gamma) if gamma is not None else None
-        pp = L.PackConvParams(w=w.data_ptr(), gamma=L.ptr(g), dst=cw.w.data_ptr(), dtype=self.dt, Cout=Cout, Cin=Cin,
-                              cin_pad=cin_pad, KH=KH, KW=KW, cout_pad=cw.cout_pad, transposed=1 if transposed else 0, k_order=cw.k_order)
+    def _pack_weight(self, w, gamma, dtype, Cout, Cin, cin_pad, KH, KW, cout_pad, transposed=False, k_order=1):
+        """ds_pack_conv_weight into a new tensor (k_order 1: chunk-major tiles of the halo kernels)."""
+        dst = torch.empty(L.load().ds_pack_conv_elems(cin_pad, KH, KW, cout_pad, int(transposed)), dtype=_TDT[dtype], device=self.dev)
+        pp = L.PackConvParams(w=w.data_ptr(), gamma=L.ptr(gamma), dst=dst.data_ptr(), dtype=dtype, Cout=Cout, Cin=Cin, cin_pad=cin_pad,
+                              KH=KH, KW=KW, cout_pad=cout_pad, transposed=int(transposed), k_order=k_order)
         L.call("ds_pack_conv_weight", C.byref(pp), L.current_stream())
+        return dst
+
+    def _pack_init7(self, w, fn, planes):
+        dst = torch.empty(planes * L.load().ds_conv7x7_c4_weight_elems(), dtype=torch.bfloat16, device=self.dev)
+        L.call(fn, w.data_ptr(), 96, int(w.shape[1]), dst.data_ptr(), L.current_stream())
+        return dst
+
+    def _pack_conv(self, weight, bias, cin_pad=None, gamma=None, beta=None, transposed=False, small_out=False, halo=False):
+        """halo=True: the layer is a single-source 3x3 stride-1 convolution of a block, i.e. it runs on an LDS-halo kernel where its tier
+        has one (bf16: chunk-major weights, k_order 1; bf16x3: the split-precision weights)."""
+        w = self._f32(weight)
+        Cin, Cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
+        s = policy.ConvLayer(Cout, Cin, Cin if cin_pad is None else cin_pad, tuple(w.shape[2:]), transposed, gamma is not None, halo,
+                             small_out, self.dt == L.DS_BF16, self.split3)
+        cw = _ConvW(s)
+        g = self._f32(gamma) if gamma is not None else None
+        cw.w = self._pack_weight(w, g, self.dt, Cout, Cin, s.cin_pad, cw.KH, cw.KW, cw.cout_pad, transposed, cw.k_order)
         cw.bias = self._f32(bias) if bias is not None else None
-        cw.res_steps, cw.res_bias, cw.w_fused = 0, None, None
-        cw.w_quad, cw.quad_cout_pad = None, 0
-        cw.w_split = None
-        cw.w_n16 = None
-        cw.w_init7 = None
-        cw.w_f32n4 = None
-        cw.w_x3, cw.x3_cout_pad = None, 0
-        if (self.dt == L.DS_F32 and gamma is None and KH == 3 and KW == 3 and not transposed and Cout <= 4 and cin_pad == Cin
-                and Cin % 32 == 0):
-            # few-output 3x3 of the fp32 / split-precision tiers (the final 96 -> 4 convolution): vector-ALU kernel, weights through scalar loads
+        if s.f32n4_fits:
             cw.w_f32n4 = torch.empty(L.load().ds_conv3x3_f32_n4_weight_floats(Cin), dtype=torch.float32, device=self.dev)
             L.call("ds_pack_conv3x3_f32_n4", w.data_ptr(), L.ptr(cw.bias), Cout, Cin, cw.w_f32n4.data_ptr(), L.current_stream())
-        if self.split3 and KH == 1 and KW == 1 and not transposed and cin_pad == Cin and Cin % 32 == 0 and Cout % 8 == 0:
-            # 1x1 convolutions of the split-precision tier (to_qkv, to_out, res_conv): pre-split weights for ds_conv1x1_x3
+        if s.x3_1x1_fits:
             cw.w_x3, cw.x3_cout_pad = pack_x3_1x1(weight.to(self.dev), gamma.to(self.dev) if gamma is not None else None)
-        if (self.dt == L.DS_BF16 and gamma is None and KH == 3 and KW == 3 and not transposed and Cout <= 16
-                and cin_pad == Cin and Cin % 32 == 0):
-            # few-output 3x3 (the final 96 -> 4 convolution): chunk-major tiles with 16 output rows for conv3x3_smalln.hip
-            n16 = L.load().ds_pack_conv_elems(Cin, 3, 3, 16, 0)
-            cw.w_n16 = torch.empty(n16, dtype=torch.bfloat16, device=self.dev)
-            pp16 = L.PackConvParams(w=w.data_ptr(), gamma=None, dst=cw.w_n16.data_ptr(), dtype=L.DS_BF16, Cout=Cout, Cin=Cin, cin_pad=Cin, KH=3, KW=3,
-                                    cout_pad=16, transposed=0, k_order=1)
-            L.call("ds_pack_conv_weight", C.byref(pp16), L.current_stream())
-        # (Cout % 8: the split-precision kernels store bf16-style 8-channel groups into a tensor sized for fp32 (channels rounded to 4))
-        if halo and self.split3 and KH == 3 and KW == 3 and not transposed and cin_pad == Cin and Cin % 32 == 0 and cw.cout_pad % 96 == 0 and Cout % 8 == 0:
+        if s.n16_fits:
+            cw.w_n16 = self._pack_weight(w, None, L.DS_BF16, Cout, Cin, Cin, 3, 3, 16)
+        if s.split3_fits:
             ws = split3_weight(weight, gamma)                                     # [Cout][3 Cin][3][3] fp32: per chunk W_hi | W_lo | W_hi (gain folded)
-            ns = L.load().ds_pack_conv_elems(3 * Cin, 3, 3, cw.cout_pad, 0)
-            cw.w_split = torch.empty(ns, dtype=torch.bfloat16, device=self.dev)
-            pps = L.PackConvParams(w=ws.data_ptr(), gamma=None, dst=cw.w_split.data_ptr(), dtype=L.DS_BF16, Cout=Cout, Cin=3 * Cin,
-                                   cin_pad=3 * Cin, KH=3, KW=3, cout_pad=cw.cout_pad, transposed=0, k_order=1)
-            L.call("ds_pack_conv_weight", C.byref(pps), L.current_stream())
+            cw.w_split = self._pack_weight(ws, None, L.DS_BF16, Cout, 3 * Cin, 3 * Cin, 3, 3, cw.cout_pad)
             self._pack_tmp.append(ws)
-        wshape = tuple(weight.shape)
-        if ((self.dt == L.DS_BF16 or (self.split3 and Cout % 8 == 0)) and gamma is None and cin_pad == Cin and Cin % 32 == 0 and wshape[2:] == (4, 4)
-                and ((transposed and (Cin // 32) % 6 == 0 and Cout % 96 == 0) or (not transposed and (Cin // 32) % 3 == 0))):
-            # Downsample / Upsample of the U-Net: also packed as quad tiles for the halo kernel (conv_quad_halo3.hip); in the split-precision
-            # tier as [W_hi | W_hi | W_lo] over 3 Cin input channels (the kernel then reads hi / lo planes: DS_CONV_F_SPLIT_IN)
+        if s.quad_fits:
+            # in the split-precision tier as [W_hi | W_hi | W_lo] over 3 Cin input channels (the kernel then reads hi / lo planes)
             wq = weight
             if self.split3:
                 w32 = weight.detach().float()
                 hi = w32.bfloat16().float()
                 wq = torch.cat([hi, hi, w32 - hi], 0 if transposed else 1)
             cw.w_quad, cw.quad_cout_pad = pack_quad_weights(wq, transposed)
-        cw.t1 = cw.t2 = None
-        cw.ncls = 1
+        if s.init7_fits:
+            cw.w_init7 = self._pack_init7(w, "ds_pack_conv7x7_c4", 1)
+        if s.init7x3_fits:
+            cw.w_init7x3 = self._pack_init7(w, "ds_pack_conv7x7_c4_x3", 2)
         if gamma is not None:
-            cw.ncls = 9 if KH == 3 else 1
+            cw.ncls = 9 if cw.KH == 3 else 1
             cw.t1 = torch.empty(cw.ncls * Cout, dtype=torch.float32, device=self.dev)
             cw.t2 = torch.empty(cw.ncls * Cout, dtype=torch.float32, device=self.dev)
             b = self._f32(beta)
-            L.call("ds_conv_fold_tables", w.data_ptr(), L.ptr(cw.bias), g.data_ptr(), b.data_ptr(), Cout, Cin, KH, KW,
+            L.call("ds_conv_fold_tables", w.data_ptr(), L.ptr(cw.bias), g.data_ptr(), b.data_ptr(), Cout, Cin, cw.KH, cw.KW,
                    cw.t1.data_ptr(), cw.t2.data_ptr(), L.current_stream())
             self._keep += [g, b]
         self._pack_tmp += [w, g]
@@ -330,18 +312,12 @@ class UnetEngine(_EngineBase):
         d["res"] = None
         if isinstance(blk.res_conv, torch.nn.Conv2d):
             d["res"] = self._pack_conv(blk.res_conv.weight, blk.res_conv.bias)
-            c2 = d["conv2"]
-            cx = blk.res_conv.weight.shape[1]
+            c2, cx = d["conv2"], blk.res_conv.weight.shape[1]
             if c2.k_order == 1 and cx % 96 == 0:      # (the fused steps come in threes: the weight ring's phase)
                 # components:128,139 fused into conv2's launch: the 1x1 tiles ([cx/32][cout_pad][32]) precede the 3x3 tiles
                 # (a second copy: the unfused fallback — split-K at small batch — keeps reading cw.w)
                 w = self._f32(blk.res_conv.weight)
-                n = L.load().ds_pack_conv_elems(cx, 1, 1, c2.cout_pad, 0)
-                rpk = torch.empty(n, dtype=_TDT[self.dt], device=self.dev)
-                pp = L.PackConvParams(w=w.data_ptr(), gamma=None, dst=rpk.data_ptr(), dtype=self.dt, Cout=c2.Cout, Cin=cx, cin_pad=cx, KH=1, KW=1,
-                                      cout_pad=c2.cout_pad, transposed=0, k_order=1)
-                L.call("ds_pack_conv_weight", C.byref(pp), L.current_stream())
-                c2.w_fused = torch.cat([rpk, c2.w])
+                c2.w_fused = torch.cat([self._pack_weight(w, None, self.dt, c2.Cout, cx, cx, 1, 1, c2.cout_pad), c2.w])
                 c2.res_steps, c2.res_bias = cx // 32, d["res"].bias
                 self._pack_tmp.append(w)
         d["tb_off"] = None
@@ -396,24 +372,7 @@ class UnetEngine(_EngineBase):
         self._lab_w, self._lab_b, self._lab_total = [], [], 0
         self.cin0 = _up(cfg["in_dim"], self.vec)
         P = {}
-        P["init"] = self._pack_conv(m.init_conv.weight, m.init_conv.bias, cin_pad=self.cin0)
-        w0 = m.init_conv.weight
-        if (self.dt == L.DS_BF16 and tuple(w0.shape[2:]) == (7, 7) and w0.shape[0] == 96 and w0.shape[1] <= 4
-                and self.cin0 in (4, 8)):
-            # the init convolution on its own kernel: four real channels = 8 bytes per pixel, a K step = one kernel row read straight from a halo
-            wf = self._f32(w0)
-            w7 = torch.empty(L.load().ds_conv7x7_c4_weight_elems(), dtype=torch.bfloat16, device=self.dev)
-            L.call("ds_pack_conv7x7_c4", wf.data_ptr(), 96, int(w0.shape[1]), w7.data_ptr(), L.current_stream())
-            self._pack_tmp.append(wf)
-            P["init"].w_init7 = w7
-        P["init"].w_init7x3 = None
-        if (self.split3 and tuple(w0.shape[2:]) == (7, 7) and w0.shape[0] == 96 and w0.shape[1] <= 4 and self.cin0 == 4):
-            # split-precision tier: the same kernel with the fp32 input split into hi / lo bf16 on its way to LDS, fp32 output
-            wf = self._f32(w0)
-            w7 = torch.empty(2 * L.load().ds_conv7x7_c4_weight_elems(), dtype=torch.bfloat16, device=self.dev)
-            L.call("ds_pack_conv7x7_c4_x3", wf.data_ptr(), 96, int(w0.shape[1]), w7.data_ptr(), L.current_stream())
-            self._pack_tmp.append(wf)
-            P["init"].w_init7x3 = w7
+        P["init"] = self._pack_conv(m.init_conv.weight, m.init_conv.bias, cin_pad=self.cin0)      # (+ the 7x7 kernel's forms: init7_fits)
         P["downs"] = []
         for blk1, at1, blk2, at2, down in m.downs:
             P["downs"].append((self._pack_block(blk1, None), self._pack_attn(at1), self._pack_block(blk2, None),
@@ -524,38 +483,45 @@ class _PlanBuilder:
         self.ops.append((getattr(self.lib, name), args, name))
 
     # ---------------------------------------------------------------- kernels
-    def halo_ksplit(self, cw, H, W, Cin, ncc=None):
-        """Split-K factor of a 3x3 halo launch: > 1 only when (patch x channel-tile x sample) blocks cannot fill the 256 CUs.
-        One of the tiling decisions that look at the batch (the others: the split-K of Down / Upsample and conv1x1_x3, the attention
-        segments), 16-bit tiers only; fp32 never splits (batch-invariant bit for bit).  The batch looked at is the plan's FULL batch
-        (self.Btile), not the half batch of a paired plan's shared prefix."""
-        B = self.Btile
-        twl = 3
-        while (1 << twl) < W and twl < 5:
-            twl += 1
-        tw_, th_ = 1 << twl, 256 >> twl
-        pn = (-(-H // th_)) * (-(-W // tw_)) * (cw.cout_pad // 96)
-        split = ncc is not None                          # split-precision launches: K slices = whole source chunks = 27 steps each
-        ncc = Cin // 32 if ncc is None else ncc
-        # the smallest factor that fills the chip, else the largest possible (r04: 3 and 6 — every channel count is a multiple of 96, so chunk
-        # counts of 3, 9, 18 had no power-of-two slice: a 96 -> 192 layer at 256 x 64, batch 1, ran as 128 blocks of 81 steps)
-        ok = [c for c in (2, 3, 4, 6, 8) if ncc % c == 0 and ncc // c >= (1 if split else 2)]
-        if not split:      # (the bf16 tier gains nothing from the 3s: same-box A/B, batch 1 and 16)
-            ok = [c for c in ok if c in (2, 4, 8)]
-        ks = 1
-        for c in ok:
-            ks = c
-            if pn * B * c >= KSPLIT_FILL:
-                break
-        if pn * B >= KSPLIT_FILL:
-            ks = 1
-        return ks
+    def _halo3_ksplit(self, cw, x, split):
+        """Split-K factor of a 3x3 halo launch over x (split: split precision), from the plan's FULL batch (self.Btile)."""
+        return policy.halo3_ksplit(self.Btile, x.H, x.W, cw.cout_pad, x.C // 32, split)
+
+    def _split_takes(self, cw, src1=None, stride=1, pad=1, out_nchw_ptr=False):
+        """Does conv(cw, ...) run the split-precision halo kernel when its input holds hi / lo planes (DS_CONV_F_SPLIT_IN)?"""
+        return cw.w_split is not None and src1 is None and stride == 1 and pad == 1 and not out_nchw_ptr
+
+    def _quad_takes(self, cw, x, stride=1, pad=0, src1=None, res=None, gn_ab=None, out_nchw_ptr=False):
+        """Does conv(cw, x, ...) run on the four-tap halo kernel (conv_quad_halo3.hip; in the split-precision tier it reads planes)?"""
+        return (cw.w_quad is not None and src1 is None and res is None and gn_ab is None and not out_nchw_ptr and (not x.split or self.e.split3)
+                and (cw.transposed or (stride == 2 and pad == 1 and x.H % 2 == 0 and x.W % 2 == 0)))
+
+    def _conv_route(self, cw, src0, src1, stride, pad, gn_ab, act, res, want_stats, out, out_nchw_ptr, gn_src, res_fuse):
+        """The kernel a launch runs on: the first packed form the call allows (the special forms exclude each other by shape or tier)."""
+        plain = src1 is None and stride == 1 and pad == 1 and not out_nchw_ptr and res is None and gn_ab is None and not want_stats
+        if cw.w_f32n4 is not None and plain and not src0.split and out.C == 4 and act == L.ACT_NONE and res_fuse is None:
+            return "f32n4"
+        if (cw.w_x3 is not None and stride == 1 and pad == 0 and not out_nchw_ptr and not src0.split and gn_src is None and act == L.ACT_NONE
+                and src0.C % 32 == 0 and (src1.C if src1 is not None else 0) % 32 == 0):
+            return "x3"
+        if cw.w_n16 is not None and plain and not src0.split:
+            return "n16"
+        if self._split_takes(cw, src1, stride, pad, out_nchw_ptr) and src0.split:
+            return "split"
+        if self._quad_takes(cw, src0, stride, pad, src1, res, gn_ab, out_nchw_ptr):
+            return "quad"
+        if cw.k_order == 1:
+            # chunk-major weights = a single-source 3x3 stride-1 pad-1 layer packed for the LDS-halo kernel (conv3x3_halo3.hip)
+            assert src1 is None and stride == 1 and pad == 1 and src0.C % 32 == 0, "chunk-major weights reached a layer the halo kernel cannot run"
+            return "halo3"
+        return "igemm"
 
     def conv(self, cw, src0, src1=None, off1=(0, 0), stride=1, pad=0, gn_ab=None, act=L.ACT_NONE, res=None,
              want_stats=False, out=None, out_nchw_ptr=False, gn_src=None, res_fuse=None, out_split=False):
         """gn_src = (partials ptr, parts, count, eps): the consumer reduces the producer's statistics itself.
         res_fuse = (x0, x1, off1): run the block's 1x1 res_conv over pad_and_concat(x0, x1) inside this launch (HALO3 tile,
-        weights packed with the res tiles appended; the caller checked halo_ksplit() == 1)."""
+        weights packed with the res tiles appended; the caller checked that the launch does not split K).
+        The route (kernel + packed form) is picked first, then its ConvParams filled once; split-K, statistics partials and conv_meta follow."""
         if gn_src is not None:
             gn_ab = True
         e, B = self.e, self.B
@@ -570,150 +536,83 @@ class _PlanBuilder:
         assert src0.C + C1 == cw.cin_pad, (src0.C, C1, cw.cin_pad)
         if out is None:
             out = self.act(_up(cw.Cout, e.vec), oh, ow)
-        # tile: BN family fixed by packing; BM halves on the small-spatial levels so the grid still fills the chip.
-        # The TILE depends on the layer shape only, never on B.  In the fp32 tier nothing else looks at B either: a sample's result (incl.
-        # its GroupNorm partial sums) does not change with the batch it is computed in (shard == unsharded, bit for bit).  The bf16 and
-        # bf16x3 tiers additionally pick split-K (halo_ksplit and the quad / conv1x1_x3 / generic-kernel choices below, all from
-        # self.Btile) and the attention kernel generation / segment count by B (ds_attn_fused_segments, ds_attn_x3_segments): there a
-        # sample's result depends on its batch to the rounding of fp32 partial sums.
-        if cw.k_order == 1:
-            # chunk-major weights = a single-source 3x3 stride-1 pad-1 layer packed for the LDS-halo kernel (conv3x3_halo3.hip)
-            assert src1 is None and stride == 1 and pad == 1 and src0.C % 32 == 0, "chunk-major weights reached a layer the halo kernel cannot run"
-            tile = L.TILE_HALO3_256x96
-        elif cw.bn == 192:
-            tile = L.TILE_64x192 if Ho * Wo <= 1024 else L.TILE_128x192
-        elif cw.bn == 96:
-            tile = L.TILE_256x96
-        else:
-            tile = L.TILE_128x32
-        if (cw.w_f32n4 is not None and src1 is None and stride == 1 and pad == 1 and res is None and gn_ab is None and not want_stats
-                and not out_nchw_ptr and not src0.split and out.C == 4 and act == L.ACT_NONE and res_fuse is None):
+        route = self._conv_route(cw, src0, src1, stride, pad, gn_ab, act, res, want_stats, out, out_nchw_ptr, gn_src, res_fuse)
+        if route == "f32n4":
             self.op("ds_conv3x3_f32_n4", src0.off, B, H, W, src0.C, cw.w_f32n4.data_ptr(), out.off)
             return out
-        split = (cw.w_split is not None and src1 is None and stride == 1 and pad == 1 and not out_nchw_ptr and src0.split)
-        quad = (cw.w_quad is not None and src1 is None and res is None and gn_ab is None and not out_nchw_ptr and (not src0.split or e.split3) and
-                (cw.transposed or (stride == 2 and pad == 1 and H % 2 == 0 and W % 2 == 0)))
-        p = L.ConvParams(src0=src0.off, src1=(src1.off if src1 is not None else None), C0=src0.C, C1=C1, H=H, W=W,
-                         H1=(src1.H if src1 is not None else 0), W1=(src1.W if src1 is not None else 0),
-                         off_h1=off1[0], off_w1=off1[1], wpk=cw.w.data_ptr(), Cout=cw.Cout, cout_pad=cw.cout_pad,
-                         KH=cw.KH, KW=cw.KW, stride=stride, pad_h=pad, pad_w=pad, Ho=Ho, Wo=Wo,
-                         transposed=1 if cw.transposed else 0, out=out.off,
-                         out_C=out.C, out_c0=0, out_nchw_f32=0,
-                         bias=L.ptr(cw.bias), gn_ab=(gn_ab if gn_src is None else None), fold_t1=L.ptr(cw.t1) if gn_ab else None,
-                         fold_t2=L.ptr(cw.t2) if gn_ab else None, ncls=cw.ncls if gn_ab else 1, act=act,
-                         res=(res.off if res is not None else None), stats_part=None, B=B, dtype=e.dt, tile=tile, wk_order=cw.k_order)
-        if split:
-            # split-precision 3x3: input = hi / lo bf16 planes (2C channels), output = planes again (conv1: feeds conv2) or fp32 (conv2)
-            p.tile = tile = L.TILE_HALO3_256x96
-            p.dtype, p.wpk, p.wk_order, p.C0 = L.DS_BF16, cw.w_split.data_ptr(), 1, 2 * src0.C
-            p.flags = 1 | (2 if out_split else 4)
-            p.out_C = 2 * out.C if out_split else out.C
-            out.split = bool(out_split)
-        if (cw.w_n16 is not None and src1 is None and stride == 1 and pad == 1 and res is None and gn_ab is None and not want_stats
-                and not out_nchw_ptr and not src0.split):
-            p.tile = tile = L.TILE_HALO3_N16
-            p.wpk, p.cout_pad, p.wk_order = cw.w_n16.data_ptr(), 16, 1
+        # The tile depends on the layer shape only.  fp32 never splits K: a sample's result (incl. its GroupNorm partials) does not change
+        # with the batch it is computed in.  The 16-bit tiers split K by self.Btile (and pick attention segments by B): to the rounding of fp32 sums.
+        tile, dtype, src, C0, flags, wpk, cout_pad, korder, out_C = None, e.dt, src0, src0.C, 0, cw.w, cw.cout_pad, cw.k_order, out.C
         xsplit = None
-        if quad:
-            p.tile = tile = L.TILE_QUAD_HALO3
-            p.wpk, p.cout_pad, p.wk_order = cw.w_quad.data_ptr(), cw.quad_cout_pad, 2
+        if route == "x3":
+            # split-precision tier: 1x1 convolution of fp32 tensors as three bf16 MFMA products (conv1x1_x3.hip)
+            tile, dtype, flags, wpk, cout_pad, korder = 0, L.DS_BF16, 8 | 4, cw.w_x3, cw.x3_cout_pad, 0
+        elif route == "n16":
+            tile, wpk, cout_pad, korder = L.TILE_HALO3_N16, cw.w_n16, 16, 1
+        elif route == "split":
+            # split-precision 3x3: input = hi / lo bf16 planes (2C channels), output = planes again (conv1: feeds conv2) or fp32 (conv2)
+            tile, dtype, C0, flags, wpk, korder = L.TILE_HALO3_256x96, L.DS_BF16, 2 * src0.C, 1 | (2 if out_split else 4), cw.w_split, 1
+            out_C = 2 * out.C if out_split else out.C
+            out.split = bool(out_split)
+        elif route == "quad":
+            tile, wpk, cout_pad, korder = L.TILE_QUAD_HALO3, cw.w_quad, cw.quad_cout_pad, 2
             if e.split3:
                 # split-precision tier: the kernel reads hi / lo bf16 planes and writes fp32.  The planes come from the producer where it
                 # wrote them (the attention block in front of a Down / Upsample, r04) — otherwise one streaming pass re-stores the fp32 input
-                given = src0 if src0.split else getattr(src0, "planes", None)
-                if given is None:
-                    xsplit = self.act(src0.C, H, W)
+                src = src0 if src0.split else src0.planes
+                if src is None:
+                    src = xsplit = self.act(src0.C, H, W)
                     self.op("ds_split_planes", src0.off, xsplit.off, B * H * W, src0.C)
-                    given = xsplit
                 elif not src0.split:
-                    xsplit, src0.planes = given, None                      # (released after this launch)
-                p.src0, p.C0, p.dtype, p.flags = given.off, 2 * src0.C, L.DS_BF16, 1 | 4
+                    xsplit, src0.planes = src, None                      # (released after this launch)
+                dtype, C0, flags = L.DS_BF16, 2 * src0.C, 1 | 4
+        else:
+            tile = policy.igemm_tile(cw.bn, Ho * Wo, cw.k_order)
+        extra = {}
         if gn_src is not None:
-            p.gn_part, p.gn_parts, p.gn_count, p.gn_eps = gn_src[0], gn_src[1], float(gn_src[2]), gn_src[3]
+            extra.update(gn_part=gn_src[0], gn_parts=gn_src[1], gn_count=float(gn_src[2]), gn_eps=gn_src[3])
         if res_fuse is not None:
             x0, x1, xoff = res_fuse
             assert tile == L.TILE_HALO3_256x96 and cw.res_steps == (x0.C + (x1.C if x1 is not None else 0)) // 32 and res is None
-            p.res_src0, p.res_C0, p.res_steps, p.res_bias, p.wpk = x0.off, x0.C, cw.res_steps, L.ptr(cw.res_bias), cw.w_fused.data_ptr()
+            wpk = cw.w_fused
+            extra.update(res_src0=x0.off, res_C0=x0.C, res_steps=cw.res_steps, res_bias=L.ptr(cw.res_bias))
             if x1 is not None:
-                p.res_src1, p.res_C1, p.res_H1, p.res_W1, p.res_off_h1, p.res_off_w1 = x1.off, x1.C, x1.H, x1.W, xoff[0], xoff[1]
-        slab = None
-        if tile == L.TILE_HALO3_256x96 and res_fuse is None:
-            # (split-precision launches too since r04: three times the K steps per block — a 32 x 8-level layer at batch 1 was 8 blocks of
-            # 648 serial steps; like the bf16 tier's, this decision looks at B: partial sums are added in a different order, nothing else)
-            ks = self.halo_ksplit(cw, H, W, src0.C, src0.C // 32 if split else None)      # (K slices = whole source chunks = triples of virtual chunks)
-            if ks > 1:
-                slab = self.raw(ks * B * Ho * Wo * _up(cw.Cout, 8) * 4)
-                p.ksplit, p.slab = ks, slab[0]
-        elif tile == L.TILE_QUAD_HALO3:
-            # Down / Upsample on the halo pipeline (r04): K slices of whole groups of six chunks (the kernel's loop period)
-            twl = 3
-            while (1 << twl) < Wo and twl < 5:
-                twl += 1
-            nblk = (-(-Ho // (256 >> twl))) * (-(-Wo // (1 << twl))) * (cw.quad_cout_pad // 96) * self.Btile
-            nch = (1 if cw.transposed else 4) * ((3 * src0.C // 32) if e.split3 else src0.C // 32)
-            ks = 1
-            if nblk < KSPLIT_FILL:
-                for c in ((2, 3, 4, 6, 8) if e.split3 else (2, 4, 8)):
-                    if nch % c == 0 and (nch // c) % 6 == 0:
-                        ks = c
-                        if nblk * c >= KSPLIT_FILL:
-                            break
-            if ks > 1:
-                slab = self.raw(ks * B * oh * ow * _up(cw.Cout, 8) * 4)
-                p.ksplit, p.slab = ks, slab[0]
-        elif e.dt == L.DS_BF16 and tile in (L.TILE_64x192, L.TILE_128x192, L.TILE_256x96):
-            # same idea for the generic kernel (4x4 stride-2, transposed and 1x1 layers of the small-spatial levels):
-            # their K loops are long (up to 192 steps) and their grids small
-            bm_, bn_ = {L.TILE_64x192: (64, 192), L.TILE_128x192: (128, 192), L.TILE_256x96: (256, 96)}[tile]
-            nblk = (-(-(Ho * Wo) // bm_)) * (cw.cout_pad // bn_) * self.Btile * (4 if cw.transposed else 1)
+                extra.update(res_src1=x1.off, res_C1=x1.C, res_H1=x1.H, res_W1=x1.W, res_off_h1=xoff[0], res_off_w1=xoff[1])
+        # K slices at small batches: the grid of (tile x channel-tile x sample) blocks cannot fill the 256 CUs (conv_policy)
+        ks = 1
+        if route in ("halo3", "split") and res_fuse is None:
+            ks = self._halo3_ksplit(cw, src0, route == "split")
+        elif route == "quad":
+            ks = policy.quad_ksplit(self.Btile, Ho, Wo, cw.quad_cout_pad, (1 if cw.transposed else 4) * (3 if e.split3 else 1) * src0.C // 32, e.split3)
+        elif route == "igemm" and e.dt == L.DS_BF16:
             nq = -(-((4 if cw.transposed else cw.KH * cw.KW) * (src0.C + C1)) // 32)
-            ks = 1
-            while ks < 8 and nblk * ks < 384 and nq // (ks * 2) >= 6:
-                ks *= 2
-            while ks > 1 and (ks - 1) * (-(-nq // ks)) >= nq:      # never an empty last slice (ceil(nq / ks) steps per slice)
-                ks //= 2
-            if ks > 1:
-                slab = self.raw(ks * B * oh * ow * _up(cw.Cout, 8) * 4)
-                p.ksplit, p.slab = ks, slab[0]
-        if (cw.w_x3 is not None and stride == 1 and pad == 0 and not out_nchw_ptr and not src0.split and gn_src is None and act == L.ACT_NONE
-                and src0.C % 32 == 0 and C1 % 32 == 0 and res_fuse is None and slab is None):
-            # split-precision tier: 1x1 convolution of fp32 tensors as three bf16 MFMA products (conv1x1_x3.hip)
-            p.dtype, p.flags, p.wpk, p.cout_pad, p.wk_order, p.tile = L.DS_BF16, 8 | 4, cw.w_x3.data_ptr(), cw.x3_cout_pad, 0, 0
-            # K slices at small batches (r04): res_conv of a 64 x 16-level block at batch 1 was 16 blocks of 24 - 36 serial chunks
-            nblk, nq, ks = (-(-(Ho * Wo) // 256)) * (cw.x3_cout_pad // 96) * self.Btile, (src0.C + C1) // 32, 1
-            if nblk < KSPLIT_FILL:
-                for c in (2, 3, 4, 6, 8):
-                    if nq // c >= 3 and (c - 1) * (-(-nq // c)) < nq:
-                        ks = c
-                        if nblk * c >= KSPLIT_FILL:
-                            break
-            if ks > 1:
-                slab = self.raw(ks * B * Ho * Wo * _up(cw.Cout, 8) * 4)
-                p.ksplit, p.slab = ks, slab[0]
-            if want_stats:
-                parts = self.lib.ds_conv1x1_x3_stats_parts(C.byref(p))
-                st = self.raw(B * parts * 2 * 4)
-                p.stats_part = st[0]
-                out.stats = (st, parts)
-            self.op("ds_conv1x1_x3", p)
-            if slab is not None:
-                self.op("ds_conv_splitk_reduce", p)
-                self.free_raw(slab)
-            return out
+            ks = policy.igemm_ksplit(self.Btile, tile, Ho, Wo, cw.cout_pad, nq, 4 if cw.transposed else 1)
+        elif route == "x3":
+            ks = policy.x3_1x1_ksplit(self.Btile, Ho, Wo, cw.x3_cout_pad, (src0.C + C1) // 32)
+        slab = None
+        if ks > 1:
+            slab = self.raw(ks * B * oh * ow * _up(cw.Cout, 8) * 4)
+            extra.update(ksplit=ks, slab=slab[0])
+        if src1 is not None:
+            extra.update(src1=src1.off, H1=src1.H, W1=src1.W)
+        p = L.ConvParams(src0=src.off, C0=C0, C1=C1, H=H, W=W, off_h1=off1[0], off_w1=off1[1], wpk=wpk.data_ptr(), Cout=cw.Cout,
+                         cout_pad=cout_pad, KH=cw.KH, KW=cw.KW, stride=stride, pad_h=pad, pad_w=pad, Ho=Ho, Wo=Wo,
+                         transposed=int(cw.transposed), out=out.off, out_C=out_C, out_c0=0, out_nchw_f32=0,
+                         bias=L.ptr(cw.bias), gn_ab=(gn_ab if gn_src is None else None), fold_t1=L.ptr(cw.t1) if gn_ab else None,
+                         fold_t2=L.ptr(cw.t2) if gn_ab else None, ncls=cw.ncls if gn_ab else 1, act=act,
+                         res=(res.off if res is not None else None), stats_part=None, B=B, dtype=dtype, tile=tile, wk_order=korder,
+                         flags=flags, **extra)
         if want_stats:
-            parts = self.lib.ds_conv_stats_parts(C.byref(p))
+            parts = (self.lib.ds_conv1x1_x3_stats_parts if route == "x3" else self.lib.ds_conv_stats_parts)(C.byref(p))
             st = self.raw(B * parts * 2 * 4)
             p.stats_part = st[0]
             out.stats = (st, parts)
-        # algorithmic work of this launch: real taps x real channels (padding excluded)
-        taps = 16 if cw.transposed else cw.KH * cw.KW
-        cin_real = min(src0.C + C1, getattr(cw, "cin_real", src0.C + C1))
-        flops = 2.0 * B * Ho * Wo * cw.Cout * taps * cin_real
-        if res_fuse is not None:
-            flops += 2.0 * B * Ho * Wo * cw.Cout * 32 * cw.res_steps
-        self.conv_meta[len(self.ops)] = (tile, flops, f"{cw.KH}x{cw.KW}{'T' if cw.transposed else ''} {src0.C + C1}->{cw.Cout} @{Ho}x{Wo}"
-                                         + (f" +1x1 {32 * cw.res_steps}" if res_fuse is not None else ""))
-        self.op("ds_conv_igemm", p)
+        if route == "x3":
+            self.op("ds_conv1x1_x3", p)
+        else:
+            self.conv_meta[len(self.ops)] = policy.conv_meta(tile, B, Ho, Wo, cw.Cout, cw.KH, cw.KW, cw.transposed, src0.C + C1, cw.cin_real,
+                                                             32 * cw.res_steps if res_fuse is not None else 0)
+            self.op("ds_conv_igemm", p)
         if xsplit is not None:
             self.free(xsplit)
         if slab is not None:
@@ -773,7 +672,7 @@ class _PlanBuilder:
                            tb_stride=e._tb_total, out=h.off, stats_part=None, B=B, dtype=e.dt,
                            wexp=(d["dw_exp"].data_ptr() if d.get("dw_exp") is not None else None))
         # split-precision tier: the two tensors only 3x3 convolutions read (h, g) are stored as hi / lo bf16 planes
-        sp = (d["conv1"].w_split is not None and d["conv2"].w_split is not None and s0.C % 16 == 0 and (s1 is None or s1.C % 16 == 0))
+        sp = (self._split_takes(d["conv1"]) and self._split_takes(d["conv2"]) and s0.C % 16 == 0 and (s1 is None or s1.C % 16 == 0))
         if sp:
             p.out_split, h.split = 1, True
         parts = self.lib.ds_dwconv_stats_parts(C.byref(p))
@@ -787,18 +686,11 @@ class _PlanBuilder:
         self.free_raw(st1)
         src2_, st2 = self.stats_src(g, d["conv1"].Cout * H * W)
         c2 = d["conv2"]
-        if (d["res"] is not None and c2.res_steps and
-                self.halo_ksplit(c2, H, W, g.C) == 1):
+        if c2.res_steps and self._halo3_ksplit(c2, g, g.split) == 1:          # (res_steps: the block's res_conv is packed in front)
             out = self.conv(c2, g, pad=1, gn_src=src2_, want_stats=want_stats, res_fuse=(s0, s1, off1))
-            self.free(g)
-            self.free_raw(st2)
-            return out
-        if d["res"] is not None:
-            out = self.conv(d["res"], s0, s1, off1)           # 1x1 res_conv straight into the output buffer
-            res = out
         else:
-            out, res = None, s0
-        out = self.conv(d["conv2"], g, pad=1, gn_src=src2_, res=res, want_stats=want_stats, out=out)
+            out = self.conv(d["res"], s0, s1, off1) if d["res"] is not None else None      # 1x1 res_conv straight into the output buffer
+            out = self.conv(c2, g, pad=1, gn_src=src2_, res=s0 if out is None else out, want_stats=want_stats, out=out)
         self.free(g)
         self.free_raw(st2)
         return out
@@ -862,11 +754,6 @@ class _PlanBuilder:
         self.free_raw(ab)
         return out
 
-    def _quad_takes(self, cw, x, stride=1):
-        """Will conv(cw, an activation shaped like x) run on the four-tap halo kernel of the split-precision tier (which reads planes)?"""
-        e = self.e
-        return bool(e.split3 and cw.w_quad is not None and (cw.transposed or (stride == 2 and x.H % 2 == 0 and x.W % 2 == 0)))
-
     def block(self, d, x, want_stats=False):
         return self.convnext(d, x, want_stats) if self.e.cfg["use_convnext"] else self.resnet(d, x, want_stats)
 
@@ -893,7 +780,7 @@ class _PlanBuilder:
             # one input stream: k/v projection + softmax_n + k.v^T, then q projection + softmax_d + ctx^T.q + to_out
             # segments of partials: the library's choice for this shape and batch — N / 128 <= 32 for the first-generation context pass, one
             # round of blocks (one segment per wave) for the second generation, which it runs from U-Net batch 96 on (the bf16 tier's second
-            # tiling decision that looks at B, after halo_ksplit)
+            # tiling decision that looks at B, after split-K)
             nseg = self.lib.ds_attn_fused_segments(B, N, Cc)
             part = self.raw(self.lib.ds_linattn_part_floats(B, heads, nseg) * 4)
             ctx = self.raw(B * heads * 1024 * 4)
@@ -1055,17 +942,16 @@ class _PlanBuilder:
             self.alloc_B = Bfull
         xin = self.act(e.cin0, H, W)
         self.ops.append(("input", xin.off, self.B))
-        if getattr(P["init"], "w_init7", None) is not None:
-            cw = P["init"]
+        cw = P["init"]
+        if cw.w_init7 is not None:
             x = self.act(96, H, W)
-            self.conv_meta[len(self.ops)] = (L.TILE_INIT7, 2.0 * B * H * W * 96 * 49 * cw.cin_real, f"7x7 {cw.cin_real}->96 @{H}x{W}")
+            self.conv_meta[len(self.ops)] = policy.conv_meta(L.TILE_INIT7, B, H, W, 96, 7, 7, False, cw.cin_real, cw.cin_real)
             self.op("ds_conv7x7_c4", xin.off, B, H, W, e.cin0, cw.w_init7.data_ptr(), L.ptr(cw.bias), x.off)
-        elif getattr(P["init"], "w_init7x3", None) is not None:
-            cw = P["init"]
+        elif cw.w_init7x3 is not None:
             x = self.act(96, H, W)
             self.op("ds_conv7x7_c4_x3", xin.off, B, H, W, cw.w_init7x3.data_ptr(), L.ptr(cw.bias), x.off)
         else:
-            x = self.conv(P["init"], xin, pad=3)
+            x = self.conv(cw, xin, pad=3)
         self.free(xin)
         self.n_cond_join = len(self.ops)               # first op that may consume a conditioning output
         skips = [x]
@@ -1086,7 +972,7 @@ class _PlanBuilder:
             self.free(y)
             skips.append(x)
             y = self.block(b2, x, True)
-            x = self.attention(a2, y, planes="both" if self._quad_takes(down, y, stride=2) else None)
+            x = self.attention(a2, y, planes="both" if (e.split3 and self._quad_takes(down, y, stride=2, pad=1)) else None)
             self.free(y)
             skips.append(x)
             x = self.conv(down, x, stride=2, pad=1)
@@ -1113,7 +999,7 @@ class _PlanBuilder:
                 y = self.block(blk, (sk, x), True)
                 self.free(sk)
                 self.free(x)
-                x = self.attention(at, y, planes="only" if (do_up and self._quad_takes(up, y)) else None)
+                x = self.attention(at, y, planes="only" if (do_up and e.split3 and self._quad_takes(up, y)) else None)
                 self.free(y)
                 if do_up:
                     y = self.conv(up, x)
