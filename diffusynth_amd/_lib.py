@@ -42,14 +42,21 @@ def _parse_structs(text):
     return out
 
 
+def _parse_defines(text, prefix):
+    return {k: int(v) for k, v in re.findall(r"^#define\s+(%s\w*)\s+(-?\d+)\b" % prefix, text, flags=re.M)}
+
+
 with open(_HEADER) as _f:
-    _STRUCTS = _parse_structs(_f.read())
+    _HEADER_TEXT = _f.read()
+_STRUCTS = _parse_structs(_HEADER_TEXT)
+SR = _parse_defines(_HEADER_TEXT, "DS_SR_")     # ds_step_rows table layout (field indices and row widths)
 ConvParams = _STRUCTS["ds_conv_params"]
 PackConvParams = _STRUCTS["ds_pack_conv_params"]
 DwconvParams = _STRUCTS["ds_dwconv_params"]
 GnApplyParams = _STRUCTS["ds_gn_apply_params"]
 AttnParams = _STRUCTS["ds_attn_params"]
 StepParams = _STRUCTS["ds_step_params"]
+StepRowsParams = _STRUCTS["ds_step_rows_params"]
 AttnFusedParams = _STRUCTS["ds_attn_fused_params"]
 AttnX3Params = _STRUCTS["ds_attn_x3_params"]
 VqAttnParams = _STRUCTS["ds_vq_attn_params"]
@@ -109,6 +116,7 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_conv1x1_in_nchw": (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _P, _P]),
     "ds_nhwc_to_nchw": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "ds_ddim_step": (C.c_int, [C.POINTER(StepParams), _P]),
+    "ds_step_rows": (C.c_int, [C.POINTER(StepRowsParams), _P]),
     "ds_philox_normal": (C.c_int, [_P, _SZ, _U64, _U64, _P]),
     "ds_gather_cols": (C.c_int, [_P, _I, _I, _P, _I, _P, _P]),
     "ds_vq_nearest": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

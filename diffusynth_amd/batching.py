@@ -1,0 +1,382 @@
+"""SamplingBatcher — concurrent sampler calls sharing U-Net steps.
+
+Every caller of the reference builds its own DiffSynthSampler and runs one call to completion (text2sound, sound2sound,
+inpainting, one batch-1 ``inpaint_sample`` per note of the MIDI arranger).  A batch-1 step leaves most of the card idle
+(DESIGN.md §5), so this module runs many such calls together: each call is submitted with the sampler it would have been
+run on, and every tick advances every active call by one step with ONE U-Net forward per bucket and ONE ``ds_step_rows``
+launch per bucket that applies each row's own guidance scale, coefficients, inpaint blend and step noise.
+
+    b = SamplingBatcher(unet, max_rows=128)
+    h = b.submit(dss, "inpaint_sample", shape, 0.7, guide, mask, condition=c, sampler="ddpm", use_dynamic_mask=True, seed=7)
+    b.run()
+    imgs, initial_noise = h.result()
+
+A call's arguments and return values are those of ``getattr(dss, method)(unet, ...)``.  The call's prologue (initial noise,
+guide, q_sample, masks, step list, coefficient tables) is the sampler's own (``DiffSynthSampler._loop_prologue``); its draws
+come from a private ``torch.Generator`` (or the sampler's Philox stream), so a request's noise does not depend on the other
+requests.  In the fp32 tier no tiling choice of the U-Net depends on the batch, so a request's result is the same bits as the
+call run alone; in the bf16x3 / bf16 tiers split-K factors and attention segment counts follow the U-Net batch, so a result
+depends on its batch mates within the tier's error contract (a batcher that holds one request is the standalone call).
+
+Buckets: one per (height, width, has_condition).  A tick runs every non-empty bucket: the U-Net batch is every request's rows
+plus, for classifier-free guidance (CFG), one unconditional row per row.  When every request of a bucket uses CFG the batch is
+laid out as the standalone call lays it out, ``[x; x]`` with ``paired_halves=True``; otherwise each CFG request contributes
+``[x (unconditional); x (conditional)]`` next to the plain rows of the others.  The step kernel writes the next U-Net input
+(duplicate rows included) directly; the batch is re-laid only when requests join or leave.
+"""
+import ctypes as C
+import inspect
+import time as _time
+from collections import deque
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .sampler import LOOP_PROGRAM
+
+METHODS = ("sample", "img_guided_sample", "inpaint_sample", "interpolate")
+_NOISE_NONE, _NOISE_DRAW, _NOISE_PHILOX = 0, 1, 2
+
+
+def _seed_from_global():
+    """One draw of torch's global generator: the seed of a request submitted with seed=None (not reproducible, as in the reference)."""
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def request_program(dss, method, *args, **kwargs):
+    """(LoopProgram, bound arguments) of ``getattr(dss, method)(model, *args, **kwargs)``: what the call computes before its first
+    model call (DiffSynthSampler._loop_prologue), with the draws on the sampler's current generator.  Runs on CPU samplers too."""
+    if method not in METHODS:
+        raise ValueError("method must be one of %s, got %r" % (", ".join(METHODS), method))
+    fn = getattr(dss, method)
+    bound = inspect.signature(fn).bind(LOOP_PROGRAM, *args, **kwargs)
+    bound.apply_defaults()
+    return fn(LOOP_PROGRAM, *args, **kwargs), bound.arguments
+
+
+class SamplingHandle:
+    """One submitted call.  ``result()`` returns what the call returns (running the batcher until this call is done)."""
+
+    def __init__(self, batcher, req):
+        self._batcher, self._req = batcher, req
+
+    def done(self):
+        return self._req.out is not None
+
+    def result(self):
+        while self._req.out is None:
+            self._batcher.step()
+        return self._req.out
+
+
+class _Request:
+    def __init__(self, dss, method, prog, args, unet_dev):
+        self.dss, self.method, self.prog = dss, method, prog
+        self.B, self.C, self.H, self.W = prog.shape
+        self.cfg = dss.CFG != 1.0
+        self.scale = float(dss.CFG)
+        self.unet_rows = self.B * (2 if self.cfg else 1)
+        self.sampler = args["sampler"]
+        cond = args["condition"]
+        self.cond = None if cond is None else cond.to(unet_dev)
+        self.uncond = None
+        if self.cfg:
+            u = dss.unconditional_condition
+            self.uncond = u.unsqueeze(0).repeat(*([self.B] + [1] * len(u.shape))).to(unet_dev)     # (DiffSynthSampler._predict)
+        self.key = (self.H, self.W, self.cond is not None)
+        self.k = 0                      # next step
+        self.state = prog.img.contiguous().float()
+        self.imgs = [prog.img]
+        self.out = None
+        if self.sampler == "ddpm":
+            self.draw_w, self.cols = dss._step_noise_layout(self.W)
+        self.mapped = [int(dss.timestep_map[i]) for i in prog.steps]
+
+
+class _Bucket:
+    def __init__(self, key):
+        self.key = key
+        self.reqs = []
+        self.dirty = True               # the request set changed: the U-Net input is re-laid at the next tick
+        self.x = None                   # the U-Net input of the next tick (written by the previous tick's ds_step_rows)
+
+
+class SamplingBatcher:
+    """See the module docstring.  ``max_rows`` bounds the U-Net rows (CFG rows counted twice) of all requests in flight and
+    ``max_buckets`` (default: the number of plans the U-Net's engine keeps, DS_MAX_PLANS) the buckets live at once; requests are
+    admitted first in, first out at the start of a tick, and a request that does not fit waits (and holds back the ones after it).
+    Not thread-safe; the U-Net is run on the current stream."""
+
+    def __init__(self, unet, max_rows=128, max_buckets=None):
+        from .engine import max_plans
+        self.unet = unet
+        self.max_rows = int(max_rows)
+        if self.max_rows < 1:
+            raise ValueError("max_rows must be >= 1")
+        # a tick visits every live bucket, one U-Net plan each: more live buckets than the engine keeps plans would rebuild every
+        # plan on every tick (LRU round robin), so admission holds a request of a new bucket while this many are live
+        self.max_buckets = max_plans() if max_buckets is None else int(max_buckets)
+        if self.max_buckets < 1:
+            raise ValueError("max_buckets must be >= 1")
+        self.dev = next(unet.parameters()).device
+        self._pending = deque()
+        self._buckets = {}
+        self._inflight = set()
+        self._geometry = None           # (height, channels) shared by every request in flight
+        self._stage = [None, None]      # double-buffered pinned staging of the per-tick upload: (host tensor, event)
+        self._flip = 0
+        self.ticks = 0
+        self.plan_builds = 0
+        self.host_seconds = 0.0
+        self.unet_batches = set()       # distinct (U-Net batch, H, W, has condition, paired) the ticks have run
+
+    # ------------------------------------------------------------------ submission
+    def submit(self, dss, method, /, *args, **kwargs):
+        """Queue ``getattr(dss, method)(unet, *args, **kwargs)``; returns a SamplingHandle.  Rejected here: an unknown method, a
+        sampler already in flight, a sharded sampler, more U-Net rows than max_rows, and a height / channel count that differs from
+        the requests in flight.  The call's prologue (its noise draws included) runs now."""
+        if method not in METHODS:
+            raise ValueError("method must be one of %s, got %r" % (", ".join(METHODS), method))
+        if id(dss) in self._inflight:
+            raise RuntimeError("this DiffSynthSampler already has a call in flight; build one sampler per concurrent call")
+        if dss.shard is not None:
+            raise ValueError("sharded samplers (shard=) are served by diffusynth_amd.dist, not by the batcher")
+        bound = inspect.signature(getattr(dss, method)).bind(LOOP_PROGRAM, *args, **kwargs)
+        bound.apply_defaults()
+        a = bound.arguments
+        shape = tuple(int(v) for v in a["shape"])
+        if self._geometry is not None:
+            assert shape[1] == self._geometry[1] and dss.channels == self._geometry[1], "shape[1] != self.channels"
+            assert shape[2] == self._geometry[0] and dss.height == self._geometry[0], "shape[2] != self.height"
+        cfg = dss.CFG != 1.0
+        rows = shape[0] * (2 if cfg else 1)
+        if rows > self.max_rows:
+            raise ValueError("the request needs %d U-Net rows, more than max_rows=%d" % (rows, self.max_rows))
+        if cfg and a["condition"] is None:
+            raise ValueError("classifier-free guidance (CFG != 1) needs a condition")
+        # every batched call gets a private generator: the entry point's _seed(seed) then seeds it instead of torch's global
+        # generators.  A Philox call draws nothing from it (its noise is the sampler's counter stream), so it lives on the CPU.
+        if dss.noise_device == "philox":
+            dss._generator = torch.Generator()
+        else:
+            dss._generator = torch.Generator(device=dss.device if dss.noise_device is None else dss.noise_device)
+            if a.get("seed") is None:
+                dss._generator.manual_seed(_seed_from_global())
+        try:
+            prog = getattr(dss, method)(LOOP_PROGRAM, *args, **kwargs)
+            req = _Request(dss, method, prog, a, self.dev)
+        except BaseException:
+            dss._generator = None
+            raise
+        self._inflight.add(id(dss))
+        self._geometry = (req.H, req.C)
+        h = SamplingHandle(self, req)
+        if not prog.steps:                          # nothing to run (start == end): the call's result is its prologue
+            self._retire(req)
+        else:
+            self._pending.append(req)
+        return h
+
+    def _retire(self, req):
+        req.out = (req.imgs, req.prog.initial_noise)
+        req.dss._generator = None
+        self._inflight.discard(id(req.dss))
+        if not self._inflight:
+            self._geometry = None
+
+    # ------------------------------------------------------------------ ticks
+    def active(self):
+        return sum(len(b.reqs) for b in self._buckets.values()) + len(self._pending)
+
+    def run(self):
+        while self.active():
+            self.step()
+
+    @torch.no_grad()
+    def step(self):
+        """One tick: admit waiting requests, then advance every active request by one step."""
+        t0 = _time.perf_counter()
+        used = sum(r.unet_rows for b in self._buckets.values() for r in b.reqs)
+        while self._pending and used + self._pending[0].unet_rows <= self.max_rows:
+            if self._pending[0].key not in self._buckets and len(self._buckets) >= self.max_buckets:
+                break
+            r = self._pending.popleft()
+            b = self._buckets.get(r.key)
+            if b is None:
+                b = self._buckets[r.key] = _Bucket(r.key)
+            b.reqs.append(r)
+            b.dirty = True
+            used += r.unet_rows
+        eng = self.unet._engine
+        builds0 = getattr(eng, "plan_builds", 0) if eng is not None else 0
+        for key in list(self._buckets):
+            b = self._buckets[key]
+            if b.reqs:
+                self._tick(b)
+            if not b.reqs:
+                del self._buckets[key]
+        eng2 = self.unet._engine
+        if eng2 is not None:
+            self.plan_builds += eng2.plan_builds - (builds0 if eng2 is eng else 0)
+        self.ticks += 1
+        self.host_seconds += _time.perf_counter() - t0
+
+    def _layout(self, b):
+        """Row layout of the bucket's U-Net batch: per request (x row of its first state row, eps row, conditional eps row or -1,
+        duplicate row or -1), the U-Net batch size and whether it is the paired [x; x] form."""
+        paired = all(r.cfg for r in b.reqs)
+        lay, base = [], 0
+        if paired:
+            n = sum(r.B for r in b.reqs)
+            for r in b.reqs:
+                lay.append((base, base, n + base, n + base))
+                base += r.B
+            return lay, 2 * n, True
+        for r in b.reqs:
+            if r.cfg:
+                lay.append((base, base, base + r.B, base + r.B))
+            else:
+                lay.append((base, base, -1, -1))
+            base += r.unet_rows
+        return lay, base, False
+
+    def _relayout(self, b):
+        b.lay, b.Bu, b.paired = self._layout(b)
+        xs, conds = [], []
+        if b.paired:
+            xs = [r.state for r in b.reqs] * 2
+            if b.key[2]:
+                conds = [r.uncond for r in b.reqs] + [r.cond for r in b.reqs]
+        else:
+            for r in b.reqs:
+                xs += [r.state, r.state] if r.cfg else [r.state]
+                if b.key[2]:
+                    conds += [r.uncond, r.cond] if r.cfg else [r.cond]
+        b.x = torch.cat(xs, 0).contiguous()
+        b.cond = torch.cat(conds, 0).contiguous() if conds else None
+        b.dirty = False
+
+    def _staging(self, nbytes):
+        """A pinned host buffer of >= nbytes whose previous upload has completed (two alternate)."""
+        i = self._flip
+        self._flip ^= 1
+        st = self._stage[i]
+        if st is None or st[0].numel() < nbytes:
+            st = self._stage[i] = (torch.empty(max(nbytes, 1 << 16) * 2, dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
+        else:
+            st[1].synchronize()
+        return st
+
+    def _tick(self, b):
+        if b.dirty:
+            self._relayout(b)
+        reqs, Bu = b.reqs, b.Bu
+        H, W = b.key[0], b.key[1]
+        Cc = reqs[0].C
+        R = sum(r.B for r in reqs)
+        ni, nf, npp = L.SR["DS_SR_NI"], L.SR["DS_SR_NF"], L.SR["DS_SR_NP"]
+        # column tables of the DDPM requests (one per distinct layout)
+        col_tabs, col_off, n_cols = {}, {}, 0
+        for r in reqs:
+            if r.sampler == "ddpm":
+                key = tuple(r.cols)
+                if key not in col_tabs:
+                    col_tabs[key] = n_cols
+                    n_cols += len(key)
+                col_off[id(r)] = col_tabs[key]
+
+        def up(n):
+            return (n + 15) & ~15
+        o_t, o_i = 0, up(8 * Bu)
+        o_f = o_i + up(4 * R * ni)
+        o_p = o_f + up(4 * R * nf)
+        o_c = o_p + up(8 * R * npp)
+        nbytes = o_c + up(4 * max(n_cols, 1))
+        host, ev = self._staging(nbytes)
+        hb = host.numpy()
+        tim = hb[o_t:o_t + 8 * Bu].view(np.int64)
+        irow = hb[o_i:o_i + 4 * R * ni].view(np.int32).reshape(R, ni)
+        frow = hb[o_f:o_f + 4 * R * nf].view(np.float32).reshape(R, nf)
+        prow = hb[o_p:o_p + 8 * R * npp].view(np.uint64).reshape(R, npp)
+        cols = hb[o_c:o_c + 4 * max(n_cols, 1)].view(np.int32)
+        for key, off in col_tabs.items():
+            cols[off:off + len(key)] = key
+        S = L.SR
+        keep = []
+        row = 0
+        CHW = Cc * H * W
+        for r, (x0, e0, ec0, d0) in zip(reqs, b.lay):
+            k, B, prog = r.k, r.B, r.prog
+            sl = slice(row, row + B)
+            ar = np.arange(B, dtype=np.int32)
+            ar64 = ar.astype(np.uint64)
+            tim[x0:x0 + B] = r.mapped[k]
+            if r.cfg:
+                tim[ec0:ec0 + B] = r.mapped[k]
+            irow[sl] = 0
+            irow[sl, S["DS_SR_X"]] = x0 + ar
+            irow[sl, S["DS_SR_EPS"]] = e0 + ar
+            irow[sl, S["DS_SR_EPSC"]] = (ec0 + ar) if ec0 >= 0 else -1
+            irow[sl, S["DS_SR_OUT"]] = x0 + ar
+            irow[sl, S["DS_SR_DUP"]] = (d0 + ar) if d0 >= 0 else -1
+            frow[sl] = 0
+            frow[sl, S["DS_SR_COEF"]:S["DS_SR_COEF"] + 5] = prog.coef_cpu[k].numpy()
+            frow[sl, S["DS_SR_CFG"]] = r.scale
+            prow[sl] = 0
+            if prog.inpaint:
+                mode, m = prog.blends[k]
+                irow[sl, S["DS_SR_BLEND"]] = mode
+                chw = 0 if m.shape[1] == 1 else 1
+                irow[sl, S["DS_SR_MASK_CHW"]] = chw
+                if mode == 1:
+                    frow[sl, S["DS_SR_Q0"]:S["DS_SR_Q1"] + 1] = prog.q_cpu[k].numpy()
+                    prow[sl, S["DS_SR_INIT"]] = np.uint64(prog.init.data_ptr()) + np.uint64(4 * CHW) * ar64
+                prow[sl, S["DS_SR_GUIDE"]] = np.uint64(prog.guide.data_ptr()) + np.uint64(4 * CHW) * ar64
+                prow[sl, S["DS_SR_MASKP"]] = np.uint64(m.data_ptr()) + np.uint64(4 * (CHW if chw else H * W)) * ar64
+            if r.sampler == "ddpm":
+                dss = r.dss
+                draw_shape = (dss.max_batchsize, Cc, H, r.draw_w)
+                irow[sl, S["DS_SR_SAMPLE"]] = ar
+                irow[sl, S["DS_SR_DRAW_ROWS"]] = dss.max_batchsize
+                irow[sl, S["DS_SR_DRAW_W"]] = r.draw_w
+                irow[sl, S["DS_SR_COLS"]] = col_off[id(r)]
+                if dss.noise_device == "philox":        # the kernel computes the draw: only its counters are reserved
+                    irow[sl, S["DS_SR_NOISE"]] = _NOISE_PHILOX
+                    prow[sl, S["DS_SR_SEED"]] = dss._philox_seed
+                    prow[sl, S["DS_SR_OFFSET"]] = dss._philox_take(int(np.prod(draw_shape)))
+                else:                                   # the standalone call's draw, on the request's own generator
+                    raw = dss._randn(draw_shape, B).contiguous()
+                    keep.append(raw)
+                    irow[sl, S["DS_SR_NOISE"]] = _NOISE_DRAW
+                    prow[sl, S["DS_SR_DRAW"]] = raw.data_ptr()
+            row += B
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        dev.copy_(host[:nbytes], non_blocking=True)
+        ev.record()
+        t_dev = dev[o_t:o_t + 8 * Bu].view(torch.int64)
+        paired = b.paired and getattr(self.unet, "cfg_paired_halves", False)
+        self.unet_batches.add((Bu, H, W, b.key[2], paired))
+        if paired:
+            eps = self.unet(b.x, t_dev, b.cond, paired_halves=True)
+        else:
+            eps = self.unet(b.x, t_dev, b.cond)
+        out = torch.empty_like(b.x)
+        p = L.StepRowsParams(x=b.x.data_ptr(), eps=eps.data_ptr(), out=out.data_ptr(), irow=dev.data_ptr() + o_i,
+                             frow=dev.data_ptr() + o_f, prow=dev.data_ptr() + o_p, cols=(dev.data_ptr() + o_c) if n_cols else None,
+                             R=R, C=Cc, H=H, W=W, Bx=Bu, Beps=eps.shape[0], Bout=Bu, n_cols=n_cols)
+        L.call("ds_step_rows", C.byref(p), L.current_stream())
+        del keep
+        b.x = out
+        done = []
+        for r, (x0, _, _, _) in zip(reqs, b.lay):
+            r.state = out[x0:x0 + r.B]
+            # (a trajectory entry owns its rows: a view would keep the whole bucket's output alive for as long as the entry lives)
+            r.imgs.append(r.state.clone() if r.prog.return_tensor else r.state.cpu().numpy())
+            r.k += 1
+            if r.k == len(r.prog.steps):
+                done.append(r)
+        for r in done:
+            b.reqs.remove(r)
+            self._retire(r)
+            b.dirty = True

@@ -185,41 +185,56 @@ __global__ void nhwc_to_nchw_kernel(const T* x, int C, int Cs, int HW, float* ou
 
 // ------------------------------------------------------------------------------------------------ sampler step
 // Every operation below is a separately rounded IEEE fp32 op in the reference's order
-// (DiffSynthSampler.py:320,327,337,343,291-293,506): contraction into FMA is switched off.
+// (DiffSynthSampler.py:320,327,337,343,291-293,506): contraction into FMA is switched off.  ddim_step_kernel and step_rows_kernel both
+// call step_element, so a row of ds_step_rows is the same bits as ds_ddim_step given the same inputs.
 #pragma clang fp contract(off)
+// cf: sqrt(1-a_t), sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma; qc: sqrt(acp[t-1]), sqrt(1-acp[t-1]) (blend mode 1 only);
+// m / g / n0: mask, guide and initial noise of the element (blend modes 1 / 2 only)
+__device__ __forceinline__ float step_element(float x, float eps, bool cfg, float eps_c, float cfg_scale, const float (&cf)[5], float noise,
+                                              int blend_mode, float m, float g, float n0, float q0, float q1) {
+    if (cfg) {
+        const float d = eps_c - eps;
+        const float sd = cfg_scale * d;
+        eps = eps + sd;
+    }
+    const float t0 = cf[0] * eps;
+    const float t1 = x - t0;
+    const float x0 = t1 / cf[1];
+    const float u0 = cf[2] * x0;
+    const float u1 = cf[3] * eps;
+    const float u2 = cf[4] * noise;
+    float v = (u0 + u1) + u2;
+    if (blend_mode) {
+        if (blend_mode == 1) {
+            const float g0 = q0 * g;
+            const float g1 = q1 * n0;
+            g = g0 + g1;
+        }
+        const float w0 = m * g;
+        const float w1 = (1.0f - m) * v;
+        v = w0 + w1;
+    }
+    return v;
+}
+
 __global__ __launch_bounds__(256) void ddim_step_kernel(const ds_step_params p, size_t total) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int b = i / p.CHW;
-        const float* cf = p.coef + (size_t)b * 5;
-        float eps = p.eps[i];
-        if (p.eps_cond) {
-            const float d = p.eps_cond[i] - eps;
-            const float sd = p.cfg_scale * d;
-            eps = eps + sd;
-        }
-        const float x = p.x[i];
-        const float t0 = cf[0] * eps;
-        const float t1 = x - t0;
-        const float x0 = t1 / cf[1];
-        const float u0 = cf[2] * x0;
-        const float u1 = cf[3] * eps;
-        const float u2 = cf[4] * p.noise[i];
-        float v = (u0 + u1) + u2;
+        const float cf[5] = {p.coef[(size_t)b * 5], p.coef[(size_t)b * 5 + 1], p.coef[(size_t)b * 5 + 2], p.coef[(size_t)b * 5 + 3],
+                             p.coef[(size_t)b * 5 + 4]};
+        float m = 0.f, g = 0.f, n0 = 0.f, q0 = 0.f, q1 = 0.f;
         if (p.blend_mode) {
             const size_t r = i - (size_t)b * p.CHW;
-            const float m = p.mask_chw ? p.mask[i] : p.mask[(size_t)b * p.HW + r % p.HW];
-            float g = p.guide[i];
+            m = p.mask_chw ? p.mask[i] : p.mask[(size_t)b * p.HW + r % p.HW];
+            g = p.guide[i];
             if (p.blend_mode == 1) {
-                const float* qc = p.qcoef + (size_t)b * 2;
-                const float g0 = qc[0] * g;
-                const float g1 = qc[1] * p.init_noise[i];
-                g = g0 + g1;
+                q0 = p.qcoef[(size_t)b * 2];
+                q1 = p.qcoef[(size_t)b * 2 + 1];
+                n0 = p.init_noise[i];
             }
-            const float w0 = m * g;
-            const float w1 = (1.0f - m) * v;
-            v = w0 + w1;
         }
-        p.out[i] = v;
+        p.out[i] = step_element(p.x[i], p.eps[i], p.eps_cond != nullptr, p.eps_cond ? p.eps_cond[i] : 0.f, p.cfg_scale, cf, p.noise[i],
+                                p.blend_mode, m, g, n0, q0, q1);
     }
 }
 #pragma clang fp contract(fast)
@@ -230,34 +245,150 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
     const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
     c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
 }
+// Philox4x32-10 block of counter `ctr` under key `seed`, Box-Muller'd into four N(0,1) lanes; pair h (lanes 2h, 2h+1) only needs
+// words 2h, 2h+1 of the block, so a caller that wants one lane computes one pair (same bits as the four-lane form)
+__device__ __forceinline__ void philox_block(uint64_t seed, uint64_t ctr, uint32_t (&c)[4]) {
+    c[0] = (uint32_t)ctr; c[1] = (uint32_t)(ctr >> 32); c[2] = 0u; c[3] = 0u;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
+    const float u1 = ((float)(a >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0,1)
+    const float u2 = ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float r = sqrtf(-2.0f * logf(u1));
+    float s, cs;
+    sincospif(2.0f * u2, &s, &cs);
+    z0 = r * cs;
+    z1 = r * s;
+}
+// element e of the stream (seed, offset): lane e % 4 of counter offset + e / 4 — what ds_philox_normal writes at out[e]
+__device__ __forceinline__ float philox_normal_at(uint64_t seed, uint64_t offset, uint64_t e) {
+    uint32_t c[4];
+    philox_block(seed, offset + e / 4, c);
+    const int lane = (int)(e & 3), h = lane >> 1;
+    float z0, z1;
+    box_muller(c[2 * h], c[2 * h + 1], z0, z1);
+    return (lane & 1) ? z1 : z0;
+}
+
 __global__ void philox_normal_kernel(float* out, size_t n, uint64_t seed, uint64_t offset) {
     const size_t nq = (n + 3) / 4;
     for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < nq; q += (size_t)gridDim.x * blockDim.x) {
-        const uint64_t ctr = offset + q;
-        uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-        uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            philox_round(c, k0, k1);
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
+        uint32_t c[4];
+        philox_block(seed, offset + q, c);
         float z[4];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0,1)
-            const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float r = sqrtf(-2.0f * logf(u1));
-            float s, cs;
-            sincospif(2.0f * u2, &s, &cs);
-            z[2 * h] = r * cs;
-            z[2 * h + 1] = r * s;
-        }
+        for (int h = 0; h < 2; ++h) box_muller(c[2 * h], c[2 * h + 1], z[2 * h], z[2 * h + 1]);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (q * 4 + j < n) out[q * 4 + j] = z[j];
     }
 }
+
+// ------------------------------------------------------------------------------------------------ step over rows of many requests
+template <int V>
+__device__ __forceinline__ void load_v(const float* p, bool vec, float (&v)[V]) {
+    if constexpr (V == 4) {
+        if (vec) {
+            const float4 t = *reinterpret_cast<const float4*>(p);
+            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) v[k] = p[k];
+}
+template <int V>
+__device__ __forceinline__ void store_v(float* p, const float (&v)[V]) {
+    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else p[0] = v[0];
+}
+
+#pragma clang fp contract(off)
+// grid (x: pieces of V elements of one row, y: row).  V == 4 only when W % 4 == 0 and x / eps / out are 16-byte aligned: a piece then
+// never crosses an image row, and the row's own guide / initial noise / mask are read in 16-byte pieces when their addresses allow it.
+template <int V>
+__global__ __launch_bounds__(256) void step_rows_kernel(const ds_step_rows_params p) {
+    const int r = blockIdx.y;
+    const int32_t* ir = p.irow + (size_t)r * DS_SR_NI;
+    const float* fr = p.frow + (size_t)r * DS_SR_NF;
+    const uint64_t* pr = p.prow + (size_t)r * DS_SR_NP;
+    const int xr = ir[DS_SR_X], er = ir[DS_SR_EPS], ecr = ir[DS_SR_EPSC], orow = ir[DS_SR_OUT], dup = ir[DS_SR_DUP];
+    const int blend = ir[DS_SR_BLEND], mchw = ir[DS_SR_MASK_CHW], nmode = ir[DS_SR_NOISE];
+    const int smp = ir[DS_SR_SAMPLE], drows = ir[DS_SR_DRAW_ROWS], dw = ir[DS_SR_DRAW_W], coff = ir[DS_SR_COLS];
+    const float* guide = reinterpret_cast<const float*>(pr[DS_SR_GUIDE]);
+    const float* init = reinterpret_cast<const float*>(pr[DS_SR_INIT]);
+    const float* mask = reinterpret_cast<const float*>(pr[DS_SR_MASKP]);
+    const float* draw = reinterpret_cast<const float*>(pr[DS_SR_DRAW]);
+    // the table is the host's.  A row that points outside the declared bounds is never read out of bounds: its output row (and its
+    // duplicate, when that one is in range) is filled with NaN so that a malformed table shows in the result, and a row whose output
+    // row itself is out of range writes nothing
+    const int HW = p.H * p.W;
+    const size_t CHW = (size_t)p.C * HW;
+    if (orow < 0 || orow >= p.Bout) return;
+    const bool bad = xr < 0 || xr >= p.Bx || er < 0 || er >= p.Beps || ecr >= p.Beps || dup >= p.Bout || blend < 0 || blend > 2 ||
+                     nmode < 0 || nmode > 2 || (blend && (!guide || !mask || (blend == 1 && !init))) ||
+                     (nmode && (smp < 0 || smp >= drows || dw <= 0 || coff < 0 || coff > p.n_cols - p.W || (nmode == 1 && !draw)));
+    if (bad) {
+        const float nan = __builtin_nanf("");
+        for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < CHW; i += (size_t)gridDim.x * blockDim.x) {
+            p.out[(size_t)orow * CHW + i] = nan;
+            if (dup >= 0 && dup < p.Bout) p.out[(size_t)dup * CHW + i] = nan;
+        }
+        return;
+    }
+    const float cf[5] = {fr[DS_SR_COEF], fr[DS_SR_COEF + 1], fr[DS_SR_COEF + 2], fr[DS_SR_COEF + 3], fr[DS_SR_COEF + 4]};
+    const float q0 = fr[DS_SR_Q0], q1 = fr[DS_SR_Q1], scale = fr[DS_SR_CFG];
+    const uint64_t seed = pr[DS_SR_SEED], offset = pr[DS_SR_OFFSET];
+    const bool avec = V == 4 && ((((uint64_t)guide | (uint64_t)init | (uint64_t)mask) & 15) == 0);
+    const float* xrow = p.x + (size_t)xr * CHW;
+    const float* erow = p.eps + (size_t)er * CHW;
+    const float* ecrow = ecr >= 0 ? p.eps + (size_t)ecr * CHW : nullptr;
+    float* orow_p = p.out + (size_t)orow * CHW;
+    float* drow_p = dup >= 0 ? p.out + (size_t)dup * CHW : nullptr;
+    const size_t nv = CHW / V;
+    for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < nv; v += (size_t)gridDim.x * blockDim.x) {
+        const size_t i0 = v * V;
+        const int j0 = (int)(i0 % p.W);
+        const size_t ch = i0 / p.W;                                   // c * H + h
+        float xv[V], ev[V], ecv[V], nz[V], mv[V], gv[V], n0[V];
+        load_v<V>(xrow + i0, true, xv);
+        load_v<V>(erow + i0, true, ev);
+        if (ecrow) load_v<V>(ecrow + i0, true, ecv);
+        else
+#pragma unroll
+            for (int k = 0; k < V; ++k) ecv[k] = 0.f;
+#pragma unroll
+        for (int k = 0; k < V; ++k) mv[k] = gv[k] = n0[k] = 0.f;
+        if (blend) {
+            load_v<V>(mask + (mchw ? i0 : i0 % HW), avec, mv);
+            load_v<V>(guide + i0, avec, gv);
+            if (blend == 1) load_v<V>(init + i0, avec, n0);
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            float n = 0.f;
+            if (nmode) {
+                int col = p.cols[coff + j0 + k];
+                col = col < 0 ? 0 : (col >= dw ? dw - 1 : col);
+                const uint64_t e = ((uint64_t)smp * p.C * p.H + ch) * (uint64_t)dw + (uint64_t)col;
+                n = nmode == 1 ? draw[e] : philox_normal_at(seed, offset, e);
+            }
+            nz[k] = n;
+        }
+        float o[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) o[k] = step_element(xv[k], ev[k], ecrow != nullptr, ecv[k], scale, cf, nz[k], blend, mv[k], gv[k], n0[k], q0, q1);
+        store_v<V>(orow_p + i0, o);
+        if (drow_p) store_v<V>(drow_p + i0, o);
+    }
+}
+#pragma clang fp contract(fast)
 
 __global__ void gather_cols_kernel(const float* src, int src_w, const int32_t* cols, int out_w, float* out, size_t total) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -472,6 +603,23 @@ extern "C" int ds_ddim_step(const ds_step_params* p, void* stream) {
     const size_t total = (size_t)p->B * p->CHW;
     hipLaunchKernelGGL(ddim_step_kernel, dim3(blocks_for(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *p, total);
     DS_CHECK_LAUNCH("ddim_step");
+    return DS_OK;
+}
+
+extern "C" int ds_step_rows(const ds_step_rows_params* p, void* stream) {
+    DS_REQUIRE(p && p->x && p->eps && p->out && p->irow && p->frow && p->prow, "step_rows: null pointer");
+    DS_REQUIRE(p->R > 0 && p->R <= 65535 && p->C > 0 && p->H > 0 && p->W > 0, "step_rows: bad sizes (R=%d C=%d H=%d W=%d)", p->R, p->C, p->H, p->W);
+    DS_REQUIRE(p->Bx > 0 && p->Beps > 0 && p->Bout > 0 && p->n_cols >= 0, "step_rows: bad row counts (Bx=%d Beps=%d Bout=%d n_cols=%d)",
+               p->Bx, p->Beps, p->Bout, p->n_cols);
+    DS_REQUIRE(p->n_cols == 0 || p->cols, "step_rows: n_cols > 0 needs cols");
+    const size_t CHW = (size_t)p->C * p->H * p->W;
+    const bool vec = p->W % 4 == 0 && ds_aligned16(p->x) && ds_aligned16(p->eps) && ds_aligned16(p->out);
+    const size_t nv = vec ? CHW / 4 : CHW;
+    const dim3 grid((unsigned)blocks_for(nv, 4096), (unsigned)p->R);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL(step_rows_kernel<4>, grid, dim3(256), 0, st, *p);
+    else hipLaunchKernelGGL(step_rows_kernel<1>, grid, dim3(256), 0, st, *p);
+    DS_CHECK_LAUNCH("step_rows");
     return DS_OK;
 }
 

@@ -149,6 +149,12 @@ def pack_quad_weights(w, transposed, dtype=torch.bfloat16):
     return out.reshape(-1).to(dtype).contiguous(), cp
 
 
+def max_plans():
+    """Plans an engine keeps (least recently used evicted): DS_MAX_PLANS, default 8."""
+    import os
+    return max(1, int(os.environ.get("DS_MAX_PLANS", "8")))
+
+
 class _EngineBase:
     """Shared by the U-Net and the VQGAN-decoder engines: dtype bookkeeping and weight packing."""
 
@@ -165,6 +171,7 @@ class _EngineBase:
         if self.dev.type != "cuda":
             raise RuntimeError("parameters must live on a HIP device ('cuda'); diffusynth_amd has no CPU path")
         self.plans = {}
+        self.plan_builds = 0     # plans built so far (cache misses of _cached_plan)
         self._keep = []          # packed tensors
         self.side_stream = None
         self._tb_total = 0
@@ -184,15 +191,15 @@ class _EngineBase:
     # single-stream and not re-entrant per model instance — two plans share the same bytes.
     def _cached_plan(self, key, make):
         import collections
-        import os
         if not isinstance(self.plans, collections.OrderedDict):
             self.plans = collections.OrderedDict(self.plans)
             self._arena, self._arena_base, self._arena_bytes = None, 0, 0
-            self._max_plans = max(1, int(os.environ.get("DS_MAX_PLANS", "8")))
+            self._max_plans = max_plans()
         plan = self.plans.get(key)
         if plan is not None:
             self.plans.move_to_end(key)
             return plan
+        self.plan_builds += 1
         dry = make()
         dry.build(0)
         peak = dry.arena.peak

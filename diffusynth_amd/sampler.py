@@ -46,6 +46,7 @@ class DiffSynthSampler:
         self.noise_device = noise_device
         self.shard = shard
         self._philox_seed, self._philox_offset = 0, 0
+        self._generator = None      # private torch.Generator for the torch draws (SamplingBatcher); None: torch's global generator
 
     # ------------------------------------------------------------------ schedule (float64 numpy)
     def define_beta_schedule(self):
@@ -101,21 +102,33 @@ class DiffSynthSampler:
         if self.noise_device == "philox":
             # counter-based: element e of the global tensor is lane e % 4 of counter offset + e // 4
             e0, n = (0, shape[0] * row) if world == 1 else (rank * bs * row, bs * row)
-            total = shape[0] * world * row
+            offset = self._philox_take(shape[0] * world * row)
             if e0 % 4 == 0:
                 out = torch.empty((n // row,) + shape[1:], dtype=torch.float32, device=self.device)
-                L.call("ds_philox_normal", out.data_ptr(), out.numel(), self._philox_seed, self._philox_offset + e0 // 4, L.current_stream())
+                L.call("ds_philox_normal", out.data_ptr(), out.numel(), self._philox_seed, offset + e0 // 4, L.current_stream())
             else:                                   # shard boundary inside a counter: draw the global tensor and slice
                 full = torch.empty((shape[0] * world,) + shape[1:], dtype=torch.float32, device=self.device)
-                L.call("ds_philox_normal", full.data_ptr(), full.numel(), self._philox_seed, self._philox_offset, L.current_stream())
+                L.call("ds_philox_normal", full.data_ptr(), full.numel(), self._philox_seed, offset, L.current_stream())
                 out = full[rank * bs:(rank + 1) * bs].contiguous()
-            self._philox_offset += (total + 3) // 4
             return out
         dev = self.device if self.noise_device is None else self.noise_device
         if world == 1:
-            return torch.randn(shape, device=dev).to(self.device)
-        full = torch.randn((shape[0] * world,) + shape[1:], device=dev)
+            return torch.randn(shape, device=dev, generator=self._generator).to(self.device)
+        full = torch.randn((shape[0] * world,) + shape[1:], device=dev, generator=self._generator)
         return full[rank * bs:(rank + 1) * bs].to(self.device)
+
+    def _philox_take(self, n):
+        """Reserve the Philox counters of an n-element draw: returns the draw's counter offset and advances the sampler's."""
+        offset = self._philox_offset
+        self._philox_offset += (int(n) + 3) // 4
+        return offset
+
+    def _step_noise_layout(self, width):
+        """(draw width, source columns) of the per-step noise of a ``width`` latent: the draw is ``(max_batchsize, C, H, draw width)``
+        and column j of the noise is column cols[j] of the draw (get_deterministic_noise_tensor's two layouts)."""
+        if self.noise_strategy == "repeat":
+            return self.train_width, self._repeat_plan(width)[0]
+        return self.max_width, list(range(width))
 
     def _repeat_plan(self, width):
         """Source columns of the repeat layout and its concat points (DSS:116-167)."""
@@ -312,6 +325,16 @@ class DiffSynthSampler:
     def p_sample_loop(self, model, shape, initial_noise=None, start_noise_level_ratio=1.0, end_noise_level_ratio=0.0,
                       return_tensor=False, condition=None, guide_img=None,
                       mask=None, sampler="ddim", inpaint=False, use_dynamic_mask=False, mask_flexivity=0.8):
+        prog = self._loop_prologue(shape, initial_noise, start_noise_level_ratio, end_noise_level_ratio, return_tensor, condition,
+                                   guide_img, mask, sampler, inpaint, use_dynamic_mask, mask_flexivity)
+        if model is LOOP_PROGRAM:           # (SamplingBatcher: the call's program; the batcher runs the steps)
+            return prog
+        return self._loop(model, prog)
+
+    def _loop_prologue(self, shape, initial_noise, start_noise_level_ratio, end_noise_level_ratio, return_tensor, condition, guide_img,
+                       mask, sampler, inpaint, use_dynamic_mask, mask_flexivity):
+        """Everything of p_sample_loop in front of the first model call (DSS:449-498): initial noise, guide gather, q_sample at start - 1,
+        the masks, the step list and the per-step scalar tables.  Returns a LoopProgram."""
         assert shape[1] == self.channels, "shape[1] != self.channels"
         assert shape[2] == self.height, "shape[2] != self.height"
         if sampler not in ("ddim", "ddpm"):
@@ -340,41 +363,54 @@ class DiffSynthSampler:
         masks = (self.get_dynamic_masks(n_masks, shape, concat_points, mask_flexivity) if use_dynamic_mask
                  else [mask for _ in range(n_masks)])
         steps = list(reversed(range(end, start)))
+        prog = LoopProgram(shape=tuple(shape), eta=eta, steps=steps, n_total=start - end, img=img, initial_noise=initial_noise,
+                           condition=condition, return_tensor=return_tensor, inpaint=inpaint)
         # per-step scalar tables hoisted out of the loop (the reference rebuilds them with 2 H2D copies per step)
-        coef_all = q_all = None
         if steps:
             tt = torch.tensor(steps, dtype=torch.long)
-            coef_all = self._step_coefficients(tt, eta).to(self.device)            # [T][5]
+            prog.coef_cpu = self._step_coefficients(tt, eta)                        # [T][5]
+            prog.coef_all = prog.coef_cpu.to(self.device)
             if inpaint:
                 tq = torch.clamp(tt - 1, min=0)
-                q_all = torch.stack([torch.from_numpy(self.sqrt_alphas_cumprod)[tq].float(),
-                                     torch.from_numpy(self.sqrt_one_minus_alphas_cumprod)[tq].float()], dim=1).to(self.device)
+                prog.q_cpu = torch.stack([torch.from_numpy(self.sqrt_alphas_cumprod)[tq].float(),
+                                          torch.from_numpy(self.sqrt_one_minus_alphas_cumprod)[tq].float()], dim=1)
+                prog.q_all = prog.q_cpu.to(self.device)
         if inpaint:
-            guide_dev = guide_img.contiguous().float()
-            init_dev = initial_noise.contiguous().float()
-        imgs = [img]
-        current_mask = None
-        for k, i in enumerate(tqdm(steps, total=start - end, disable=self.mute)):
-            t = torch.full((B,), i, device=self.device, dtype=torch.long)
-            blend = None
-            if inpaint:
+            prog.guide = guide_img.contiguous().float()
+            prog.init = initial_noise.contiguous().float()
+            # per step: blend mode and the mask as the step kernel reads it.  Any mask the reference's broadcasting accepts (DSS:506):
+            # (B,1,H,W) stays a one-channel plane, everything else (e.g. the (B,C,H,W) masks of inpaint_with_text.py:229-231) is expanded
+            # to the latent's shape — once per distinct mask
+            current_mask, planes = None, {}
+            for i in steps:
                 if i > 0:
                     current_mask = masks.pop()
                     mode = 1
                 else:
                     mode = 2
-                # any mask the reference's broadcasting accepts (DSS:506): (B,1,H,W) stays a one-channel plane, everything
-                # else (e.g. the (B,C,H,W) masks of inpaint_with_text.py:229-231) is expanded to the latent's shape
-                m = current_mask.to(self.device).float()
-                if m.dim() == 4 and m.shape[1] == 1:
-                    m = m.expand(B, 1, shape[2], shape[3]).contiguous()
-                else:
-                    m = m.expand(*shape).contiguous()
-                blend = (mode, guide_dev, init_dev, m, q_all[k:k + 1].expand(B, 2).contiguous())
-            img = self.ddim_sample(model, img, t, condition=condition, ddim_eta=eta,
-                                   _coef=coef_all[k:k + 1].expand(B, 5).contiguous(), _blend=blend)
-            imgs.append(img if return_tensor else img.cpu().numpy())
-        return imgs, initial_noise
+                if id(current_mask) not in planes:              # (the source is kept in the entry: its id stays unique)
+                    m = current_mask.to(self.device).float()
+                    if m.dim() == 4 and m.shape[1] == 1:
+                        m = m.expand(B, 1, shape[2], shape[3]).contiguous()
+                    else:
+                        m = m.expand(*shape).contiguous()
+                    planes[id(current_mask)] = (current_mask, m)
+                prog.blends.append((mode, planes[id(current_mask)][1]))
+        return prog
+
+    def _loop(self, model, prog):
+        B, img = prog.shape[0], prog.img
+        imgs = [img]
+        for k, i in enumerate(tqdm(prog.steps, total=prog.n_total, disable=self.mute)):
+            t = torch.full((B,), i, device=self.device, dtype=torch.long)
+            blend = None
+            if prog.inpaint:
+                mode, m = prog.blends[k]
+                blend = (mode, prog.guide, prog.init, m, prog.q_all[k:k + 1].expand(B, 2).contiguous())
+            img = self.ddim_sample(model, img, t, condition=prog.condition, ddim_eta=prog.eta,
+                                   _coef=prog.coef_all[k:k + 1].expand(B, 5).contiguous(), _blend=blend)
+            imgs.append(img if prog.return_tensor else img.cpu().numpy())
+        return imgs, prog.initial_noise
 
     def sample(self, model, shape, return_tensor=False, condition=None, sampler="ddim", initial_noise=None, seed=None):
         self._seed(seed)
@@ -407,5 +443,30 @@ class DiffSynthSampler:
 
     def _seed(self, seed):
         if seed is not None:
-            torch.manual_seed(seed)
+            if self._generator is not None:
+                self._generator.manual_seed(seed)
+            else:
+                torch.manual_seed(seed)
             self._philox_seed, self._philox_offset = int(seed), 0
+
+
+class _LoopProgramRequest:
+    """Passed as ``model`` to an entry point (sample, img_guided_sample, inpaint_sample, interpolate), it stops the call after
+    p_sample_loop's prologue: the call returns its LoopProgram (diffusynth_amd.batching runs the steps)."""
+
+    def __repr__(self):
+        return "LOOP_PROGRAM"
+
+
+LOOP_PROGRAM = _LoopProgramRequest()
+
+
+class LoopProgram:
+    """What p_sample_loop's prologue derives for one call: the steps (timestep indices, descending), their coefficient rows
+    (``coef_cpu`` [T][5], ``q_cpu`` [T][2] for inpainting; ``coef_all`` / ``q_all`` on the device), and for inpainting the guide, the
+    initial noise and per step ``blends[k] = (mode, mask)``; ``img`` is the state before the first step."""
+
+    def __init__(self, **kw):
+        self.coef_cpu = self.coef_all = self.q_cpu = self.q_all = self.guide = self.init = None
+        self.blends = []
+        self.__dict__.update(kw)

@@ -406,6 +406,55 @@ typedef struct {
                                     inpaint UI passes a per-channel mask: inpaint_with_text.py:229-231)    */
 } ds_step_params;
 int ds_ddim_step(const ds_step_params* p, void* stream);
+/* One sampler step over R rows that belong to different requests (diffusynth_amd/batching.py: concurrent sampler calls sharing one
+ * U-Net batch).  Row r reads its state from x[irow[r][DS_SR_X]], its eps (the unconditional half under CFG) from eps[irow[r][DS_SR_EPS]]
+ * and, when irow[r][DS_SR_EPSC] >= 0, the conditional eps from that row of eps; it writes the new state to out[irow[r][DS_SR_OUT]] and,
+ * when irow[r][DS_SR_DUP] >= 0, a second copy to that row (the classifier-free-guidance duplicate of the next U-Net input).  Rows are
+ * C*H*W fp32 each.  The arithmetic is ds_ddim_step's (same device function, no FMA contraction), with the row's own CFG scale,
+ * coefficients (frow: coef[5] as ds_step_params.coef, qcoef[2], cfg scale), blend mode and mask layout.
+ * Step noise (irow[r][DS_SR_NOISE]): 0 none (sigma == 0), 1 read from a raw draw, 2 computed in the kernel.  For element (c, h, j) of
+ * the row, the source index into its request's draw of shape (draw_rows, C, H, draw_w) is
+ *     e = ((sample * C + c) * H + h) * draw_w + cols[cols_off + j]
+ * mode 1 reads draw[e] (prow DS_SR_DRAW), mode 2 computes lane e % 4 of Philox counter offset + e / 4 under key seed (prow DS_SR_SEED /
+ * DS_SR_OFFSET): what ds_philox_normal followed by ds_gather_cols gives.  prow DS_SR_GUIDE / DS_SR_INIT / DS_SR_MASKP address the row's
+ * own guide, initial noise and mask (mask: H*W floats, or C*H*W when irow DS_SR_MASK_CHW != 0); with W % 4 == 0 they are read in
+ * 16-byte pieces when 16-byte aligned.  The tables are device arrays, row-major [R][DS_SR_NI] int32, [R][DS_SR_NF] float,
+ * [R][DS_SR_NP] uint64; Bx / Beps / Bout are the row counts of x / eps / out and n_cols the length of cols.  A row whose entries fall
+ * outside those bounds (or name an unknown mode, or lack a pointer its modes need) reads nothing: its output row, and its duplicate
+ * when that is in range, is filled with NaN; a row whose output row is out of range writes nothing. */
+#define DS_SR_X 0
+#define DS_SR_EPS 1
+#define DS_SR_EPSC 2
+#define DS_SR_OUT 3
+#define DS_SR_DUP 4
+#define DS_SR_BLEND 5
+#define DS_SR_MASK_CHW 6
+#define DS_SR_NOISE 7
+#define DS_SR_SAMPLE 8
+#define DS_SR_DRAW_ROWS 9
+#define DS_SR_DRAW_W 10
+#define DS_SR_COLS 11
+#define DS_SR_NI 12
+#define DS_SR_COEF 0                   /* frow: coef[5] at 0..4 */
+#define DS_SR_Q0 5
+#define DS_SR_Q1 6
+#define DS_SR_CFG 7
+#define DS_SR_NF 8
+#define DS_SR_GUIDE 0                  /* prow */
+#define DS_SR_INIT 1
+#define DS_SR_MASKP 2
+#define DS_SR_DRAW 3
+#define DS_SR_SEED 4
+#define DS_SR_OFFSET 5
+#define DS_SR_NP 6
+typedef struct {
+    const float* x; const float* eps; float* out;
+    const int32_t* irow; const float* frow; const uint64_t* prow;
+    const int32_t* cols;
+    int32_t R, C, H, W;
+    int32_t Bx, Beps, Bout, n_cols;
+} ds_step_rows_params;
+int ds_step_rows(const ds_step_rows_params* p, void* stream);
 /* counter-based N(0,1) generator (Philox4x32-10 + Box-Muller) for the throughput mode */
 int ds_philox_normal(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 /* column gather of the "repeat" noise layout (DiffSynthSampler.py:97-167): out[b][c][h][j] = src[b][c][h][cols[j]] */
