@@ -50,6 +50,7 @@ with open(_HEADER) as _f:
     _HEADER_TEXT = _f.read()
 _STRUCTS = _parse_structs(_HEADER_TEXT)
 SR = _parse_defines(_HEADER_TEXT, "DS_SR_")     # ds_step_rows table layout (field indices and row widths)
+DW_FAMILY = {v: k[6:].lower() for k, v in _parse_defines(_HEADER_TEXT, "DS_DW_").items()}     # ds_dwconv_launch_choice: family code -> name
 ConvParams = _STRUCTS["ds_conv_params"]
 PackConvParams = _STRUCTS["ds_pack_conv_params"]
 DwconvParams = _STRUCTS["ds_dwconv_params"]
@@ -76,6 +77,7 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_conv_fold_tables": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "ds_dwconv7": (C.c_int, [C.POINTER(DwconvParams), _P]),
     "ds_dwconv_stats_parts": (C.c_int, [C.POINTER(DwconvParams)]),
+    "ds_dwconv_launch_choice": (C.c_int, [C.POINTER(DwconvParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ds_pack_dw_weight": (C.c_int, [_P, _I, _P, _P]),
     "ds_pack_dw_weight_mfma": (C.c_int, [_P, _I, _P, _P]),
     "ds_split_planes": (C.c_int, [_P, _P, C.c_longlong, _I, _P]),
@@ -91,6 +93,7 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_attn_fused_context": (C.c_int, [C.POINTER(AttnFusedParams), _P]),
     "ds_attn_fused_output": (C.c_int, [C.POINTER(AttnFusedParams), _P]),
     "ds_attn_fused_stats_parts": (C.c_int, [C.POINTER(AttnFusedParams)]),
+    "ds_attn_fused_generations": (C.c_int, [C.POINTER(AttnFusedParams)]),
     "ds_attn_fused_segments": (C.c_int, [_I, _I, _I]),
     "ds_attn_fused_segments_gen": (C.c_int, [_I, _I, _I, _I]),
     "ds_pack_attn_x3": (C.c_int, [_P, _P, _P, _I, _P]),
@@ -144,7 +147,7 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_stft_plus": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "ds_bounds_report": (C.c_int, [C.c_char_p, _I, _I]),
 }
-_UNCHECKED = {"ds_conv3x3_f32_n4_weight_floats", "ds_bounds_report", "ds_abi_version", "ds_conv_stats_parts", "ds_conv1x1_x3_stats_parts", "ds_conv_tile_bn", "ds_dwconv_stats_parts", "ds_attn_fused_stats_parts", "ds_attn_fused_segments", "ds_attn_fused_segments_gen", "ds_attn_x3_stats_parts", "ds_attn_x3_segments", "ds_vq_attn_segments", "ds_conv3x3_c80_stats_slots", "ds_convt4x4_c80_stats_slots"}
+_UNCHECKED = {"ds_conv3x3_f32_n4_weight_floats", "ds_bounds_report", "ds_abi_version", "ds_conv_stats_parts", "ds_conv1x1_x3_stats_parts", "ds_conv_tile_bn", "ds_dwconv_stats_parts", "ds_attn_fused_stats_parts", "ds_attn_fused_generations", "ds_attn_fused_segments", "ds_attn_fused_segments_gen", "ds_attn_x3_stats_parts", "ds_attn_x3_segments", "ds_vq_attn_segments", "ds_conv3x3_c80_stats_slots", "ds_convt4x4_c80_stats_slots"}
 EXPORTS = sorted(list(_PROTOS) + ["ds_last_error_string"])
 
 _lib = None

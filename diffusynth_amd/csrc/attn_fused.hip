@@ -536,6 +536,8 @@ extern "C" int ds_attn_fused_segments_gen(int B, int N, int C, int gen) {
 
 extern "C" int ds_attn_fused_segments(int B, int N, int C) { return ds_attn_fused_segments_gen(B, N, C, 0); }
 
+extern "C" int ds_attn_fused_generations(const ds_attn_fused_params* p) { return (use_ctx2(p) ? 1 : 0) | (use_out2(p) ? 2 : 0); }
+
 extern "C" int ds_attn_fused_stats_parts(const ds_attn_fused_params* p) {
     if (use_out2(p)) return attn_out2_blocks(p->N, p->B, p->C);
     const int tp = 32 * group_t(p->C, p->N);

@@ -781,6 +781,10 @@ __global__ __launch_bounds__(NW * 64, 1) void dwconv7_mfma2_kernel(const ds_dwco
     tile_body(nt - 1, std::false_type{});
 }
 
+// The batch the batch-dependent choices below look at: ds_dwconv_params.batch_hint where the caller gives one (the shared prefix of a paired
+// plan runs at half the batch and must group its GroupNorm partials as the plain plan does at the full batch), else B.
+static int dw_batch(const ds_dwconv_params* p) { return p->batch_hint > 0 ? p->batch_hint : p->B; }
+
 static bool dw_tall(const ds_dwconv_params* p) { return p->W <= 16; }
 static Dw2Geo dw2_geo(const ds_dwconv_params* p) {
     const int tw = dw_tall(p) ? 16 : 32, th = dw_tall(p) ? 32 : 16;
@@ -793,7 +797,7 @@ static Dw2Geo dw2_geo(const ds_dwconv_params* p) {
     // The longest such chunk (<= 8 items) that still leaves two chunks per CU: small batches get short chunks (parallelism before amortisation)
     g.tpc = 1;
     for (int d = 2; d <= 8; ++d)
-        if ((g.tiles % d == 0 || (d % g.tiles == 0 && p->B % (d / g.tiles) == 0)) && (long long)p->B * g.tiles / d * g.ncblk >= 512) g.tpc = d;
+        if ((g.tiles % d == 0 || (d % g.tiles == 0 && p->B % (d / g.tiles) == 0)) && (long long)dw_batch(p) * g.tiles / d * g.ncblk >= 512) g.tpc = d;
     g.nchunk = p->B * g.tiles / g.tpc;                        // chunks per channel block
     g.total = g.nchunk * g.ncblk;
     return g;
@@ -1180,7 +1184,7 @@ static DwStrip dw_strip(const ds_dwconv_params* p) {
         return g;
     g.strips_w = (p->W + ST_W - 1) / ST_W;
     g.ncblk = (p->C0 + p->C1) / 32;
-    const long n0 = (long)p->B * g.ncblk * g.strips_w;
+    const long n0 = (long)dw_batch(p) * g.ncblk * g.strips_w;
     while (n0 * g.hparts < 2 * ST_MIN_ITEMS && p->H / (2 * g.hparts) >= 2 * ST_R) g.hparts *= 2;
     if (n0 * g.hparts < ST_MIN_ITEMS && !forced) return g;
     g.rows_per_part = ((p->H + g.hparts - 1) / g.hparts + ST_R - 1) / ST_R * ST_R;
@@ -1204,6 +1208,23 @@ extern "C" int ds_dwconv_stats_parts(const ds_dwconv_params* p) {
     return (int)((total + DW_BLOCK - 1) / DW_BLOCK);
 }
 
+extern "C" int ds_dwconv_launch_choice(const ds_dwconv_params* p, int32_t* family, int32_t* ranges, int32_t* samples_per_chunk) {
+    DS_REQUIRE(p && family && ranges && samples_per_chunk, "dwconv_launch_choice: null pointer");
+    *ranges = *samples_per_chunk = 1;
+    if (dw_use_mfma(p)) {
+        const Dw2Geo g = dw2_geo(p);
+        *family = DS_DW_MFMA;
+        *ranges = g.tiles >= g.tpc ? g.tiles / g.tpc : 1;
+        *samples_per_chunk = g.tpc > g.tiles ? g.tpc / g.tiles : 1;
+    } else if (const DwStrip g = dw_strip(p); g.on) {
+        *family = DS_DW_STRIP;
+        *ranges = g.hparts;
+    } else {
+        *family = dw_use_lds(p) ? DS_DW_TILE : DS_DW_DIRECT;
+    }
+    return DS_OK;
+}
+
 extern "C" int ds_dwconv7(const ds_dwconv_params* p, void* stream) {
     DS_REQUIRE(p && p->src0 && p->wt && p->bias && p->out, "dwconv7: null pointer");
     DS_REQUIRE(p->dtype == DS_F32 || p->dtype == DS_BF16, "dwconv7: dtype %d", p->dtype);
@@ -1212,6 +1233,7 @@ extern "C" int ds_dwconv7(const ds_dwconv_params* p, void* stream) {
     DS_REQUIRE(p->C0 > 0 && p->C0 % V == 0 && p->C1 % V == 0, "dwconv7: channels (%d,%d) must be multiples of %d", p->C0, p->C1, V);
     DS_REQUIRE(p->C1 == 0 || (p->src1 && p->H1 > 0 && p->W1 > 0), "dwconv7: second source incomplete");
     DS_REQUIRE(p->B > 0 && p->H > 0 && p->W > 0, "dwconv7: empty problem");
+    DS_REQUIRE(p->batch_hint >= 0, "dwconv7: batch_hint must be 0 (use B) or the batch the launch decisions look at, got %d", p->batch_hint);
     DS_REQUIRE(p->strip >= 0 && p->strip <= 2, "dwconv7: strip must be 0 (library's choice), 1 (strip kernel) or 2 (tile kernel), got %d", p->strip);
     DS_REQUIRE(!p->out_split || (p->dtype == DS_F32 && dw_use_lds(p)), "dwconv7: out_split needs the fp32 LDS-tile kernel (channels multiples of %d, samples below 2 GB)", 16);
     if (!ds_aligned16(p->src0) || !ds_aligned16(p->out) || !ds_aligned16(p->wt) || (p->C1 && !ds_aligned16(p->src1)))

@@ -489,6 +489,47 @@ class _PlanBuilder:
     def op(self, name, *args):
         self.ops.append((getattr(self.lib, name), args, name))
 
+    # ---------------------------------------------------------------- inspection
+    def launch_signature(self):
+        """What the recorded launches DECIDED, for tests that ask which batches take the same code paths: (categorical, counts).
+        categorical: one tuple per op, never addresses or sizes that merely scale with the batch —
+          convolutions: (name, tile, K slices, flags, res_steps, two samples per block [the halo kernel's pair predicate, restated]);
+          ds_dwconv7: (name, kernel family, row ranges / chunks per image, a chunk covers several samples) from ds_dwconv_launch_choice;
+          attention: (name, generations of the two passes [ds_attn_fused_generations; 0 elsewhere]) on the context op;
+          anything else: (name,).
+        counts: per attention block (segments of the context pass, GroupNorm partials per sample of the output pass) in op order — budgets
+        divided by the batch, kept apart because they change at almost every batch.  Read-only; works on a dry build."""
+        cat, counts = [], []
+        lib = self.lib
+        for item in self.ops:
+            if isinstance(item[0], str):                       # ops run() binds per call: sinusoid, cond_embed, labels, input, output
+                cat.append((item[0],))
+                continue
+            _, args, name = item
+            p = args[0] if args else None
+            if name in ("ds_conv_igemm", "ds_conv1x1_x3"):
+                ks = max(1, p.ksplit)
+                # conv3x3_halo3.hip, ds_conv_igemm's halo3 dispatch: the 8 x 32 tile holds two images of at most 16 x 8
+                pair = bool(name == "ds_conv_igemm" and p.tile == L.TILE_HALO3_256x96 and p.flags != 0 and p.W <= 8 and 2 * p.H <= 32
+                            and ks == 1 and not p.res_steps and p.B >= 2)
+                cat.append((name, p.tile, ks, p.flags, p.res_steps, pair))
+            elif name == "ds_dwconv7":
+                fam, ranges, spc = C.c_int32(), C.c_int32(), C.c_int32()
+                L.call("ds_dwconv_launch_choice", C.byref(p), C.byref(fam), C.byref(ranges), C.byref(spc))
+                cat.append((name, L.DW_FAMILY[fam.value], ranges.value, spc.value > 1))
+            elif name == "ds_attn_fused_context":
+                counts.append((p.nseg, lib.ds_attn_fused_stats_parts(C.byref(p))))
+                cat.append((name, lib.ds_attn_fused_generations(C.byref(p))))
+            elif name == "ds_attn_x3_context":
+                counts.append((p.nseg, lib.ds_attn_x3_stats_parts(C.byref(p))))
+                cat.append((name, 0))
+            elif name == "ds_linattn_context":
+                counts.append((p.nseg, 0))
+                cat.append((name, 0))
+            else:
+                cat.append((name,))
+        return tuple(cat), tuple(counts)
+
     # ---------------------------------------------------------------- kernels
     def _halo3_ksplit(self, cw, x, split):
         """Split-K factor of a 3x3 halo launch over x (split: split precision), from the plan's FULL batch (self.Btile)."""
@@ -677,7 +718,8 @@ class _PlanBuilder:
                            wt=d["dw"].data_ptr(), bias=d["dw_bias"].data_ptr(),
                            tbias=(self.tb_all[0] + 4 * d["tb_off"]) if (d["tb_off"] is not None and self.tb_all) else None,
                            tb_stride=e._tb_total, out=h.off, stats_part=None, B=B, dtype=e.dt,
-                           wexp=(d["dw_exp"].data_ptr() if d.get("dw_exp") is not None else None))
+                           wexp=(d["dw_exp"].data_ptr() if d.get("dw_exp") is not None else None),
+                           batch_hint=self.Btile)      # (kernel family and row ranges / chunks per image: by the FULL batch, like split-K)
         # split-precision tier: the two tensors only 3x3 convolutions read (h, g) are stored as hi / lo bf16 planes
         sp = (self._split_takes(d["conv1"]) and self._split_takes(d["conv2"]) and s0.C % 16 == 0 and (s1 is None or s1.C % 16 == 0))
         if sp:
@@ -941,7 +983,10 @@ class _PlanBuilder:
         # classifier-free guidance evaluates cat([x, x]) with cat([uncond, cond]): the two halves are the same computation until the first
         # attention block adds the label query — the init convolution and the first block run ONCE, at half the batch, and their two results
         # (the skip tensor and the block output with its GroupNorm partials) are duplicated (ds_dup_batch).  Bit-identical to the plain plan:
-        # the split-K decisions of these layers are taken from the full batch (self.Btile), everything else depends on the layer shape only.
+        # every decision of these layers that looks at the batch is taken from the full batch (self.Btile) — the split-K factors, and the
+        # depthwise launch's kernel family and row ranges / chunks per image (ds_dwconv_params.batch_hint) — so the prefix groups its partial
+        # sums as the plain plan does; everything else depends on the layer shape only (tests/test_hip_batch_ladder.py compares the two
+        # plans' launch_signature() at every even batch up to 256 and their output bits on a ladder of batches).
         Bfull = self.B
         half = self.paired and len(P["downs"]) > 0
         if half:

@@ -183,9 +183,23 @@ typedef struct {
                                     down a 16-column strip: every input row leaves HBM once) by shape and batch, 1 = the strip kernel wherever its shape
                                     conditions hold (W >= 16, H >= 32), 2 = never.  Outputs are identical bit for bit; the statistics partials are
                                     grouped differently (ds_dwconv_stats_parts answers for the same setting) */
+    int32_t batch_hint;          /* 0 = B.  The batch every batch-dependent launch decision looks at instead of B (tile or strip kernel and the row
+                                    ranges per image of the fp32 kernels, the chunk length of the bf16 matrix-core kernel): the shared prefix of a
+                                    paired classifier-free-guidance plan runs at half the batch and passes the FULL batch here, so that its GroupNorm
+                                    partials are grouped - and therefore rounded - exactly as the plain plan's.  Only a chunk of several whole
+                                    samples (bf16, images of fewer than 8 tiles) still has to divide B itself; that does not change the grouping */
 } ds_dwconv_params;
 int ds_dwconv7(const ds_dwconv_params* p, void* stream);
 int ds_dwconv_stats_parts(const ds_dwconv_params* p);
+/* What ds_dwconv7 would launch for p, for plan inspection (no launch, pointers are not read except for NULL tests):
+ * *family = DS_DW_DIRECT / DS_DW_TILE / DS_DW_STRIP / DS_DW_MFMA; *ranges = GroupNorm partials per image and channel block that follow from a
+ * batch-dependent choice (strip kernel: row ranges per image, `hparts`; matrix-core kernel: chunks per image; else 1); *samples_per_chunk =
+ * whole samples one chunk of the matrix-core kernel covers (1 elsewhere).  Returns DS_OK. */
+#define DS_DW_DIRECT 0
+#define DS_DW_TILE 1
+#define DS_DW_STRIP 2
+#define DS_DW_MFMA 3
+int ds_dwconv_launch_choice(const ds_dwconv_params* p, int32_t* family, int32_t* ranges, int32_t* samples_per_chunk);
 int ds_pack_dw_weight(const float* w_c1kk, int C, float* dst_tap_major, void* stream);
 /* [C][1][7][7] fp32 -> [C][6 k-steps][64 lanes][8] bf16 B-operand fragments of v_mfma_f32_16x16x32_bf16 */
 int ds_pack_dw_weight_mfma(const float* w_c1kk, int C, void* dst_bf16, void* stream);
@@ -276,6 +290,9 @@ int ds_attn_fused_segments(int B, int N, int C);
 /* the same for an explicit kernel generation (ds_attn_fused_params.gen = 1 / 2; 0 = by batch, as above): a caller that forces a generation
  * sizes `part` from THIS count */
 int ds_attn_fused_segments_gen(int B, int N, int C, int gen);
+/* which generation the two passes would run for p, for plan inspection (no launch): bit 0 = the context pass runs the second generation,
+ * bit 1 = the output pass does */
+int ds_attn_fused_generations(const ds_attn_fused_params* p);
 
 /* ---------------------------------------------------------------- fused LinearAttention of the VQGAN (bf16 tier; csrc/vq_attn.hip)
  * VQGAN.py:246-272 (heads = 1, dim_head = 32, softmax over n on k only): q enters linearly, so after the context the block is one 1x1

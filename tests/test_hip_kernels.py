@@ -772,7 +772,8 @@ def test_conv_quad_halo3_split_precision(mode="up"):
     import ctypes as C
     from diffusynth_amd.engine import pack_quad_weights
     h = H()
-    for mode, cin, cout, (Hh, Ww) in (("up", 192, 96, (9, 27)), ("down", 96, 192, (18, 54)), ("up", 384, 96, (32, 8))):
+    # (the last case: the deepest Downsample, whose 144 chunks the plans cut into up to 8 slices at small batches)
+    for mode, cin, cout, (Hh, Ww) in (("up", 192, 96, (9, 27)), ("down", 96, 192, (18, 54)), ("up", 384, 96, (32, 8)), ("down", 384, 384, (32, 16))):
         tr = mode == "up"
         B = 2
         x = synth_input("k_qs_x%s%d" % (mode, cin), (B, cin, Hh, Ww)) * 1.5 + 0.3
@@ -815,7 +816,10 @@ def test_conv_quad_halo3_split_precision(mode="up"):
 @pytest.mark.parametrize("out_mode", ["split", "f32", "f32+res"])
 @pytest.mark.parametrize("shape,cout", [((2, 96, 8, 64), 192), ((1, 64, 37, 16), 96), ((2, 32, 33, 8), 96), ((1, 96, 9, 27), 96),
                                         # r05, two samples per block (images of at most 16 x 8, batch >= 2): an odd batch leaves the last block half empty
-                                        ((3, 96, 16, 8), 192), ((2, 64, 12, 7), 96), ((5, 32, 16, 5), 96)])
+                                        ((3, 96, 16, 8), 192), ((2, 64, 12, 7), 96), ((5, 32, 16, 5), 96),
+                                        # the deepest level's production factors (tests/test_hip_batch_ladder.py: the plans of the batches 1 .. 256):
+                                        # 768 channels = 24 chunks in 8 slices of three (the loop's odd-count peel), 192 channels in 6 slices of one
+                                        ((2, 768, 32, 8), 384), ((2, 192, 16, 16), 96)])
 def test_conv3x3_halo3_split_precision(shape, cout, out_mode):
     """Split-precision 3x3 (DS_CONV_F_*): fp32 tensors on bf16 matrix cores as x_hi w_hi + x_lo w_hi + x_hi w_lo.  Input as hi / lo
     bf16 planes, GroupNorm fold, exact GELU; output as hi / lo planes or as fp32 (+ fp32 residual).  Against F.conv2d in float64
@@ -859,7 +863,7 @@ def test_conv3x3_halo3_split_precision(shape, cout, out_mode):
                      ncls=9, act=L.ACT_GELU if gelu else L.ACT_NONE, res=L.ptr(rd), stats_part=None, B=B, dtype=L.DS_BF16,
                      tile=L.TILE_HALO3_256x96, wk_order=1, flags=flags)
     # whole-K launch, then (r04) the same layer as K slices + ds_conv_splitk_reduce: what the engine runs at small batches
-    for ks in (1, 2, 3, 4, 6):
+    for ks in (1, 2, 3, 4, 6, 8):
         if ks > 1 and (Cin // 32) % ks != 0:          # K slices = whole source chunks
             continue
         out.fill_(float("nan"))
@@ -971,8 +975,20 @@ def test_conv7x7_c4_x3_matches_torch(hw, cin):
 
 
 # ----------------------------------------------------------------------------------------- fused attention block
+def _ladder_nseg(tier, Cc, N):
+    """Segment counts the plans of the batches 1 .. 256 take at this channel count (NSEG_ON_LADDER of tests/test_hip_batch_ladder.py, whose
+    census fails when a count is met that is not recorded there), with the split-precision tier's floor and cap, 8 and 128 — swept on
+    images of at least 4096 pixels, where all of them are legal (at most one segment per 32-pixel tile)."""
+    from test_hip_batch_ladder import NSEG_ON_LADDER
+    if N < 4096:
+        return ()
+    return tuple(n for n in sorted({8, 128} | set(NSEG_ON_LADDER[tier][Cc])) if n <= (N + 31) // 32)
+
+
 @pytest.mark.parametrize("Cc,hw,cond", [(96, (16, 16), True), (96, (5, 10), False), (192, (33, 32), True), (384, (8, 6), True),
-                                        (96, (193, 257), True), (192, (257, 259), False), (384, (32, 33), True)])
+                                        (96, (193, 257), True), (192, (257, 259), False), (384, (32, 33), True),
+                                        # 4096 pixels = 128 tiles: the segment counts production takes (_ladder_nseg), both generations
+                                        (96, (64, 64), True), (192, (64, 64), False), (384, (64, 64), True)])
 def test_fused_attention_block_matches_oracle(Cc, hw, cond):
     """ds_attn_fused_context/_output + gn_finalize + gn_apply == Residual(PreNorm(LinearCrossAttentionAdd)) of the oracle
     (bf16 tier; N ragged against the 32-pixel tiles and the segments).  The two large cases give every wave of the second-generation
@@ -1007,7 +1023,9 @@ def test_fused_attention_block_matches_oracle(Cc, hw, cond):
     lq = None
     if cond:
         lq = dev(F.linear(c, sd[tag + ".fn.fn.label_query.weight"], sd[tag + ".fn.fn.label_query.bias"]))
-    for nseg, v2 in ((1, False), (3, False), (3, True)):       # v2: second-generation output pass (to_out folded into the context)
+    sweep = [(1, False), (3, False), (3, True)]                # v2: second-generation kernels (output pass: to_out folded into the context)
+    sweep += [(n, v2) for n in _ladder_nseg("bf16", Cc, N) for v2 in (False, True)]
+    for nseg, v2 in sweep:
         ab = h.gn_ab_of(xq)
         part = torch.empty(L.load().ds_linattn_part_floats(B, 4, nseg), device="cuda")
         ctx = torch.empty(B * 4 * 1024, device="cuda")
@@ -1037,7 +1055,9 @@ def test_fused_attention_block_matches_oracle(Cc, hw, cond):
 
 
 @pytest.mark.parametrize("Cc,hw,cond", [(96, (16, 16), True), (96, (5, 10), False), (192, (33, 32), True), (384, (8, 6), True),
-                                        (96, (193, 257), True), (192, (129, 131), False), (384, (32, 33), True)])
+                                        (96, (193, 257), True), (192, (129, 131), False), (384, (32, 33), True),
+                                        # 4096 pixels = 128 tiles: the segment counts production takes (_ladder_nseg), 8 (the floor) .. 128 (the cap)
+                                        (96, (64, 64), True), (192, (64, 64), False), (384, (64, 64), True)])
 def test_attn_x3_block_matches_oracle(Cc, hw, cond):
     """Split-precision fused attention (tier bf16x3, csrc/attn_x3.hip): ds_attn_x3_context/_output + ds_gn_apply on fp32 tensors ==
     Residual(PreNorm(LinearCrossAttentionAdd)) of the oracle (components:142-152,252-293) to 2e-5 — every product is three bf16 MFMA
@@ -1071,7 +1091,7 @@ def test_attn_x3_block_matches_oracle(Cc, hw, cond):
     lq = dev(F.linear(c, sd[tag + ".fn.fn.label_query.weight"], sd[tag + ".fn.fn.label_query.bias"])) if cond else None
     bo = dev(sd[tag + ".fn.fn.to_out.0.bias"])
     go, bo2 = dev(sd[tag + ".fn.fn.to_out.1.weight"]), dev(sd[tag + ".fn.fn.to_out.1.bias"])
-    for nseg in (1, 3, lib.ds_attn_x3_segments(B, N, Cc)):
+    for nseg in (1, 3, lib.ds_attn_x3_segments(B, N, Cc)) + _ladder_nseg("bf16x3", Cc, N):
         ab = h.gn_ab_of(x)
         part = torch.empty(lib.ds_linattn_part_floats(B, 4, nseg), device="cuda")
         ctx = torch.empty(B * 4 * 1024, device="cuda")
