@@ -145,6 +145,10 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_istft_plus": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "ds_istft_ws_floats": (_SZ, [_I, _I, _I]),
     "ds_stft_plus": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "ds_stft_images_ws_floats": (_SZ, [_I, _I, _I]),
+    "ds_stft_images": (C.c_int, [_P, _P, C.c_longlong, _I, _I, _I, _P, _P, _P, _P]),
+    "ds_latent_image_ws_floats": (_SZ, [_I, _I]),
+    "ds_latent_image": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "ds_bounds_report": (C.c_int, [C.c_char_p, _I, _I]),
 }
 _UNCHECKED = {"ds_conv3x3_f32_n4_weight_floats", "ds_bounds_report", "ds_abi_version", "ds_conv_stats_parts", "ds_conv1x1_x3_stats_parts", "ds_conv_tile_bn", "ds_dwconv_stats_parts", "ds_attn_fused_stats_parts", "ds_attn_fused_generations", "ds_attn_fused_segments", "ds_attn_fused_segments_gen", "ds_attn_x3_stats_parts", "ds_attn_x3_segments", "ds_vq_attn_segments", "ds_conv3x3_c80_stats_slots", "ds_convt4x4_c80_stats_slots"}

@@ -4,7 +4,8 @@ Replaces the audio branch of encodeBatch2GradioOutput_STFT
 (webUI/natural_language_guided_4/utils.py:219-245: decoder -> .cpu().numpy() -> per-sample
 tools.decode_stft / tools.depad_STFT -> librosa.istft(D, hop_length=256, win_length=1024)) with one
 batched kernel pair (ds_istft_plus): the (B,3,512,T) decoder output never leaves HBM and the whole
-batch is inverted at once.  The UI images of the reference function are out of scope.
+batch is inverted at once.  The spectrogram / phase images of the two batch helpers are rendered from the same device tensor
+(ui_images.stft_images: ds_stft_images) and cross to the host as bytes, one copy per image kind for the whole batch.
 
 librosa is absent offline, so the inverse-STFT stage is parity-unpinned against the reference; it is
 checked against the CPU oracle (librosa's documented algorithm, cross-checked with torch.istft /
@@ -14,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .ui_images import stft_images
 
 
 @torch.no_grad()
@@ -37,20 +39,34 @@ def latents_to_audio(decoder, quantized_latents):
     return stft_representation_to_audio(decoder(quantized_latents))
 
 
+def _image_lists(enc, original_amp=None):
+    """Two lists of per-clip (F+1, T, 3) uint8 arrays: one device -> host copy per image kind."""
+    spec, phase = stft_images(enc, original_amp)
+    return list(spec.cpu().numpy()), list(phase.cpu().numpy())
+
+
+def _signals(enc):
+    return [s.astype(np.float64) for s in stft_representation_to_audio(enc).cpu().numpy()]
+
+
 def encodeBatch2GradioOutput_STFT(decoder, latent_vector_batch, resolution=(512, 256), original_STFT_batch=None):
-    """Signature of utils.py:194.  Returns the reference's 6-tuple with the image slots set to None (UI rendering is
-    out of scope) and the signals as float64 numpy arrays like librosa returns them."""
+    """Signature and 6-tuple of utils.py:194: (spectrogram images, phase images, signals, and the same three with the log-magnitude of
+    original_STFT_batch in place of the decoder's — empty lists when it is not given).  Images are (F+1, T, 3) uint8 arrays, signals
+    float64 arrays like librosa returns them."""
     dev = next(decoder.parameters()).device
     if isinstance(latent_vector_batch, np.ndarray):
         latent_vector_batch = torch.from_numpy(latent_vector_batch)
     rec = decoder(latent_vector_batch.to(dev))
-    signals = [s.astype(np.float64) for s in stft_representation_to_audio(rec).cpu().numpy()]
-    with_amp = []
+    signals = _signals(rec)
+    specs, phases = _image_lists(rec)
+    specs_amp, phases_amp, with_amp = [], [], []
     if original_STFT_batch is not None:
+        orig = torch.as_tensor(original_STFT_batch).to(dev)
         mixed = rec.clone()
-        mixed[:, 0] = torch.as_tensor(original_STFT_batch)[:, 0].to(dev)
-        with_amp = [s.astype(np.float64) for s in stft_representation_to_audio(mixed).cpu().numpy()]
-    return None, None, signals, None, None, with_amp
+        mixed[:, 0] = orig[:, 0]
+        with_amp = _signals(mixed)
+        specs_amp, phases_amp = _image_lists(rec, orig)
+    return specs, phases, signals, specs_amp, phases_amp, with_amp
 
 
 @torch.no_grad()
@@ -74,9 +90,11 @@ def audio_to_stft_representation(audio, time_resolution=256, hop_length=256, pad
 
 @torch.no_grad()
 def InputBatch2Encode_STFT(encoder, STFT_batch, resolution=(512, 256), quantizer=None, squared=True):
-    """Latent branch of utils.py:131-191: (latents, quantised latents); the images / reconstructed signals of the reference
-    tuple are UI products and returned as None."""
+    """5-tuple of utils.py:131-191: the spectrogram / phase images and the signals of the INPUT batch, the latents and the quantised
+    latents (None without a quantizer)."""
     dev = next(encoder.parameters()).device
-    z = encoder(STFT_batch.to(dev))
+    x = STFT_batch.to(dev)
+    z = encoder(x)
     q = quantizer(z)[0] if quantizer is not None else None
-    return None, None, None, z, q
+    specs, phases = _image_lists(x)
+    return specs, phases, _signals(x), z, q

@@ -556,6 +556,22 @@ size_t ds_istft_ws_floats(int B, int F, int T);
  * audio [B][L] fp32 -> enc [B][3][512][T_out] fp32, T_out >= 1 + L/hop.  reflect_pad: 0 = zero padding of the
  * centred frames (librosa >= 0.10 default), 1 = reflect (older librosa). */
 int ds_stft_plus(const float* audio, int B, int L, int hop, int reflect_pad, int T_out, float* enc, void* stream);
+/* The spectrogram and phase images the reference's UI shows for an STFT+ tensor (csrc/ui_images.hip; per clip tools.decode_stft +
+ * tools.depad_STFT + np.abs / np.angle + spectrogram_to_Gradio_image / phase_to_Gradio_image: webUI/natural_language_guided_4/utils.py:8-86
+ * as called at utils.py:172-181, 229-238 and 249-259; tools.np_power_to_db: tools.py:41-50).  enc [B][3][F][T] fp32 -> spec_img, phase_img
+ * [B][F+1][T][3] uint8, row 0 = the highest bin, the last row = the implied zero bin.  amp (or NULL): a second source of the log-magnitude
+ * channel, clip b at amp + b * amp_batch_stride floats ([F][T] each; the "with original amplitude" variant reads channel 0 of the original
+ * batch in place).  Out-of-range phase bytes are the low byte of the int32 value (the reference's cast wraps on x86).  Pointers need
+ * 4-byte alignment only; 16-byte aligned tensors with T % 4 == 0 take the 16-byte path.  ws: ds_stft_images_ws_floats floats. */
+size_t ds_stft_images_ws_floats(int B, int F, int T);
+int ds_stft_images(const float* enc, const float* amp, long long amp_batch_stride, int B, int F, int T, float* ws, unsigned char* spec_img,
+                   unsigned char* phase_img, void* stream);
+/* The latent image (latent_representation_to_Gradio_image, webUI/natural_language_guided_4/utils.py:89-128) without its 8 x 8 enlargement:
+ * lat [B][C][H][W] fp32 (C must be 4) -> img [B][H][W][4] uint8 = trunc((x - min) / (max - min) * 255) per (sample, channel) in fp32,
+ * channels last, flipped vertically; a constant channel renders 0.  lat is not written.  The enlargement is a repeat of bytes and is left
+ * to the caller, after the copy to the host.  ws: ds_latent_image_ws_floats floats. */
+size_t ds_latent_image_ws_floats(int B, int C);
+int ds_latent_image(const float* lat, int B, int C, int H, int W, float* ws, unsigned char* img, void* stream);
 
 #ifdef __cplusplus
 }

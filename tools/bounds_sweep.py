@@ -31,10 +31,33 @@ def report(tag, fail):
         fail.append((tag, n, msg))
 
 
+def sweep_ui_images(fail):
+    """The UI images (csrc/ui_images.hip): both paths of ds_stft_images (16-byte loads / one pixel per thread), ragged last blocks, rows and
+    clips whose byte offset is not a multiple of 16, misaligned views, the second magnitude source, and ds_latent_image."""
+    from diffusynth_amd import ui_images as U
+    for B, F, T in ((2, 512, 64), (3, 512, 100), (1, 512, 27), (1, 512, 300), (1, 512, 16), (1, 128, 20), (1, 512, 1), (3, 512, 9),
+                    (8, 512, 256), (2, 37, 5)):
+        enc = synth_input("bs_ui%d_%d" % (F, T), (B, 3, F, T))
+        U.stft_images(enc.cuda())
+        flat = torch.zeros(enc.numel() + 1, device="cuda")
+        flat[1:] = enc.flatten().cuda()
+        U.stft_images(flat[1:].view(B, 3, F, T))
+        amp = synth_input("bs_ui_amp%d_%d" % (F, T), (B, 2, F, T)).cuda()
+        U.stft_images(enc.cuda(), amp)
+    report("stft_images 10 shapes x (aligned, misaligned view, second magnitude source)", fail)
+    for shape in ((1, 4, 128, 64), (3, 4, 16, 12), (2, 4, 5, 3), (64, 4, 128, 64)):
+        U.latent_images(synth_input("bs_lat%d" % shape[3], shape).cuda())
+    report("latent_image 4 shapes", fail)
+
+
 def main():
     lib = L.load()
     assert "bounds" in L.lib_path(), L.lib_path()
     fail = []
+    if "--only-ui-images" in sys.argv:
+        sweep_ui_images(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
     # 0) the tool detects a violation (negative control) and resets
     b = torch.zeros(16, device="cuda")
     sink = torch.zeros(1, device="cuda")
@@ -105,6 +128,8 @@ def main():
     except L.DsError as e:
         print("[bounds] empty split-K slice rejected:", str(e)[-90:], flush=True)
     report("after rejected launch", fail)
+    # 4) the UI images
+    sweep_ui_images(fail)
     if fail:
         print("BOUNDS VIOLATIONS", fail)
         sys.exit(1)

@@ -458,7 +458,49 @@ def gen_vq_bn(R):
              dec_q=q, dec_y=g._decoder(q), enc_x=x, enc_z=g._encoder(x))
 
 
-GENS = {"vq_bn": gen_vq_bn, "vq_plain": gen_vq_plain, "keys": gen_keys, "schedule": gen_schedule, "noise_layout": gen_noise_layout, "masks": gen_masks,
+def gen_ui_images(R):
+    """The UI's pictures (webUI/natural_language_guided_4/utils.py): spectrogram_to_Gradio_image / phase_to_Gradio_image on
+    decode_stft -> depad_STFT -> np.abs / np.angle exactly as the two batch helpers call them, and latent_representation_to_Gradio_image.
+    The inputs are seeded or already committed (tests/ui_images_ref.py rebuilds them), so the file holds outputs only: the red channel of
+    every image (green == red is asserted here) and the two blue constants; latent images before their 8 x 8 enlargement (asserted to be
+    a plain repeat)."""
+    import importlib
+    rtools = R[4]
+    U = importlib.import_module("webUI.natural_language_guided_4.utils")
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ui_images_ref as C
+    out, blues = {}, {"spec": set(), "phase": set()}
+
+    def images(stft):
+        D = rtools.depad_STFT(rtools.decode_stft(stft))
+        return {"spec": U.spectrogram_to_Gradio_image(np.abs(D)), "phase": U.phase_to_Gradio_image(np.angle(D))}
+
+    for case in C.STFT_CASES:
+        enc, amp = C.stft_case_inputs(case)
+        red = {"spec": [], "phase": []}
+        for i, stft in enumerate(enc.copy()):
+            if amp is not None:
+                stft[0, :, :] = amp[i, 0, :, :]
+            for kind, img in images(stft).items():
+                assert img.dtype == np.uint8 and img.shape == (stft.shape[1] + 1, stft.shape[2], 3)
+                assert np.array_equal(img[..., 0], img[..., 1])
+                blues[kind] |= set(np.unique(img[..., 2]).tolist())
+                red[kind].append(img[..., 0])
+        for kind in red:
+            out[f"{case}_{kind}"] = np.stack(red[kind])
+    assert len(blues["spec"]) == 1 and len(blues["phase"]) == 1, blues
+    out["spec_blue"], out["phase_blue"] = np.uint8(blues["spec"].pop()), np.uint8(blues["phase"].pop())
+    for case in C.LATENT_CASES:
+        lat = C.latent_case_input(case)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            big = U.latent_representation_to_Gradio_image(torch.from_numpy(lat.copy()))
+        small = big[::8, ::8]
+        assert big.dtype == np.uint8 and np.array_equal(big, np.repeat(np.repeat(small, 8, axis=0), 8, axis=1))
+        out[case] = small
+    save("ui_images", **out)
+
+
+GENS = {"ui_images": gen_ui_images, "vq_bn": gen_vq_bn, "vq_plain": gen_vq_plain, "keys": gen_keys, "schedule": gen_schedule, "noise_layout": gen_noise_layout, "masks": gen_masks,
         "step": gen_step, "blocks": gen_blocks, "unet": gen_unet, "traj": gen_traj, "tail": gen_tail, "front": gen_front, "head": gen_head, "interp": gen_interp}
 
 
