@@ -51,6 +51,8 @@ with open(_HEADER) as _f:
 _STRUCTS = _parse_structs(_HEADER_TEXT)
 SR = _parse_defines(_HEADER_TEXT, "DS_SR_")     # ds_step_rows table layout (field indices and row widths)
 DW_FAMILY = {v: k[6:].lower() for k, v in _parse_defines(_HEADER_TEXT, "DS_DW_").items()}     # ds_dwconv_launch_choice: family code -> name
+PV = _parse_defines(_HEADER_TEXT, "DS_PV_")     # arranger signal table (field indices and row width)
+MIX_BLOCK = _parse_defines(_HEADER_TEXT, "DS_MIX_")["DS_MIX_BLOCK"]
 ConvParams = _STRUCTS["ds_conv_params"]
 PackConvParams = _STRUCTS["ds_pack_conv_params"]
 DwconvParams = _STRUCTS["ds_dwconv_params"]
@@ -149,6 +151,14 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_stft_images": (C.c_int, [_P, _P, C.c_longlong, _I, _I, _I, _P, _P, _P, _P]),
     "ds_latent_image_ws_floats": (_SZ, [_I, _I]),
     "ds_latent_image": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "ds_pv_stft": (C.c_int, [_P, _P, _I, _I, C.c_longlong, C.c_longlong, _P, _P]),
+    "ds_pv_vocode": (C.c_int, [_P, _P, _P, _P, _I, C.c_longlong, C.c_longlong, _P, _P]),
+    "ds_pv_istft_ws_bytes": (_SZ, [C.c_longlong]),
+    "ds_pv_istft": (C.c_int, [_P, _P, _I, _I, _I, C.c_longlong, C.c_longlong, _P, _P, _P]),
+    "ds_resample_sinc": (C.c_int, [_P, _P, _P, _I, _I, C.c_longlong, C.c_longlong, _P, _P]),
+    "ds_peak_normalize_ws_bytes": (_SZ, [_I, _I]),
+    "ds_peak_normalize": (C.c_int, [_P, _P, _I, _I, C.c_longlong, _P, _P, _P]),
+    "ds_mix_notes": (C.c_int, [_P, C.c_longlong, _P, _I, _P, _P, _I, _P, _I, _P]),
     "ds_bounds_report": (C.c_int, [C.c_char_p, _I, _I]),
 }
 _UNCHECKED = {"ds_conv3x3_f32_n4_weight_floats", "ds_bounds_report", "ds_abi_version", "ds_conv_stats_parts", "ds_conv1x1_x3_stats_parts", "ds_conv_tile_bn", "ds_dwconv_stats_parts", "ds_attn_fused_stats_parts", "ds_attn_fused_generations", "ds_attn_fused_segments", "ds_attn_fused_segments_gen", "ds_attn_x3_stats_parts", "ds_attn_x3_segments", "ds_vq_attn_segments", "ds_conv3x3_c80_stats_slots", "ds_convt4x4_c80_stats_slots"}

@@ -573,6 +573,58 @@ int ds_stft_images(const float* enc, const float* amp, long long amp_batch_strid
 size_t ds_latent_image_ws_floats(int B, int C);
 int ds_latent_image(const float* lat, int B, int C, int H, int W, float* ws, unsigned char* img, void* stream);
 
+/* ---------------------------------------------------------------- arranger audio stage (csrc/arranger.hip)
+ * What webUI/natural_language_guided_4/track_maker.py does on the host per note event: peak normalisation (:142), chained
+ * librosa.effects.pitch_shift(y, sr, n_steps, n_fft=4096, hop_length=1024) calls (:12-47) and the mix into the track (:147).  One
+ * pitch_shift = ds_pv_stft -> ds_pv_vocode -> ds_pv_istft -> ds_resample_sinc, each batched over n_signals signals of different lengths.
+ * A signal is row s of tab, a device array [n_signals][DS_PV_NI] int32 (offsets and counts in ELEMENTS of the concatenated buffers):
+ *   XOFF, LEN    its samples in x (ds_pv_stft, ds_peak_normalize) and in out (ds_resample_sinc, ds_peak_normalize: fix_length to LEN)
+ *   FOFF, NF     its analysis frames in spec [total_frames][2049][2]; NF = 1 + LEN / 1024 (centred, zero padded, periodic Hann 4096)
+ *   TOFF, NOUT   its synthesis frames in voc [total_out][2049][2], in the frame workspace and in step_idx / step_alpha:
+ *                NOUT = len(arange(0, NF, rate)), step_idx = floor(step), step_alpha = step mod 1, both computed in float64
+ *   SOFF, SLEN   its stretched samples in y; SLEN = round(LEN / rate)
+ *   NRES         ceil(SLEN * rate): output samples from NRES on are zero
+ * Whatever is floored or rounded is the host's, in float64.  A row that does not fit the stated totals reads and writes nothing.
+ * No atomics: results are bit-reproducible and do not depend on what else is in the batch.
+ * ds_pv_vocode keeps the phase as a running product of unit phasors u(R) conj(u(L)) (u(0) = 1), which is librosa's accumulator
+ * phi + wrap(angle R - angle L - phi) modulo 2 pi.  ds_pv_istft: window-sum-square normalisation where it exceeds FLT_MIN, zeros where no
+ * frame reaches; ws = ds_pv_istft_ws_bytes(total_out) bytes.
+ * ds_resample_sinc (rates: device array of n_signals doubles) is this library's definition, not librosa's soxr_hq: output sample m
+ * sits at input position m / rates[s]; kernel h(t) = fc sinc(fc t) kaiser(t fc / Z; beta), fc = DS_RS_FC min(1, rate), Z = DS_RS_ZEROS zero
+ * crossings each side, beta = DS_RS_BETA; samples outside the stretched signal are zero. */
+#define DS_PV_XOFF 0
+#define DS_PV_LEN 1
+#define DS_PV_FOFF 2
+#define DS_PV_NF 3
+#define DS_PV_TOFF 4
+#define DS_PV_NOUT 5
+#define DS_PV_SOFF 6
+#define DS_PV_SLEN 7
+#define DS_PV_NRES 8
+#define DS_PV_NI 9
+#define DS_RS_FC 0.95
+#define DS_RS_ZEROS 32.0
+#define DS_RS_BETA 12.0
+int ds_pv_stft(const float* x, const int32_t* tab, int n_signals, int max_frames, long long total_samples, long long total_frames, float* spec,
+               void* stream);
+int ds_pv_vocode(const float* spec, const int32_t* tab, const int32_t* step_idx, const float* step_alpha, int n_signals, long long total_frames,
+                 long long total_out, float* voc, void* stream);
+size_t ds_pv_istft_ws_bytes(long long total_out);
+int ds_pv_istft(const float* voc, const int32_t* tab, int n_signals, int max_out, int max_stretched, long long total_out, long long total_stretched,
+                float* ws, float* y, void* stream);
+int ds_resample_sinc(const float* ys, const int32_t* tab, const double* rates, int n_signals, int max_len, long long total_stretched,
+                     long long total_samples, float* out, void* stream);
+/* out = x / max|x| per signal (IEEE division; rows XOFF, LEN of tab).  ws: ds_peak_normalize_ws_bytes bytes. */
+size_t ds_peak_normalize_ws_bytes(int n_signals, int max_len);
+int ds_peak_normalize(const float* x, const int32_t* tab, int n_signals, int max_len, long long total_samples, float* ws, float* out, void* stream);
+/* track[s] = sum, in event order, of the notes that cover s (every sample of track is written).  ev [n_events][3] int32: start sample in the
+ * track, offset of the note in notes, length.  Block b owns samples [b DS_MIX_BLOCK, (b + 1) DS_MIX_BLOCK) and walks
+ * blk_ev[blk_ptr[b] .. blk_ptr[b + 1]): the ascending indices of the events that touch them (blk_ptr has ceil(track_len / DS_MIX_BLOCK) + 1
+ * entries).  fp32 additions in that order: what numpy's `float32 += float64` gives for fp32-valued notes. */
+#define DS_MIX_BLOCK 1024
+int ds_mix_notes(const float* notes, long long total_samples, const int32_t* ev, int n_events, const int32_t* blk_ptr, const int32_t* blk_ev,
+                 int n_blk_ev, float* track, int track_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

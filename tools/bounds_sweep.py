@@ -50,12 +50,35 @@ def sweep_ui_images(fail):
     report("latent_image 4 shapes", fail)
 
 
+def sweep_arranger(fail):
+    """The arranger's audio stage (csrc/arranger.hip): ragged batches incl. a signal shorter than one hop and one of a single odd frame pair,
+    both directions of the shift, the chain tree, peak normalisation, and a mix with notes at both ends of the track."""
+    from diffusynth_amd import arranger as A
+    sigs = [synth_input("bs_arr%d" % n, (n,)).cuda() for n in (28416, 77568, 30001, 4097, 1023, 50000, 2048, 1)]
+    A.pitch_shift(sigs[:7], [1, 2, 3, 4, -3, 0.5, 4])
+    A.pitch_shift(sigs[:7], [-12, 12, 0, -4, 7, 4, -1])
+    A.pitch_shift(torch.stack([sigs[0], sigs[0]]), 4)
+    report("pitch_shift 2 ragged batches of 7 + a (2, L) batch", fail)
+    A.pitch_shift_chain([sigs[0], sigs[0], sigs[2], sigs[4]], [31, 5, 9, 2])
+    report("pitch_shift_chain tree (8 levels)", fail)
+    normed = A.peak_normalize(sigs)
+    report("peak_normalize 8 signals (1 .. 77568 samples)", fail)
+    n = 100000
+    A.mix_notes(normed, [(0, 0), (n - 77568, 1), (1023, 7), (n - 1, 7), (0, 7), (500, 3), (500, 3), (n - 1023, 4), (60000, 2)], n)
+    A.mix_notes(normed[7:], [(3, 0)], 5)
+    report("mix_notes 9 events over 98 blocks + a 5-sample track", fail)
+
+
 def main():
     lib = L.load()
     assert "bounds" in L.lib_path(), L.lib_path()
     fail = []
     if "--only-ui-images" in sys.argv:
         sweep_ui_images(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
+    if "--only-arranger" in sys.argv:
+        sweep_arranger(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
         sys.exit(1 if fail else 0)
     # 0) the tool detects a violation (negative control) and resets
@@ -130,6 +153,8 @@ def main():
     report("after rejected launch", fail)
     # 4) the UI images
     sweep_ui_images(fail)
+    # 5) the arranger's audio stage
+    sweep_arranger(fail)
     if fail:
         print("BOUNDS VIOLATIONS", fail)
         sys.exit(1)
