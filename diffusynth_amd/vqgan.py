@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .engine import _EngineBase, _PlanBuilder
+from .engine import _ChanSums, _EngineBase, _PlanBase
 from .unet import _Holder
 
 PRODUCTION_CONFIG = dict(in_channels=3, hidden_channels=[80, 160], embedding_dim=4, out_channels=3, block_depth=2,
@@ -325,7 +325,8 @@ class DecoderEngine(_EngineBase):
                 d["in_nchw"] = self._f32(m.weight).reshape(cout, cin).contiguous()
             return d
         if kind == "attn":
-            d = {"qkv": self._pack_conv(m.to_qkv.weight, None), "out": self._pack_conv(m.to_out.weight, m.to_out.bias), "nin": None}
+            d = {"qkv": self._pack_conv(m.to_qkv.weight, None), "out": self._pack_conv(m.to_out.weight, m.to_out.bias), "nin": None,
+                 "fused": None, "merged": None}
             dim = int(m.to_qkv.weight.shape[1])
             if self.dt == L.DS_BF16 and dim in (80, 160) and tuple(m.to_qkv.weight.shape[:2]) == (96, dim) and self.use_vq_attn:
                 # the whole block on csrc/vq_attn.hip: context from x, then ONE per-sample 1x1 convolution (q enters linearly)
@@ -352,7 +353,7 @@ class DecoderEngine(_EngineBase):
             if hasattr(m, "nin_shortcut"):
                 d["nin"] = self._pack_conv(m.nin_shortcut.weight, m.nin_shortcut.bias, small_out=small)
             cout, cin = m.conv1.weight.shape[:2]
-            d["c80"] = None
+            d["c80"] = d["final"] = None
             if (self.dt == L.DS_BF16 and cout == 80 and cin == 80 and d["nin"] is None and not self.bn and self.use_c80):
                 # the 80-channel block body: 3x3 + bias + residual as one kernel (conv3x3_c80.hip) behind the GroupNorm apply pass
                 wf = self._f32(m.conv1.weight)
@@ -403,16 +404,17 @@ class DecoderEngine(_EngineBase):
         return out
 
 
-class _DecoderPlan(_PlanBuilder):
-    def __init__(self, eng, B, H, W):
-        super().__init__(eng, B, H, W, False)
-        self.tb_all = self.lab_all = None
+_Q, _QOUT = range(2)         # _Op.late of the plans below: which tensor of run(q, out)
+
+
+class _DecoderPlan(_PlanBase):
+    prof_all = True              # diagnostics (tools/tail_bench.py --ops): an event pair around every op
 
     def vq_attention(self, d, x):
         """VQGAN.py:261-272: one head of 32, softmax over n on k only, 1x1 skip."""
         e, B = self.e, self.B
         N = x.H * x.W
-        f = d.get("fused")
+        f = d["fused"]
         if f is not None and x.C in (80, 160):
             lib = self.lib
             nseg = lib.ds_vq_attn_segments(B, N, x.C)
@@ -424,12 +426,12 @@ class _DecoderPlan(_PlanBuilder):
             p = L.VqAttnParams(x=x.off, B=B, N=N, C=x.C, nseg=nseg, wqkv=f["wqkv"].data_ptr(), wq=f["wq"].data_ptr(), wout=f["wout"].data_ptr(),
                                wnin=L.ptr(f["wnin"]), bias=f["bias"].data_ptr(), part=part[0], ctx=ctx[0], wfold=wfold[0], y=y.off, stats_ws=ws[0])
             self.conv_meta[len(self.ops) + 1] = (0, 2.0 * B * N * x.C * x.C, f"attention {x.C} @{x.H}x{x.W}: per-sample 1x1")
-            self.op("ds_vq_attn_context", p)
-            self.op("ds_vq_attn_output", p)
+            self.op("ds_vq_attn_context", C.byref(p))
+            self.op("ds_vq_attn_output", C.byref(p))
             self.free_raw(part)
             self.free_raw(ctx)
             self.free_raw(wfold)
-            y.stats = (ws, nseg // 4, "chan_ws")          # per-channel partial sums of y: the next Normalize only finishes them
+            y.stats = _ChanSums(ws, nseg // 4)          # per-channel partial sums of y: the next Normalize only finishes them
             return y
         qkv = self.conv(d["qkv"], x)
         nseg = max(1, min(N // 1024, 16))
@@ -438,12 +440,12 @@ class _DecoderPlan(_PlanBuilder):
         ao = self.act(32, x.H, x.W)
         p = L.AttnParams(qkv=qkv.off, B=B, N=N, heads=1, dtype=e.dt, nseg=nseg, part=part[0], ctx=ctx[0], label_q=None,
                          label_k=None, label_v=None, lq_stride=0, lk_stride=0, lv_stride=0, q_softmax=0, scale=1.0, out=ao.off)
-        self.op("ds_linattn_context", p)
-        self.op("ds_linattn_output", p)
+        self.op("ds_linattn_context", C.byref(p))
+        self.op("ds_linattn_output", C.byref(p))
         self.free(qkv)
         self.free_raw(part)
         self.free_raw(ctx)
-        if d.get("merged") is not None:
+        if d["merged"] is not None:
             out = self.conv(d["merged"], x, src1=ao)
         elif d["nin"] is not None:
             out = self.conv(d["nin"], x)
@@ -462,7 +464,7 @@ class _DecoderPlan(_PlanBuilder):
         out = self.act(x.C, x.H, x.W)
         p = L.GnApplyParams(x=x.off, res=None, out=out.off, gn_ab=e.bn_unit_ab(self.B).data_ptr(), gamma=nrm[0].data_ptr(), beta=nrm[1].data_ptr(),
                             cbias=None, cb_stride=0, B=self.B, HW=x.H * x.W, C=x.C, G=1, act=act, dtype=e.dt)
-        self.op("ds_gn_apply", p)
+        self.op("ds_gn_apply", C.byref(p))
         return out
 
     def vq_res(self, d, x):
@@ -470,7 +472,7 @@ class _DecoderPlan(_PlanBuilder):
         e = self.e
         # the Encoder's blocks are built with act_type="act_type" (VQGAN.py:441) => swish whatever the config says
         act = L.ACT_RELU if (e.cfg["act_type"] == "relu" and e.is_decoder) else L.ACT_SILU
-        if d.get("c80") is not None and x.C == 80:
+        if d["c80"] is not None and x.C == 80:
             # statistics, act(GroupNorm(x)) in one apply pass, then ONE kernel: 3x3 + bias + x (conv3x3_c80.hip)
             B, G = self.B, e.cfg["num_groups"]
             ab = self.raw(B * G * 2 * 4)
@@ -483,11 +485,11 @@ class _DecoderPlan(_PlanBuilder):
             hact = self.act(80, x.H, x.W)
             gp = L.GnApplyParams(x=x.off, res=None, out=hact.off, gn_ab=ab[0], gamma=d["norm"][0].data_ptr(), beta=d["norm"][1].data_ptr(),
                                  cbias=None, cb_stride=0, B=B, HW=x.H * x.W, C=80, G=G, act=act, dtype=e.dt)
-            self.op("ds_gn_apply", gp)
+            self.op("ds_gn_apply", C.byref(gp))
             self.op("ds_conv3x3_c80_res", hact.off, x.off, B, x.H, x.W, wp.data_ptr(), bias.data_ptr(), out.off, ws[0])
             self.free(hact)
             self.free_raw(ab)
-            out.stats = (ws, slots, "chan_ws")          # (released with the tensor if no Normalize consumes it)
+            out.stats = _ChanSums(ws, slots)          # (released with the tensor if no Normalize consumes it)
             return out
         h = self._normalize(x, d["norm"], act)
         if d["nin"] is not None:
@@ -501,14 +503,13 @@ class _DecoderPlan(_PlanBuilder):
     def build(self, base):
         self.base = base
         e, B, H, W = self.e, self.B, self.H, self.W
-        first = e.P[0].get("in_nchw") if (e.plan_list and e.plan_list[0][0] == "conv1x1") else None
+        first = e.P[0]["in_nchw"] if (e.plan_list and e.plan_list[0][0] == "conv1x1") else None
         if first is not None:
             x = self.act(e.plan_list[0][2], H, W)
-            self.ops.append(("input_conv", x.off, first))
+            self.op("ds_conv1x1_in_nchw", None, B, e.in_ch, H * W, first.data_ptr(), None, first.shape[0], x.off, late=((0, _Q),))
         else:
-            xin = self.act(e.cin0, H, W)
-            self.ops.append(("input", xin.off))
-            x = xin
+            x = self.act(e.cin0, H, W)
+            self.op("ds_nchw_to_nhwc", None, B, e.in_ch, H, W, x.off, e.cin0, e.dt, late=((0, _Q),))
         pending_norm = None
         fused_gn = None                                # (ab, norm): Normalize + ReLU left to the following layer's input staging
         for idx, ((kind, cin, cout), d) in enumerate(zip(e.plan_list, e.P)):
@@ -518,12 +519,14 @@ class _DecoderPlan(_PlanBuilder):
                 y = self.conv(d["conv"], x)
             elif kind == "attn":
                 y = self.vq_attention(d, x)
-            elif kind == "res" and d.get("final") is not None and x.W > 8 and (kind, cin, cout) == e.plan_list[-1][:3] and d is e.P[-1]:
+            elif kind == "res" and d["final"] is not None and x.W > 8 and (kind, cin, cout) == e.plan_list[-1][:3] and d is e.P[-1]:
                 # last block of the decoder: GroupNorm statistics, then ONE kernel reads x once and writes the activated fp32 planes
                 G = e.cfg["num_groups"]
                 ab = self.raw(B * G * 2 * 4)
                 self._stats_op(x, G, 1e-6, ab)
-                self.ops.append(("final", x.off, x.C, x.H, x.W, ab[0], d))
+                w3, b3, wn, bn = d["final"]
+                self.op("ds_dec_final", x.off, B, x.H, x.W, x.C, ab[0], G, d["norm"][0].data_ptr(), d["norm"][1].data_ptr(),
+                        w3.data_ptr(), b3.data_ptr(), wn.data_ptr(), bn.data_ptr(), None, late=((13, _QOUT),))
                 self.free_raw(ab)
                 self.out_hw = (x.H, x.W)
                 self.free(x)
@@ -535,7 +538,7 @@ class _DecoderPlan(_PlanBuilder):
                 continue
             elif kind == "relu":
                 nxt = e.plan_list[idx + 1][0] if idx + 1 < len(e.plan_list) else None
-                if nxt == "up" and e.P[idx + 1].get("up80") is not None and x.C in (80, 160):
+                if nxt == "up" and e.P[idx + 1]["up80"] is not None and x.C in (80, 160):
                     # the 80-channel Upsample applies Normalize + ReLU to its input while staging it: statistics only, no apply pass
                     G = e.cfg["num_groups"]
                     ab = self.raw(B * G * 2 * 4)
@@ -545,12 +548,12 @@ class _DecoderPlan(_PlanBuilder):
                     continue
                 y = self._normalize(x, pending_norm, L.ACT_RELU)   # Normalize + nn.ReLU fused
                 pending_norm = None
-            elif kind == "up" and d.get("up80") is not None and x.C in (80, 160):
+            elif kind == "up" and d["up80"] is not None and x.C in (80, 160):
                 wp, bias = d["up80"]
                 y = self.act(80, 2 * x.H, 2 * x.W)
                 self.conv_meta[len(self.ops)] = (15, 2.0 * B * x.H * x.W * 4 * 80 * 4 * x.C, f"2x2T {x.C}->80 @{x.H}x{x.W}")
                 # per-channel statistics of the output where the next layer is a Normalize (the last Upsample: the final block follows)
-                want_ws = idx + 1 < len(e.plan_list) and e.plan_list[idx + 1][0] == "res" and e.P[idx + 1].get("final") is not None
+                want_ws = idx + 1 < len(e.plan_list) and e.plan_list[idx + 1][0] == "res" and e.P[idx + 1]["final"] is not None
                 slots = self.lib.ds_convt4x4_c80_stats_slots(B, x.H, x.W, x.C)
                 ws = self.raw(B * slots * 80 * 2 * 4) if want_ws else None
                 if fused_gn is not None:
@@ -562,7 +565,7 @@ class _DecoderPlan(_PlanBuilder):
                 else:
                     self.op("ds_convt4x4_c80", x.off, B, x.H, x.W, x.C, wp.data_ptr(), L.ptr(bias), y.off, None, 0, None, None, ws[0] if ws else None)
                 if ws:
-                    y.stats = (ws, slots, "chan_ws")
+                    y.stats = _ChanSums(ws, slots)
             elif kind == "up":
                 y = self.conv(d["conv"], x)
             elif kind == "down":
@@ -574,45 +577,11 @@ class _DecoderPlan(_PlanBuilder):
             self.free(x)
             x = y
         self.out_hw = (x.H, x.W)
-        self.ops.append(("tail" if e.is_decoder else "latent", x.off, x.C))
+        if e.is_decoder:
+            self.op("ds_decoder_tail", x.off, e.dt, B, x.C, x.H * x.W, None, late=((5, _QOUT),))
+        else:
+            self.op("ds_nhwc_to_nchw", x.off, e.dt, B, e.out_ch, x.C, x.H, x.W, None, late=((7, _QOUT),))
         self.free(x)
 
     def run(self, q, out):
-        e, B = self.e, self.B
-        st = L.current_stream()
-        lib = self.lib
-        prof = getattr(self, "prof", None)                    # diagnostics (tools/tail_bench.py --ops): an event after every op
-        if prof is not None:
-            # ... and one in front of the first: whatever the caller enqueued before this plan (the VQ search) is not op 0's time
-            self.prof_start = torch.cuda.Event(enable_timing=True)
-            self.prof_start.record()
-        for k, item in enumerate(self.ops):
-            tag = item[0]
-            if tag == "input":
-                rc = lib.ds_nchw_to_nhwc(q.data_ptr(), B, q.shape[1], self.H, self.W, item[1], e.cin0, e.dt, st)
-                name = "ds_nchw_to_nhwc"
-            elif tag == "input_conv":
-                w = item[2]
-                rc = lib.ds_conv1x1_in_nchw(q.data_ptr(), B, q.shape[1], self.H * self.W, w.data_ptr(), None, w.shape[0], item[1], st)
-                name = "ds_conv1x1_in_nchw"
-            elif tag == "tail":
-                rc = lib.ds_decoder_tail(item[1], e.dt, B, item[2], self.out_hw[0] * self.out_hw[1], out.data_ptr(), st)
-                name = "ds_decoder_tail"
-            elif tag == "final":
-                _, xoff, xc, xh, xw, ab, d = item
-                w3, b3, wn, bn = d["final"]
-                rc = lib.ds_dec_final(xoff, B, xh, xw, xc, ab, e.cfg["num_groups"], d["norm"][0].data_ptr(), d["norm"][1].data_ptr(),
-                                      w3.data_ptr(), b3.data_ptr(), wn.data_ptr(), bn.data_ptr(), out.data_ptr(), st)
-                name = "ds_dec_final"
-            elif tag == "latent":
-                rc = lib.ds_nhwc_to_nchw(item[1], e.dt, B, out.shape[1], item[2], self.out_hw[0], self.out_hw[1], out.data_ptr(), st)
-                name = "ds_nhwc_to_nchw"
-            else:
-                fn, args, name = item
-                rc = fn(C.byref(args[0]), st) if isinstance(args[0], C.Structure) else fn(*args, st)
-            if rc != 0:
-                L.check(rc, name)
-            if prof is not None:
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record()
-                prof.append((k, name, ev))
+        self.launch(0, len(self.ops), L.current_stream(), (q, out), self._prof_now())

@@ -173,3 +173,17 @@ def test_policy_module_is_pure_python():
     imported = {a.name.split(".")[0] for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names}
     imported |= {(n.module or "").split(".")[0] or "." for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)}
     assert imported <= {"collections"}, imported
+
+
+def test_free_releases_the_statistics_buffer_of_every_form():
+    """An activation's GroupNorm statistics come in three forms (engine._Partials / _Finished / _ChanSums); freeing the activation
+    returns the buffer of whichever is attached to the arena.  (The finished form once raised a TypeError here and kept its bytes.)"""
+    from diffusynth_amd import engine as E
+    plan = object.__new__(E._PlanBase)                # free() needs the arena and its base address only: no library, no device
+    plan.arena, plan.base = E._Arena(), 4096
+    for form in (lambda buf: E._Partials(buf, 3), lambda buf: E._Finished(buf), lambda buf: E._ChanSums(buf, 5)):
+        off, n = plan.arena.alloc(1000)
+        a = E._Act(plan.base + off, n, 8, 4, 4)
+        a.stats = form(plan.raw(64))
+        plan.free(a)
+        assert a.stats is None and plan.arena.free == [[0, 1 << 62]]

@@ -85,7 +85,7 @@ def _signature(eng, B, H, W, paired=False):
     pb = _PlanBuilder(eng, B, H, W, True, paired)
     pb.build(4096)
     cat, counts = pb.launch_signature()
-    chans = tuple(it[1][0].C for it in pb.ops if not isinstance(it[0], str) and it[2] in ("ds_attn_x3_context", "ds_attn_fused_context"))
+    chans = tuple(op.args[0]._obj.C for op in pb.ops if op.name in ("ds_attn_x3_context", "ds_attn_fused_context"))
     return cat, counts, chans
 
 

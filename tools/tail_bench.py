@@ -20,7 +20,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--ops", type=int, default=0, help="1: per-op timeline of the decoder plan (events after every op)")
+    ap.add_argument("--ops", type=int, default=0, help="1: per-op timeline of the decoder plan (an event pair around every op)")
     a = ap.parse_args()
     torch.manual_seed(0)
     vae = VQGAN(**PRODUCTION_CONFIG).cuda()
@@ -46,12 +46,10 @@ def main():
             e0.record()
             run()
             torch.cuda.synchronize()
-            print(f"  before the decoder plan (VQ search, layout) {e0.elapsed_time(pl.prof_start) * 1e3:8.1f} us")
-            prev = pl.prof_start
-            for k, name, ev in pl.prof:
+            print(f"  before the decoder plan (VQ search, layout) {e0.elapsed_time(pl.prof[0][1]) * 1e3:8.1f} us")
+            for k, ev0, ev1 in pl.prof:
                 meta = pl.conv_meta.get(k)
-                print(f"  op{k:3d} {name:22s} {prev.elapsed_time(ev) * 1e3:8.1f} us  {meta[2] if meta else ''}")
-                prev = ev
+                print(f"  op{k:3d} {pl.ops[k].name:22s} {ev0.elapsed_time(ev1) * 1e3:8.1f} us  {meta[2] if meta else ''}")
             pl.prof = None
     print(f"tail B={a.batch} {a.dtype}: {ms:.2f} ms per batch -> audio {tuple(audio.shape)}; {a.batch / ms * 1e3:.0f} clips/s")
 
