@@ -65,8 +65,11 @@ class PackedConv:
 
 
 def run_conv(pc, x0, x1=None, off1=(0, 0), stride=1, pad=0, gn_ab=None, act=L.ACT_NONE, res=None, want_stats=False,
-             nchw_out=False, ksplit=1):
-    """x0/x1/res: NHWC device tensors.  Returns (out NHWC or NCHW fp32, stats partial tensor or None)."""
+             nchw_out=False, ksplit=1, gn_part=None):
+    """x0/x1/res: NHWC device tensors.  gn_part = (buffer [B][parts][2], parts, count, eps) replaces gn_ab: the kernel reduces the
+    producer's raw partials itself (the fold tables are passed as with gn_ab).  Returns (out NHWC or NCHW fp32, stats partial tensor or None)."""
+    assert gn_ab is None or gn_part is None
+    fold = gn_ab is not None or gn_part is not None
     B, H, W, C0 = x0.shape
     C1 = x1.shape[3] if x1 is not None else 0
     if pc.transposed:
@@ -83,10 +86,12 @@ def run_conv(pc, x0, x1=None, off1=(0, 0), stride=1, pad=0, gn_ab=None, act=L.AC
                      off_h1=off1[0], off_w1=off1[1], wpk=pc.w.data_ptr(), Cout=pc.Cout, cout_pad=pc.cout_pad, KH=pc.KH,
                      KW=pc.KW, stride=stride, pad_h=pad, pad_w=pad, Ho=Ho, Wo=Wo, transposed=int(pc.transposed),
                      out=out.data_ptr(), out_C=out_C, out_c0=0, out_nchw_f32=0, bias=L.ptr(pc.bias),
-                     gn_ab=L.ptr(gn_ab), fold_t1=L.ptr(pc.t1) if gn_ab is not None else None,
-                     fold_t2=L.ptr(pc.t2) if gn_ab is not None else None, ncls=pc.ncls if gn_ab is not None else 1,
+                     gn_ab=L.ptr(gn_ab), fold_t1=L.ptr(pc.t1) if fold else None,
+                     fold_t2=L.ptr(pc.t2) if fold else None, ncls=pc.ncls if fold else 1,
                      act=act, res=L.ptr(res), stats_part=None, B=B, dtype=pc.dt, tile=pc.tile)
     p.wk_order = pc.k_order
+    if gn_part is not None:
+        p.gn_part, p.gn_parts, p.gn_count, p.gn_eps = gn_part[0].data_ptr(), gn_part[1], float(gn_part[2]), gn_part[3]
     st = None
     slab = None
     if ksplit > 1:

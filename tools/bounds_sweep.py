@@ -69,10 +69,301 @@ def sweep_arranger(fail):
     report("mix_notes 9 events over 98 blocks + a 5-sample track", fail)
 
 
+def _partials(stored, parts):
+    """(sum, sumsq) of ``parts`` chunks of each sample of a device tensor as fp32 [B][parts][2], placed 24 bytes into a NaN-filled allocation:
+    the base is 8-byte but not 16-byte aligned and anything read beyond the buffer is NaN (tests/gn_partials_ref.py:guarded)."""
+    xd = stored.double().flatten(1)
+    p = torch.stack([torch.stack([c.sum(1), (c * c).sum(1)], 1) for c in torch.tensor_split(xd, parts, dim=1)], 1).float()
+    buf = torch.full((6 + p.numel() + 58,), float("nan"), device="cuda")
+    view = buf[6:6 + p.numel()].view(p.shape)
+    view.copy_(p)
+    return view
+
+
+def _set_part(p, part, count):
+    p.gn_ab, p.gn_part, p.gn_parts, p.gn_count, p.gn_eps = None, part.data_ptr(), part.shape[1], float(count), 1e-5
+
+
+def _conv(x, wpk, out, out_C, B, C0, H, W, cout, cout_pad, k, tile, dt, wk_order, part=None, count=0, ks=1, **kw):
+    """One ds_conv_igemm launch (stride 1, same size; + ds_conv_splitk_reduce for K slices) with statistics; returns its partials."""
+    p = L.ConvParams(src0=x.data_ptr(), src1=None, C0=C0, C1=0, H=H, W=W, H1=0, W1=0, off_h1=0, off_w1=0, wpk=wpk.data_ptr(), Cout=cout,
+                     cout_pad=cout_pad, KH=k, KW=k, stride=1, pad_h=k // 2, pad_w=k // 2, Ho=H, Wo=W, transposed=0, out=out.data_ptr(), out_C=out_C,
+                     out_c0=0, out_nchw_f32=0, bias=None, gn_ab=None, fold_t1=None, fold_t2=None, ncls=9 if k == 3 else 1, act=L.ACT_NONE, res=None,
+                     stats_part=None, B=B, dtype=dt, tile=tile, wk_order=wk_order)
+    for key, v in kw.items():
+        setattr(p, key, v)
+    if part is not None:
+        _set_part(p, part, count)
+    slab = None
+    if ks > 1:
+        slab = torch.full((ks * B * H * W * ((cout + 7) // 8 * 8),), float("nan"), device="cuda")
+        p.ksplit, p.slab = ks, slab.data_ptr()
+    st = torch.zeros(B, L.load().ds_conv_stats_parts(C.byref(p)), 2, device="cuda")
+    p.stats_part = st.data_ptr()
+    L.call("ds_conv_igemm", C.byref(p), L.current_stream())
+    if ks > 1:
+        L.call("ds_conv_splitk_reduce", C.byref(p), L.current_stream())
+    torch.cuda.synchronize()
+    assert torch.isfinite(out.float()).all() and torch.isfinite(st).all()
+    return st
+
+
+def sweep_gn_partials(fail):
+    """GroupNorm from raw partials, the shapes of tests/test_hip_gn_partials.py: every kernel that reduces gn_part with 1 .. 300 partials
+    (the halo kernel also 64 / 65 / 256 / 257: both sides of its 4 x 64 prefetch) behind an 8-byte-aligned base, every depthwise family and
+    tile instantiation as a producer, and the producer -> consumer chains without ds_gn_finalize."""
+    from diffusynth_amd.engine import split3_weight, to_split_planes
+    from hip_helpers import PackedConv, to_nhwc
+    lib = L.load()
+    st = L.current_stream()
+    bf, f32 = L.DS_BF16, L.DS_F32
+    tdt = {bf: torch.bfloat16, f32: torch.float32}
+    PARTS, PARTS_HALO = (1, 65, 300), (1, 64, 65, 256, 257, 300)
+    vec = lambda tag, n, s=1.0: (1.0 if s == 0 else 0.0) + synth_input(tag, (n,), s or 0.2).cuda()
+
+    # ---- ds_gn_apply: fast form (every channel count, HW below `rows` / ragged / several blocks, the grid cap at B = 64), generic lazy form
+    def gn_apply(dt, B, Cc, HW, res, cbias=False, act=L.ACT_NONE):
+        x = to_nhwc(synth_input("bs_gp_x", (B, Cc, HW, 1)) * 1.5 + 0.7, dt)
+        r = to_nhwc(synth_input("bs_gp_r", (B, Cc, HW, 1)), dt) if res else None
+        cb = synth_input("bs_gp_cb", (B, Cc)).cuda() if cbias else None
+        g, be = vec("bs_gp_g", Cc, 0), vec("bs_gp_be", Cc, 0.3)
+        for parts in PARTS:
+            part = _partials(x, parts)
+            out = torch.full_like(x, float("nan"))
+            p = L.GnApplyParams(x=x.data_ptr(), res=L.ptr(r), out=out.data_ptr(), gn_ab=None, gamma=g.data_ptr(), beta=be.data_ptr(), cbias=L.ptr(cb),
+                                cb_stride=Cc, B=B, HW=HW, C=Cc, G=1, act=act, dtype=dt)
+            p.gn_part, p.gn_parts, p.gn_count, p.gn_eps = part.data_ptr(), parts, float(Cc * HW), 1e-5
+            L.call("ds_gn_apply", C.byref(p), st)
+            torch.cuda.synchronize()
+            assert torch.isfinite(out.float()).all()
+
+    for Cc in (64, 96, 192, 384, 768):
+        for HW in (5, 67, 600):
+            for res in (False, True):
+                gn_apply(bf, 3, Cc, HW, res)
+    gn_apply(bf, 64, 768, 520, True)
+    report("gn_apply from partials, fast form 31 shapes x 3 partial counts", fail)
+    gn_apply(f32, 3, 96, 70, True)
+    gn_apply(bf, 3, 160, 70, False, cbias=True)
+    gn_apply(bf, 3, 96, 70, False, act=L.ACT_SILU)
+    report("gn_apply from partials, generic lazy form 3 shapes x 3 partial counts", fail)
+
+    # ---- generic igemm tiles: 3x3 fold (GELU + residual + statistics), 1x1 fold on two tiles, both dtypes
+    def folded(tag, cout, cin, k, dt, tile):
+        w = synth_input("bs_gp_w%s" % tag, (cout, cin, k, k), 0.05)
+        return PackedConv(w, synth_input("bs_gp_b%d" % cout, (cout,)), dt, tile, gamma=1 + 0.2 * synth_input("bs_gp_g%d" % cin, (cin,)),
+                          beta=0.3 * synth_input("bs_gp_be%d" % cin, (cin,)))
+
+    def fold_kw(pc):
+        return dict(bias=L.ptr(pc.bias), fold_t1=pc.t1.data_ptr(), fold_t2=pc.t2.data_ptr())
+
+    for dt in (f32, bf):
+        for cout, k, (H, W), tiles in ((192, 3, (9, 7), (L.TILE_128x192,)), (384, 1, (8, 16), (L.TILE_128x192, L.TILE_256x96))):
+            x = to_nhwc(synth_input("bs_gp_ix%d" % k, (3, 96, H, W)) * 2 + 0.7, dt)
+            r = to_nhwc(synth_input("bs_gp_ir%d" % k, (3, cout, H, W)), dt)
+            for tile in tiles:
+                pc = folded("i%d" % k, cout, 96, k, dt, tile)
+                for parts in PARTS:
+                    out = torch.full((3, H, W, cout), float("nan"), device="cuda").to(tdt[dt])
+                    _conv(x, pc.w, out, cout, 3, 96, H, W, cout, pc.cout_pad, k, tile, dt, 0, _partials(x, parts), 96 * H * W,
+                          act=L.ACT_GELU if k == 3 else L.ACT_NONE, res=r.data_ptr() if k == 3 else None, **fold_kw(pc))
+        report(f"conv_igemm from partials dtype {dt}", fail)
+
+    # ---- halo kernel, bf16: the three patch widths, GELU + residual + statistics, whole K and K slices
+    HT = L.TILE_HALO3_256x96
+    for (B, cin, H, W), cout in (((3, 96, 8, 64), 192), ((3, 32, 33, 8), 96), ((3, 64, 7, 3), 96)):
+        x = to_nhwc(synth_input("bs_gp_hx%d" % cin, (B, cin, H, W)) * 1.5 + 0.4, bf)
+        r = to_nhwc(synth_input("bs_gp_hr%d" % cin, (B, cout, H, W)), bf)
+        pc = folded("h%d" % cin, cout, cin, 3, bf, HT)
+        for ks in (1, 2, 3):
+            if (cin // 32) % ks:
+                continue
+            for parts in PARTS_HALO:
+                out = torch.full((B, H, W, cout), float("nan"), device="cuda").bfloat16()
+                _conv(x, pc.w, out, cout, B, cin, H, W, cout, pc.cout_pad, 3, HT, bf, 1, _partials(x, parts), cin * H * W, ks, act=L.ACT_GELU,
+                      res=r.data_ptr(), **fold_kw(pc))
+    report("conv3x3_halo3 bf16 from partials, 3 shapes x K slices x 6 partial counts", fail)
+
+    # ---- halo kernel, split precision (hi / lo planes in; planes out + GELU, or fp32 out + residual), two samples per block incl. an odd batch
+    class X3:
+        def __init__(self, tag, cout, cin):
+            w = synth_input("bs_gp_xw%s" % tag, (cout, cin, 3, 3), 0.05)
+            g, be = 1 + 0.2 * synth_input("bs_gp_xg%d" % cin, (cin,)), 0.3 * synth_input("bs_gp_xbe%d" % cin, (cin,))
+            self.cout, self.cin = cout, cin
+            self.pc = PackedConv(split3_weight(w, g), synth_input("bs_gp_xb%d" % cout, (cout,)), bf, HT)
+            self.t1, self.t2 = torch.empty(9 * cout, device="cuda"), torch.empty(9 * cout, device="cuda")
+            wd, gd, bd = w.cuda().contiguous(), g.cuda(), be.cuda()
+            L.call("ds_conv_fold_tables", wd.data_ptr(), self.pc.bias.data_ptr(), gd.data_ptr(), bd.data_ptr(), cout, cin, 3, 3, self.t1.data_ptr(),
+                   self.t2.data_ptr(), st)
+            torch.cuda.synchronize()
+
+        def run(self, planes, B, H, W, split_out, part, ks=1, res=None):
+            cout = self.cout
+            out = torch.full((B, H, W, 2 * cout), float("nan"), device="cuda").bfloat16() if split_out else torch.full((B, H, W, cout), float("nan"), device="cuda")
+            sp = _conv(planes, self.pc.w, out, 2 * cout if split_out else cout, B, 2 * self.cin, H, W, cout, self.pc.cout_pad, 3, HT, bf, 1, part,
+                       self.cin * H * W, ks, bias=self.pc.bias.data_ptr(), fold_t1=self.t1.data_ptr(), fold_t2=self.t2.data_ptr(),
+                       act=L.ACT_GELU if split_out else L.ACT_NONE, res=L.ptr(res), flags=1 | (2 if split_out else 4))
+            return out, sp
+
+    def planes_sum(pl):
+        c = pl.shape[-1] // 2
+        return pl[..., :c].float() + pl[..., c:].float()
+
+    for (B, cin, H, W), cout in (((3, 96, 8, 64), 192), ((3, 96, 16, 8), 192), ((5, 32, 16, 5), 96), ((2, 64, 12, 7), 96)):
+        cv = X3("%d_%d" % (cout, cin), cout, cin)
+        xs = to_split_planes((synth_input("bs_gp_sx%d" % cin, (B, H, W, cin)) * 1.5 + 0.4)).cuda()
+        r = synth_input("bs_gp_sr%d" % cin, (B, H, W, cout)).cuda()
+        for ks in (1, 2, 3):
+            if (cin // 32) % ks:
+                continue
+            for parts in PARTS_HALO:
+                part = _partials(planes_sum(xs), parts)
+                cv.run(xs, B, H, W, True, part, ks)
+                cv.run(xs, B, H, W, False, part, ks, res=r)
+    report("conv3x3_halo3 split precision from partials, 4 shapes x 2 output modes x K slices x 6 partial counts", fail)
+
+    # ---- halo kernel with the fused 1x1 res_conv over two sources
+    B, cin, H, W, cout, c0, c1 = 2, 96, 9, 27, 96, 96, 96
+    pc = folded("rc", cout, cin, 3, bf, HT)
+    rpk = torch.empty(lib.ds_pack_conv_elems(c0 + c1, 1, 1, pc.cout_pad, 0), dtype=torch.bfloat16, device="cuda")
+    wr = synth_input("bs_gp_wr", (cout, c0 + c1, 1, 1), 0.1).cuda().contiguous()
+    pp = L.PackConvParams(w=wr.data_ptr(), gamma=None, dst=rpk.data_ptr(), dtype=bf, Cout=cout, Cin=c0 + c1, cin_pad=c0 + c1, KH=1, KW=1,
+                          cout_pad=pc.cout_pad, transposed=0, k_order=1)
+    L.call("ds_pack_conv_weight", C.byref(pp), st)
+    wall, br = torch.cat([rpk, pc.w]), synth_input("bs_gp_br", (cout,)).cuda()
+    x = to_nhwc(synth_input("bs_gp_rcx", (B, cin, H, W)) * 1.5 + 0.4, bf)
+    x0, x1 = to_nhwc(synth_input("bs_gp_rc0", (B, c0, H, W)), bf), to_nhwc(synth_input("bs_gp_rc1", (B, c1, H - 2, W - 1)), bf)
+    for parts in PARTS_HALO:
+        out = torch.full((B, H, W, cout), float("nan"), device="cuda").bfloat16()
+        _conv(x, wall, out, cout, B, cin, H, W, cout, pc.cout_pad, 3, HT, bf, 1, _partials(x, parts), cin * H * W, res_src0=x0.data_ptr(),
+              res_src1=x1.data_ptr(), res_C0=c0, res_C1=c1, res_H1=H - 2, res_W1=W - 1, res_off_h1=1, res_off_w1=0, res_steps=(c0 + c1) // 32,
+              res_bias=br.data_ptr(), **fold_kw(pc))
+    report("conv3x3_halo3 + fused res_conv from partials", fail)
+
+    # ---- fused attention, both generations, and its split-precision form; then the tail without ds_gn_finalize (partials of y -> gn_apply)
+    def attention(Cc, H, W, cond, x3):
+        B, N = 3, H * W
+        dt = f32 if x3 else bf
+        x = to_nhwc(synth_input("bs_gp_ax%d" % Cc, (B, Cc, H, W)) * 1.3 + 0.6, dt)
+        wq, wo = synth_input("bs_gp_awq%d" % Cc, (384, Cc), Cc ** -0.5).cuda(), synth_input("bs_gp_awo%d" % Cc, (Cc, 128), 0.09).cuda()
+        g, be, bo = vec("bs_gp_ag", Cc, 0), vec("bs_gp_abe", Cc, 0.3), vec("bs_gp_abo", Cc, 0.3)
+        go, bo2 = vec("bs_gp_ago", Cc, 0), vec("bs_gp_abo2", Cc, 0.3)
+        lq = synth_input("bs_gp_alq", (B, 128)).cuda() if cond else None
+        t1, t2 = torch.empty(384, device="cuda"), torch.empty(384, device="cuda")
+        L.call("ds_conv_fold_tables", wq.data_ptr(), None, g.data_ptr(), be.data_ptr(), 384, Cc, 1, 1, t1.data_ptr(), t2.data_ptr(), st)
+        ctx = torch.empty(B * 4 * 1024, device="cuda")
+        for parts in PARTS:
+            part = _partials(x, parts)
+            y = torch.full((B, H, W, Cc), float("nan"), device="cuda").to(tdt[dt])
+            if x3:
+                whl = torch.empty(2 * 384 * Cc, dtype=torch.bfloat16, device="cuda")
+                L.call("ds_pack_attn_x3", wq.data_ptr(), g.data_ptr(), whl.data_ptr(), Cc, st)
+                runs = []
+                for nseg in sorted({3, lib.ds_attn_x3_segments(B, N, Cc)}):
+                    scratch = (torch.empty(lib.ds_linattn_part_floats(B, 4, nseg), device="cuda"),
+                               torch.empty(lib.ds_attn_x3_qplane_bytes(B, N), dtype=torch.uint8, device="cuda"),
+                               torch.empty(lib.ds_attn_x3_mfold_bytes(B, Cc), dtype=torch.uint8, device="cuda"))
+                    p = L.AttnX3Params(x=x.data_ptr(), B=B, N=N, C=Cc, nseg=nseg, wqkv_hl=whl.data_ptr(), t1=t1.data_ptr(), t2=t2.data_ptr(), gn_ab=None,
+                                       label_q=L.ptr(lq), lq_stride=128, scale=32 ** -0.5, part=scratch[0].data_ptr(), ctx=ctx.data_ptr(),
+                                       qplanes=scratch[1].data_ptr(), mfold=scratch[2].data_ptr(), wout=wo.data_ptr(), bias_out=bo.data_ptr(),
+                                       y=y.data_ptr(), stats_part=None)
+                    runs.append((p, "ds_attn_x3", lib.ds_attn_x3_stats_parts, scratch))
+            else:
+                wq16, wo16 = torch.empty(384 * Cc, dtype=torch.bfloat16, device="cuda"), torch.empty(Cc * 128, dtype=torch.bfloat16, device="cuda")
+                L.call("ds_pack_attn_fused", wq.data_ptr(), g.data_ptr(), wo.data_ptr(), wq16.data_ptr(), wo16.data_ptr(), Cc, st)
+                runs = []
+                for gen in (1, 2):
+                    scratch = (torch.empty(lib.ds_linattn_part_floats(B, 4, 3), device="cuda"),
+                               torch.empty(B * Cc * 128, dtype=torch.bfloat16, device="cuda") if gen == 2 else None)
+                    p = L.AttnFusedParams(x=x.data_ptr(), B=B, N=N, C=Cc, nseg=3, wqkv=wq16.data_ptr(), t1=t1.data_ptr(), t2=t2.data_ptr(), gn_ab=None,
+                                          label_q=L.ptr(lq), lq_stride=128, scale=32 ** -0.5, part=scratch[0].data_ptr(), ctx=ctx.data_ptr(),
+                                          wout_perm=wo16.data_ptr(), bias_out=bo.data_ptr(), y=y.data_ptr(), stats_part=None)
+                    p.mfold, p.gen = L.ptr(scratch[1]), gen
+                    runs.append((p, "ds_attn_fused", lib.ds_attn_fused_stats_parts, scratch))
+            for p, name, nparts, _scratch in runs:
+                _set_part(p, part, Cc * N)
+                sp = torch.zeros(B, nparts(C.byref(p)), 2, device="cuda")
+                p.stats_part = sp.data_ptr()
+                L.call(name + "_context", C.byref(p), st)
+                L.call(name + "_output", C.byref(p), st)
+                out = torch.full_like(y, float("nan"))
+                gp = L.GnApplyParams(x=y.data_ptr(), res=x.data_ptr(), out=out.data_ptr(), gn_ab=None, gamma=go.data_ptr(), beta=bo2.data_ptr(),
+                                     cbias=None, cb_stride=0, B=B, HW=N, C=Cc, G=1, act=L.ACT_NONE, dtype=dt)
+                gp.gn_part, gp.gn_parts, gp.gn_count, gp.gn_eps = sp.data_ptr(), sp.shape[1], float(Cc * N), 1e-5
+                L.call("ds_gn_apply", C.byref(gp), st)
+                torch.cuda.synchronize()
+                assert torch.isfinite(y.float()).all() and torch.isfinite(out.float()).all()
+
+    for x3 in (False, True):
+        for Cc, (H, W), cond in ((96, (5, 10), False), (192, (33, 32), True), (384, (8, 6), True)):
+            attention(Cc, H, W, cond, x3)
+        report("attn_%s from partials + gn_apply from the partials of y, 3 shapes x 3 partial counts" % ("x3" if x3 else "fused gen 1 / 2"), fail)
+
+    # ---- depthwise 7x7: every family and tile instantiation (two sources with pad offsets, time bias, B = 3)
+    def dwconv(dt, c0, c1, H, W, wexp=False, out_split=0, strip=0):
+        B, Cc = 3, c0 + c1
+        x0 = to_nhwc(synth_input("bs_gp_d0", (B, c0, H, W)) * 1.5 + 0.5, dt)
+        x1 = to_nhwc(synth_input("bs_gp_d1", (B, c1, H - 1, W - 3)), dt) if c1 else None
+        w = synth_input("bs_gp_dw%d" % Cc, (Cc, 1, 7, 7), 0.2).cuda().contiguous()
+        wt = torch.empty(49 * Cc, device="cuda")
+        L.call("ds_pack_dw_weight", w.data_ptr(), Cc, wt.data_ptr(), st)
+        we = None
+        if wexp:
+            we = torch.empty(Cc * 6 * 64 * 8, dtype=torch.bfloat16, device="cuda")
+            L.call("ds_pack_dw_weight_mfma", w.data_ptr(), Cc, we.data_ptr(), st)
+        b, tb = synth_input("bs_gp_db", (Cc,)).cuda(), synth_input("bs_gp_dtb", (B, Cc + 12)).cuda()
+        out = torch.full((B, H, W, 2 * Cc), float("nan"), device="cuda").bfloat16() if out_split else torch.full((B, H, W, Cc), float("nan"), device="cuda").to(tdt[dt])
+        p = L.DwconvParams(src0=x0.data_ptr(), src1=L.ptr(x1), C0=c0, C1=c1, H=H, W=W, H1=(H - 1 if c1 else 0), W1=(W - 3 if c1 else 0), off_h1=0,
+                           off_w1=1, wt=wt.data_ptr(), bias=b.data_ptr(), tbias=tb.data_ptr() + 4 * 5, tb_stride=Cc + 12, out=out.data_ptr(),
+                           stats_part=None, B=B, dtype=dt, wexp=L.ptr(we), out_split=out_split, strip=strip)
+        sp = torch.zeros(B, lib.ds_dwconv_stats_parts(C.byref(p)), 2, device="cuda")
+        p.stats_part = sp.data_ptr()
+        L.call("ds_dwconv7", C.byref(p), st)
+        torch.cuda.synchronize()
+        assert torch.isfinite(out.float()).all() and torch.isfinite(sp).all()
+        return out, sp
+
+    dwconv(bf, 40, 0, 10, 9)
+    dwconv(f32, 20, 0, 10, 9)
+    for W in (7, 12, 40):
+        dwconv(bf, 32, 64, 19, W)
+        dwconv(f32, 48, 0, 19, W)
+        dwconv(f32, 16, 32, 19, W)
+    for H, W in ((16, 8), (19, 24)):
+        for split in (0, 1):
+            dwconv(f32, 96, 0, H, W, out_split=split)
+    dwconv(f32, 96, 0, 64, 16, out_split=1, strip=1)
+    dwconv(f32, 32, 64, 70, 37, out_split=1, strip=1)
+    dwconv(bf, 96, 192, 40, 16, wexp=True)
+    dwconv(bf, 96, 192, 37, 70, wexp=True)
+    report("dwconv7 family matrix: direct, 8 / 16 / 32-wide tiles (bf16, fp32 NV = 4 / 8), strip, matrix cores", fail)
+
+    # ---- ConvNeXt chains without ds_gn_finalize: depthwise -> 3x3 (GELU, statistics) -> 3x3 + residual, partials handed on raw
+    c1x, c2x = X3("ch1", 192, 96), X3("ch2", 96, 192)
+    for (H, W), strip in (((16, 8), 0), ((19, 24), 0), ((64, 16), 1)):
+        pl0, sp0 = dwconv(f32, 96, 0, H, W, out_split=1, strip=strip)
+        pl1, sp1 = c1x.run(pl0, 3, H, W, True, sp0)
+        c1x.run(pl0, 3, H, W, True, sp0, ks=3)
+        c2x.run(pl1, 3, H, W, False, sp1, res=synth_input("bs_gp_chr", (3, H, W, 96)).cuda())
+    H, W = 37, 70
+    y0, sp0 = dwconv(bf, 96, 0, H, W, wexp=True)
+    p1, p2 = folded("cb1", 192, 96, 3, bf, HT), folded("cb2", 96, 192, 3, bf, HT)
+    y1 = torch.full((3, H, W, 192), float("nan"), device="cuda").bfloat16()
+    sp1 = _conv(y0, p1.w, y1, 192, 3, 96, H, W, 192, p1.cout_pad, 3, HT, bf, 1, sp0, 96 * H * W, act=L.ACT_GELU, **fold_kw(p1))
+    y2 = torch.full((3, H, W, 96), float("nan"), device="cuda").bfloat16()
+    r = to_nhwc(synth_input("bs_gp_chrb", (3, 96, H, W)), bf)
+    _conv(y1, p2.w, y2, 96, 3, 192, H, W, 96, p2.cout_pad, 3, HT, bf, 1, sp1, 192 * H * W, res=r.data_ptr(), **fold_kw(p2))
+    report("chains dwconv -> conv3x3 -> conv3x3 on raw partials (split precision: tile, two samples per block, strip; bf16: matrix cores)", fail)
+
+
 def main():
     lib = L.load()
     assert "bounds" in L.lib_path(), L.lib_path()
     fail = []
+    if "--only-gn-partials" in sys.argv:
+        sweep_gn_partials(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
     if "--only-ui-images" in sys.argv:
         sweep_ui_images(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
@@ -155,6 +446,8 @@ def main():
     sweep_ui_images(fail)
     # 5) the arranger's audio stage
     sweep_arranger(fail)
+    # 6) GroupNorm from raw partials in every kernel that reduces them, the depthwise families, the chains without ds_gn_finalize
+    sweep_gn_partials(fail)
     if fail:
         print("BOUNDS VIOLATIONS", fail)
         sys.exit(1)
