@@ -1,43 +1,35 @@
-// 3x3 stride-1 pad-1 convolution, bf16, LDS input halo — the conv3x3_halo2 pipeline on 16x16x32 MFMAs (gfx950).
+// 3x3 stride-1 pad-1 convolution, bf16 (and the split-precision tier on bf16 planes), from an input halo in LDS on 16x16x32 MFMAs (gfx950).
 //
-// Same block tile (256 px x 96 ch, 4 waves of 64 px x 96 ch, two blocks per CU), same data flow and the same hand-placed
-// step as conv3x3_halo2.hip (chunk-major weights through a 3-slot register ring into a 3-buffer LDS ring, input halo of a
-// 32-channel chunk double-buffered in LDS, buffer loads with scalar offsets, counted lgkmcnt + raw s_barrier, fused 1x1
-// res_conv steps in front of the nine-tap chunks).  What differs:
-//
-//   * v_mfma_f32_16x16x32_bf16 instead of 32x32x16.  halo2's K loop is pipe-bound (92-95 % MFMA-busy) at a clock the chip
-//     lowers to 1.5 GHz under it; the 16x16x32 shape sustains a higher clock for the same FLOPs (MI355X_MICROARCH.md:
-//     1.12-1.14x with operands re-read from LDS).  One MFMA consumes the whole 32-channel chunk of a tap, so a step is
-//     24 MFMAs of 16 cycles on 4 pixel fragments x 6 weight fragments — ten ds_read_b128 per step, as before.
-//   * LDS images with 64-byte rows (no pad) and an XOR swizzle instead of the 80-byte pitch: a 16-row x 64-byte fragment
-//     read puts lanes {0-3, 12-15} of one 16-byte column and lanes {4-11} of the next into one bank group, which any odd
-//     pitch makes a 2-way conflict.  Halo pixel hp keeps its 16-byte quarters at (q ^ 2*bit2(hp)); halo rows are padded
-//     to a multiple of 4 pixels so that a tap shift changes bit2 by a per-lane constant: a fragment address is
-//     (base_i ^ mask(tap)) + immediate, one v_xor per fragment read.  Weight rows are swizzled by W_SWZ(row) = (-((row >> 3) & 3)) & 3 and
-//     MFMA row m of weight fragment j is channel 24*(m>>2) + 4*j + (m&3): lane group g then accumulates channels
-//     24g .. 24g+23 of its pixel — 48 contiguous output bytes per lane, no cross-lane permute in the epilogue (halo2 needs
-//     one v_permlane32_swap + s_nop per accumulator register).  All reads and writes are conflict-free (checked by
-//     enumeration for the three tile shapes, every tap and every lane group).
-//   * the kernel is templated on the tile width (32 / 16 / 8 px): halo pitch, tap offsets and trip counts are immediates.
+//   * Block tile 256 px x 96 ch, 4 waves of 64 px x 96 ch (4 pixel fragments x 6 weight fragments of 16 x 16), two blocks per CU.  The kernel
+//     is templated on the tile width (32 / 16 / 8 px, halo_twl): halo pitch, tap offsets and trip counts are immediates.
+//   * K is walked in 32-channel chunks of nine taps.  The input halo of a chunk ((TH + 2) x (TW + 2) pixels) is double-buffered in LDS and
+//     refilled in two halves during the previous chunk; the chunk-major weights [chunk][tap][cout_pad][32] travel through a 3-slot register
+//     ring into a 3-buffer LDS ring, one 96 x 32 tile per step.  Buffer loads with scalar offsets: an offset with bit 31 set (outside the
+//     image, a pad column) is beyond the buffer and returns zeros without touching memory.
+//   * One step = one tap: v_mfma_f32_16x16x32_bf16 consumes the whole 32-channel chunk of a tap, so a step is 24 MFMAs of 16 cycles and ten
+//     ds_read_b128 (4 pixel + 6 weight fragments, read one step ahead).  The LDS / VMEM instructions are placed one per MFMA gap
+//     (sched_group_barrier); a step ends in a counted `s_waitcnt lgkmcnt(10)` + raw s_barrier that retires the step's LDS writes and leaves
+//     the next step's reads in flight (tests/test_isa_schedule_cpu.py checks the emitted ISA).  The 16x16x32 shape sustains a higher clock
+//     than 32x32x16 for the same FLOPs (MI355X_MICROARCH.md: 1.12-1.14x with operands re-read from LDS).
+//   * LDS images with 64-byte rows (no pad) and an XOR swizzle: a 16-row x 64-byte fragment read puts lanes {0-3, 12-15} of one 16-byte
+//     column and lanes {4-11} of the next into one bank group, which any odd pitch makes a 2-way conflict.  Halo pixel hp keeps its 16-byte
+//     quarters at (q ^ 2*bit2(hp)); halo rows are padded to a multiple of 4 pixels so that a tap shift changes bit2 by a per-lane constant: a
+//     fragment address is (base_i ^ mask(tap)) + immediate, one v_xor per fragment read.  Weight rows are swizzled by W_SWZ(row).  All
+//     reads and writes are conflict-free (checked by enumeration for the three tile shapes, every tap and every lane group).
+//   * MFMA row m of weight fragment j is channel EPI_CH(j) + W_ROW0(m) (conv_halo3_common.hpp): lane group g accumulates three runs of 8
+//     consecutive channels of its pixel, 64 contiguous output bytes per pixel and store instruction, no cross-lane permute in the epilogue.
+//   * Around the K loop: the GroupNorm fold of the input (statistics reduced from the producer's partials in the prologue, shift table
+//     in LDS), a fused 1x1 res_conv as one-step chunks in front of the nine-tap chunks, K slices for small batches (raw fp32 partial sums to
+//     a slab, ds_conv_splitk_reduce finishes them), and the register epilogues of conv_halo3_common.hpp.
 #include "common.hpp"
 #ifndef DS_STAMP
 #define DS_STAMP 0   // diagnostic build: per-wave s_memtime / s_memrealtime stamps around prologue, K loop and epilogue -> p.slab (8 longs per wave)
-#endif
-#ifndef DS_NGROUP
-#define DS_NGROUP 2   // N-blocks per group of the block order (0: N-block fastest over the whole layer, the order up to r03)
 #endif
 #if DS_BOUNDS
 void ds_conv_bounds_table(const ds_conv_params& p, int kernel, int stats_parts, ds_bx* out);   // conv_igemm.hip
 #endif
 
 #include "conv_halo3_common.hpp"
-
-#ifndef DS_EPI_ROWS_NORES
-#define DS_EPI_ROWS_NORES 0      // (with the 24-channel lane map the staged form won 1..5 % here; with 64-byte runs from the registers it does not)
-#endif
-#ifndef DS_EPI_ROWS
-#define DS_EPI_ROWS 1      // line-sized stores through an LDS tile (halo3_epilogue_rows); 0: the register-only epilogue (A/B)
-#endif
 
 namespace {
 
@@ -82,27 +74,22 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
     // MFMA, which sets the clock this loop runs at.)
     const int gx = gridDim.x, gy = gridDim.y, nwg = gx * gy * gridDim.z;
     int wid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-#ifndef DS_HALO3_NOXCD
     if ((nwg & 7) == 0) wid = (wid & 7) * (nwg >> 3) + (wid >> 3);
-#endif
-#if DS_NGROUP
-    // r04: N-blocks in groups of DS_NGROUP (2) fastest, then the tile and the sample, then the N-group — the blocks resident on an XCD at one
+    // r04: N-blocks in groups of NGROUP (2) fastest, then the tile and the sample, then the N-group — the blocks resident on an XCD at one
     // time then stream the SAME two N-blocks' weights (shared through its L2) instead of all of the layer's: fabric reads of the 64 x 16 /
     // 32 x 8 launches 2.44 -> 1.84 / 0.61 -> 0.45 GB (PMC FETCH_SIZE), step time unchanged (717.7 vs 717.4 steps/s, same box; groups of 1
     // lose the input's L2 reuse: -0.7 %)
+    constexpr int NGROUP = 2;
     int by, bxz;
-    if (gy % DS_NGROUP == 0 && gy > DS_NGROUP) {
-        const int lo = wid % DS_NGROUP, t = wid / DS_NGROUP, nxz = gx * (int)gridDim.z;
+    if (gy % NGROUP == 0 && gy > NGROUP) {
+        const int lo = wid % NGROUP, t = wid / NGROUP, nxz = gx * (int)gridDim.z;
         bxz = t % nxz;
-        by = (t / nxz) * DS_NGROUP + lo;
+        by = (t / nxz) * NGROUP + lo;
     } else {
         by = wid % gy;
         bxz = wid / gy;
     }
     const int bx = bxz % gx, bz = bxz / gx;
-#else
-    const int by = wid % gy, bxz = wid / gy, bx = bxz % gx, bz = bxz / gx;
-#endif
     const int th = bx / tiles_w, tw = bx - th * tiles_w;
     const int h0 = th * TH, w0 = tw * TW;
     // split-K (small batches at the small-spatial levels: too few blocks for 256 CUs): blockIdx.z = sample * ksplit + K slice; a slice
@@ -212,17 +199,12 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
     };
     auto store_halo = [&](auto bufc, auto halfc) { store_halo_from(rh, bufc, halfc); };
 
-    // ---- per-lane fragment bases.  Pixel of (tile i, lane m): tile-local (row, col)
-    auto tile_rc = [&](int i, int& row_l, int& col_l) {
-        if constexpr (TWL == 5) { row_l = 2 * wave + (i >> 1); col_l = 16 * (i & 1) + m; }
-        else if constexpr (TWL == 4) { row_l = 4 * wave + i; col_l = m; }
-        else { row_l = 8 * wave + i + 4 * (m >> 3); col_l = m & 7; }      // rows (i, i + 4): conflict-free with the 12-pixel pitch
-    };
+    // ---- per-lane fragment bases.  Pixel of (tile i, lane m): tile-local (row, col) = halo_tile_rc
     int xb[XT];                  // address of tap (0, 0) in halo buffer 0
 #pragma unroll
     for (int i = 0; i < XT; ++i) {
         int row_l, col_l;
-        tile_rc(i, row_l, col_l);
+        halo_tile_rc<TWL>(wave, i, m, row_l, col_l);
         const int hp0 = (row_l + (PAIR ? 2 * (row_l >> 4) : 0)) * HCP + col_l;      // (PAIR: the second sample's rows sit two halo rows lower)
         xb[i] = OFF_H + hp0 * PSTR + ((q ^ (((hp0 >> 2) & 1) << 1)) << 4);
     }
@@ -277,26 +259,11 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
     GnPartialLoads gnl;
     const bool raw = ksplit > 1;                     // K slice: zero shift table, factor 1, no statistics
     if (p.gn_part && !raw) gn_partials_issue(p.gn_part, p.gn_parts, b, gnl);
-    const bool fold = !raw && (p.gn_ab != nullptr || p.gn_part != nullptr);
+    const bool fold = !raw && CONV_FOLD(p);
     const int ncls = fold ? p.ncls : 1;
     constexpr int ST_IT = (10 * BN + NT - 1) / NT;     // 4 shift-table entries per thread at most (row 9 stays zero)
+#if !DS_BOUNDS      // (the diagnostic build fills the table from plain, checked loads once the mean is known: below)
     float t1v[ST_IT], t2v[ST_IT], rbv[ST_IT];
-#if DS_BOUNDS
-#pragma unroll
-    for (int k = 0; k < ST_IT; ++k) {
-        const int e = tid + k * NT, cls = e / BN, n = n0 + e - cls * BN;
-        t1v[k] = 0.f;
-        t2v[k] = 0.f;
-        if (e < ncls * BN && n < p.Cout) {
-            if (fold) {
-                t1v[k] = DS_LD(float, p.fold_t1 + cls * p.Cout + n, DS_BX_T1);
-                t2v[k] = DS_LD(float, p.fold_t2 + cls * p.Cout + n, DS_BX_T2);
-            } else if (p.bias && !raw) t1v[k] = DS_LD(float, p.bias + n, DS_BX_BIAS);
-            if (NR > 0 && p.res_bias) t1v[k] += DS_LD(float, p.res_bias + n, DS_BX_AUX2);
-        }
-        rbv[k] = 0.f;
-    }
-#else
     // Range-checked buffer loads with arithmetic out-of-range offsets (bit 31): written as `if (valid) t = load` every entry became an
     // exec-masked region with its own s_waitcnt vmcnt(0) — eight serial L2 round trips in front of the halo request.
     {
@@ -356,11 +323,15 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
             reinterpret_cast<float*>(smem + G::LDS)[1] = am1;
         }
     }
+#if DS_BOUNDS      // (a K slice: zeros)
+    conv_shift_table<BN, 10, NT>(raw ? conv_kslice_view(p) : p, fold, n0, gn_am, NR > 0 ? p.res_bias : nullptr, shl);
+#else
 #pragma unroll
     for (int k = 0; k < ST_IT; ++k) {
         const int e = tid + k * NT;
         if (e < 10 * BN) shl[e] = (t1v[k] + rbv[k]) - gn_am * t2v[k];      // entries beyond the ncls real rows are zeros
     }
+#endif
     const long st_p2 = DS_STAMP ? __builtin_amdgcn_s_memrealtime() : 0;    // statistics reduced, shift table written
 #pragma unroll
     for (int i = 0; i < XT; ++i)
@@ -569,9 +540,7 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
         }
     }
     // ---- epilogue
-    auto coord = [&](int i) {
-        int row_l, col_l;
-        tile_rc(i, row_l, col_l);
+    auto at = [&](int row_l, int col_l) {
         ConvCoord c;
         if constexpr (PAIR) {                                           // rows 0 .. 15: sample b, rows 16 .. 31: sample b + 1 (pix counts through both)
             const int smp = row_l >> 4;
@@ -587,26 +556,8 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
         c.pix = c.ho * p.W + c.wo;
         return c;
     };
-    auto coord2 = [&](int i, int mm) {                                  // pixel (tile i, lane mm): the contiguous side of halo3_epilogue_rows
-        int row_l, col_l;
-        if constexpr (TWL == 5) { row_l = 2 * wave + (i >> 1); col_l = 16 * (i & 1) + mm; }
-        else if constexpr (TWL == 4) { row_l = 4 * wave + i; col_l = mm; }
-        else { row_l = 8 * wave + i + 4 * (mm >> 3); col_l = mm & 7; }
-        ConvCoord c;
-        if constexpr (PAIR) {
-            const int smp = row_l >> 4;
-            c.ho = row_l & 15;
-            c.wo = w0 + col_l;
-            c.ok = c.ho < p.H && c.wo < p.W && (!smp || has2);
-            c.pix = (smp * p.H + c.ho) * p.W + c.wo;
-            return c;
-        }
-        c.ho = h0 + row_l;
-        c.wo = w0 + col_l;
-        c.ok = c.ho < p.H && c.wo < p.W;
-        c.pix = c.ho * p.W + c.wo;
-        return c;
-    };
+    auto coord2 = [&](int i, int mm) { int row_l, col_l; halo_tile_rc<TWL>(wave, i, mm, row_l, col_l); return at(row_l, col_l); };      // pixel (tile i, lane mm)
+    auto coord = [&](int i) { return coord2(i, m); };
     char* const stage = smem + OFF_H + wave * EPI_F32_WAVE;              // (both halo buffers are dead: 4 x 6400 B of their 2 x HB)
     static_assert(4 * EPI_F32_WAVE <= 2 * G::HB, "the staging tiles fit the halo buffers");
     float s1 = 0.f, s2 = 0.f;
@@ -622,22 +573,9 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
     if constexpr (PAIR) {
         // (its factor and mean come back from the LDS slot the prologue parked them in)
         const float gn_a1 = reinterpret_cast<const float*>(smem + G::LDS)[0], gn_am1 = reinterpret_cast<const float*>(smem + G::LDS)[1];
-        const bool fold1 = fold;
         float* const shl1 = reinterpret_cast<float*>(smem + OFF_H + 4 * EPI_F32_WAVE);
         static_assert(4 * EPI_F32_WAVE + SHL_BYTES <= 2 * G::HB, "the second shift table fits the halo buffers too");
-        const int ncls1 = ncls, cout1 = p.Cout;
-#pragma unroll
-        for (int k = 0; k < ST_IT; ++k) {
-            const int e = tid + k * NT, cls = e / BN, n = n0 + e - cls * BN;
-            float t1 = 0.f, t2 = 0.f;
-            if (e < ncls1 * BN && n < cout1) {
-                if (fold1) {
-                    t1 = DS_LD(float, p.fold_t1 + cls * cout1 + n, DS_BX_T1);
-                    t2 = DS_LD(float, p.fold_t2 + cls * cout1 + n, DS_BX_T2);
-                } else if (p.bias) t1 = DS_LD(float, p.bias + n, DS_BX_BIAS);
-            }
-            if (e < 10 * BN) shl1[e] = t1 - gn_am1 * t2;
-        }
+        conv_shift_table<BN, 10, NT>(p, fold, n0, gn_am1, nullptr, shl1);
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(wave) >= 2) {      // (wave-uniform by construction: the table pointer and the factor stay scalar)
             shl_w = shl1;
@@ -646,38 +584,19 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
         b_e = b >> 1;
         outHW_e = 2 * outHW;
     }
-    if constexpr (HP) {
-      if (raw) {                             // K slice of a split-precision launch: raw fp32 partial sums -> slab[kz][b][pixel][roundup(Cout, 8)]
-        ds_conv_params q = p;
-        q.out = p.slab;
-        q.out_C = (p.Cout + 7) / 8 * 8;
-        q.out_c0 = 0;
-        q.gn_ab = nullptr;
-        q.gn_part = nullptr;
-        q.res = nullptr;
-        halo3_epilogue_hp<DS_ACT_NONE, 2, false>(q, acc, kz * p.B + b, n0, outHW, shl, coord, s1, s2, 1.0f, lane);
-      } else
+    if (raw) {                               // K slice (either tier): raw fp32 partial sums -> slab[kz][b][pixel][roundup(Cout, 8)]
+        halo3_epilogue_hp<DS_ACT_NONE, 2>(conv_kslice_view(p), acc, kz * p.B + b, n0, outHW, shl, coord, s1, s2, 1.0f, lane);
+    } else if constexpr (HP) {
       if (out_mode == 1) {                   // split bf16 planes (conv1 of a block in the split-precision tier: GELU, no residual)
-        if (p.act == DS_ACT_GELU) halo3_epilogue_hp<DS_ACT_GELU, 1, false>(p, acc, b_e, n0, outHW_e, shl_w, coord, s1, s2, ga_w, lane);
-        else halo3_epilogue_hp<DS_ACT_NONE, 1, false>(p, acc, b_e, n0, outHW_e, shl_w, coord, s1, s2, ga_w, lane);
+        if (p.act == DS_ACT_GELU) halo3_epilogue_hp<DS_ACT_GELU, 1>(p, acc, b_e, n0, outHW_e, shl_w, coord, s1, s2, ga_w, lane);
+        else halo3_epilogue_hp<DS_ACT_NONE, 1>(p, acc, b_e, n0, outHW_e, shl_w, coord, s1, s2, ga_w, lane);
       } else if (out_mode == 2) {          // fp32 (+ fp32 residual): conv2
-        if (p.res && DS_EPI_ROWS) halo3_epilogue_rows_f32<true, true>(p, acc, b_e, n0, outHW_e, shl_w, coord, coord2, stage, s1, s2, ga_w, lane);
-        else if (DS_EPI_ROWS) halo3_epilogue_rows_f32<true, false>(p, acc, b_e, n0, outHW_e, shl_w, coord, coord2, stage, s1, s2, ga_w, lane);
-        else if (p.res) halo3_epilogue_hp<DS_ACT_NONE, 2, true>(p, acc, b_e, n0, outHW_e, shl_w, coord, s1, s2, ga_w, lane);
-        else halo3_epilogue_hp<DS_ACT_NONE, 2, false>(p, acc, b_e, n0, outHW_e, shl_w, coord, s1, s2, ga_w, lane);
+        if (p.res) halo3_epilogue_rows_f32<true, true>(p, acc, b_e, n0, outHW_e, shl_w, coord, coord2, stage, s1, s2, ga_w, lane);
+        else halo3_epilogue_rows_f32<true, false>(p, acc, b_e, n0, outHW_e, shl_w, coord, coord2, stage, s1, s2, ga_w, lane);
       } else {                             // split input, bf16 output
         if (p.act == DS_ACT_GELU) halo3_epilogue<DS_ACT_GELU, true, false>(p, acc, b_e, n0, outHW_e, shl_w, coord, s1, s2, ga_w, lane);
         else halo3_epilogue<DS_ACT_NONE, true, false>(p, acc, b_e, n0, outHW_e, shl_w, coord, s1, s2, ga_w, lane);
       }
-    } else
-    if (raw) {                               // fp32 partial sums of this K slice -> slab[kz][b][pixel][roundup(Cout, 8)]
-        ds_conv_params q = p;
-        q.out = p.slab;
-        q.out_C = (p.Cout + 7) / 8 * 8;
-        q.out_c0 = 0;
-        q.gn_ab = nullptr;
-        q.gn_part = nullptr;
-        halo3_epilogue_hp<DS_ACT_NONE, 2, false>(q, acc, kz * p.B + b, n0, outHW, shl, coord, s1, s2, 1.0f, lane);
     } else
     // (the border class costs a few selects per pixel tile: always computed; instantiations = activation x residual)
     if (p.act == DS_ACT_GELU) {
@@ -692,13 +611,8 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
     } else {
         // with a residual the line-sized form wins 5-7 % on the 256x64 / 128x32 layers (its residual loads are whole lines too); without one the
         // register-only epilogue is 0.6 % faster (same-box A/B, profiles/r03_epilogue_rows_ab.txt)
-        if (p.res && DS_EPI_ROWS) halo3_epilogue_rows<DS_ACT_NONE, true, true>(p, acc, b, n0, outHW, shl, coord, coord2, stage, s1, s2, gn_a, lane);
-        else if (p.res) halo3_epilogue<DS_ACT_NONE, true, true>(p, acc, b, n0, outHW, shl, coord, s1, s2, gn_a, lane);
-#if DS_EPI_ROWS_NORES
-        else halo3_epilogue_rows<DS_ACT_NONE, true, false>(p, acc, b, n0, outHW, shl, coord, coord2, stage, s1, s2, gn_a, lane);
-#else
+        if (p.res) halo3_epilogue_rows<DS_ACT_NONE, true, true>(p, acc, b, n0, outHW, shl, coord, coord2, stage, s1, s2, gn_a, lane);
         else halo3_epilogue<DS_ACT_NONE, true, false>(p, acc, b, n0, outHW, shl, coord, s1, s2, gn_a, lane);
-#endif
     }
     long st_e2 = 0, st_e3 = 0;
     if constexpr (DS_STAMP) {
@@ -734,17 +648,11 @@ __global__ __launch_bounds__(NT, PAIR ? 1 : DS_MINBLK) DS_VGPR_ATTR void conv3x3
     }
 }
 
-int halo3_twl(int W) {
-    int twl = 3;
-    while ((1 << twl) < W && twl < 5) ++twl;
-    return twl;
-}
-
 }  // namespace
 
 // statistics partials of a whole-K launch: one per block (pixel tile x N-block)
 int ds_conv3x3_halo3_parts(const ds_conv_params* p) {
-    const int twl = halo3_twl(p->W), TW = 1 << twl, TH = BM >> twl;
+    const int twl = halo_twl(p->W), TW = 1 << twl, TH = BM >> twl;
     return ((p->H + TH - 1) / TH) * ((p->W + TW - 1) / TW) * (p->cout_pad / BN);
 }
 
@@ -780,7 +688,7 @@ int ds_conv3x3_halo3_launch(const ds_conv_params* p, hipStream_t st) {
                    (long long)(nchunks * 9 + p->res_steps) * p->cout_pad * 64 < (1ll << 31),
                "conv3x3_halo3: one sample / the packed weights must stay below 2 GiB (32-bit buffer offsets)");
     DS_REQUIRE((long long)p->H * p->W * p->out_C * (out_mode == 2 ? 4 : 2) < (1ll << 31), "conv3x3_halo3: one output sample must stay below 2 GiB (32-bit buffer offsets)");
-    const int twl = halo3_twl(p->W), TW = 1 << twl, TH = BM >> twl;
+    const int twl = halo_twl(p->W), TW = 1 << twl, TH = BM >> twl;
     // r05: two samples per block where an image fills at most half of the 8 x 32 tile (the deepest level at 128 x 64 latents: 16 x 8)
     const bool pair = p->flags != 0 && twl == 3 && 2 * p->H <= TH && p->W <= TW && p->ksplit <= 1 && !p->res_steps && p->B >= 2;
     dim3 grid(((p->H + TH - 1) / TH) * ((p->W + TW - 1) / TW), p->cout_pad / BN, pair ? (p->B + 1) / 2 : p->B * (p->ksplit > 1 ? p->ksplit : 1));

@@ -9,9 +9,6 @@
 // (sum, sumsq) partials are taken from the exact stored values.
 #pragma once
 #include "common.hpp"
-#ifndef DS_ABLATE
-#define DS_ABLATE 0
-#endif
 #ifndef DS_EPI_ABL
 #define DS_EPI_ABL 0   // diagnostic builds of the register epilogue: bit0 no output stores, bit1 no residual loads, bit2 no activation
 #endif
@@ -21,6 +18,46 @@ struct ConvCoord {
     int ho, wo;   // output coordinates (border class of the GroupNorm fold)
     int pix;      // pixel index inside the sample's output image
 };
+
+// The GroupNorm fold is on: the shifts come from the fold tables and this sample's statistics, not from the bias.
+// (a macro: as a function, in any form, the test comes out of hipcc as four scalar branches in every generic kernel)
+#define CONV_FOLD(p) ((p).gn_ab != nullptr || (p).gn_part != nullptr)
+
+// Border class of output pixel (ho, wo) of an Ho x Wo image: row of the fold tables (0 / 1 / 2 = first / inner / last, rows x 3 + columns)
+__device__ __forceinline__ int conv_border_class(int ho, int wo, int Ho, int Wo) {
+    return (ho == 0 ? 0 : (ho == Ho - 1 ? 2 : 1)) * 3 + (wo == 0 ? 0 : (wo == Wo - 1 ? 2 : 1));
+}
+
+// One entry of the shift table: channel n + q, border class cls, gam = factor x mean of this sample (zero beyond Cout).
+// (q: the position inside a vector of channels — added last, as a constant it stays the loads' immediate offset)
+__device__ __forceinline__ float conv_shift_entry(const ds_conv_params& p, bool fold, int cls, int n, float gam, int q = 0) {
+    float v = 0.f;
+    if (n + q < p.Cout) {
+        if (fold) v = DS_LD(float, p.fold_t1 + cls * p.Cout + n + q, DS_BX_T1) - gam * DS_LD(float, p.fold_t2 + cls * p.Cout + n + q, DS_BX_T2);
+        else if (p.bias) v = DS_LD(float, p.bias + n + q, DS_BX_BIAS);
+    }
+    return v;
+}
+
+// A K slice's launch as its epilogue sees it: raw fp32 partial sums -> slab[kz][b][pixel][roundup(Cout, 8)]; bias, fold, activation,
+// residual and statistics happen in ds_conv_splitk_reduce
+__device__ __forceinline__ ds_conv_params conv_kslice_view(const ds_conv_params& p) {
+    ds_conv_params q = p;
+    q.out = p.slab;
+    q.out_C = (p.Cout + 7) / 8 * 8;
+    q.out_c0 = 0;
+    q.bias = nullptr; q.gn_ab = nullptr; q.gn_part = nullptr; q.res = nullptr;
+    return q;
+}
+
+// bf16 -> fp32 and add: the low / high half of each dword of eight packed bf16
+__device__ __forceinline__ void add_bf16x8(float (&w)[8], const u32x4& rr) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        w[2 * e] += __uint_as_float(rr[e] << 16);
+        w[2 * e + 1] += __uint_as_float(rr[e] & 0xffff0000u);
+    }
+}
 
 template <typename T> __device__ __forceinline__ void store_scalar(T* p, float v);
 template <> __device__ __forceinline__ void store_scalar<float>(float* p, float v) { *p = v; }
@@ -45,7 +82,7 @@ __device__ __forceinline__ void conv_epilogue_body(const ds_conv_params& p, f32x
     constexpr int TN = FN * 32;
     constexpr int SW = TN + 4;  // stage row stride in floats (keeps 16-B alignment, spreads banks)
     const int lane = threadIdx.x & 63, frow = lane & 31, fh = lane >> 5;
-    const bool fold = p.gn_ab != nullptr || p.gn_part != nullptr;
+    const bool fold = CONV_FOLD(p);
     float ga = 1.f, gam = 0.f;
     if (p.gn_part) {
         ga = gn_a;      // reduced from the producer's partials at kernel start (conv_gn_prologue)
@@ -61,12 +98,7 @@ __device__ __forceinline__ void conv_epilogue_body(const ds_conv_params& p, f32x
     for (int j = 0; j < FN; ++j) {
         const int n = n_base + j * 32 + frow;
         nok[j] = n < p.Cout;
-        float sv = 0.f;
-        if (nok[j]) {
-            if (fold) sv = DS_LD(float, p.fold_t1 + cls_mid * p.Cout + n, DS_BX_T1) - gam * DS_LD(float, p.fold_t2 + cls_mid * p.Cout + n, DS_BX_T2);
-            else if (p.bias) sv = DS_LD(float, p.bias + n, DS_BX_BIAS);
-        }
-        shift_mid[j] = sv;
+        shift_mid[j] = conv_shift_entry(p, fold, cls_mid, n, gam);
     }
     T* const outp = reinterpret_cast<T*>(p.out);
     const T* const resp = reinterpret_cast<const T*>(p.res);
@@ -83,17 +115,14 @@ __device__ __forceinline__ void conv_epilogue_body(const ds_conv_params& p, f32x
             bool border = false;
             if constexpr (NCLS9) {
                 const ConvCoord c = coord(ml_base + i * 32 + row);
-                cls = (c.ho == 0 ? 0 : (c.ho == p.Ho - 1 ? 2 : 1)) * 3 + (c.wo == 0 ? 0 : (c.wo == p.Wo - 1 ? 2 : 1));
+                cls = conv_border_class(c.ho, c.wo, p.Ho, p.Wo);
                 border = cls != cls_mid && c.ok;
             }
 #pragma unroll
             for (int j = 0; j < FN; ++j) {
                 float sh = shift_mid[j];
                 if constexpr (NCLS9) {
-                    if (border && nok[j]) {
-                        const int n = n_base + j * 32 + frow;
-                        sh = DS_LD(float, p.fold_t1 + cls * p.Cout + n, DS_BX_T1) - gam * DS_LD(float, p.fold_t2 + cls * p.Cout + n, DS_BX_T2);
-                    }
+                    if (border && nok[j]) sh = conv_shift_entry(p, true, cls, n_base + j * 32 + frow, gam);      // (nine classes come with the fold)
                 }
                 stage[row * SW + j * 32 + frow] = act_const<ACT>(ga * acc[i][j][r] + sh);
             }
@@ -122,7 +151,7 @@ __device__ __forceinline__ void conv_epilogue_body(const ds_conv_params& p, f32x
 #pragma unroll
                     for (int q = 0; q < V; ++q) v[q] += rv[q];
                 }
-                if constexpr (!(DS_ABLATE & 32)) vec16_store<T>(outp + o, v, DS_BX_OUT);
+                vec16_store<T>(outp + o, v, DS_BX_OUT);
 #pragma unroll
                 for (int q = 0; q < V; ++q) {
                     s1 += v[q];
@@ -147,18 +176,20 @@ __device__ __forceinline__ void permlane32_swap(float& a, float& b) {
     asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
 }
 
-template <int BN>
-__device__ __forceinline__ void conv_shift_table(const ds_conv_params& p, int n0, float gam, float* shl) {
-    const bool fold = p.gn_ab != nullptr || p.gn_part != nullptr;
+// Shift table of an N-block from plain loads: shl[cls][BN] for the classes in use, zeros up to ROWS rows; `add` (the fused res_conv's
+// bias) joins every real entry.  NT threads, unrolled.
+template <int BN, int ROWS, int NT>
+__device__ __forceinline__ void conv_shift_table(const ds_conv_params& p, bool fold, int n0, float gam, const float* add, float* shl) {
     const int ncls = fold ? p.ncls : 1;
-    for (int e = threadIdx.x; e < ncls * BN; e += blockDim.x) {
-        const int cls = e / BN, n = n0 + e - cls * BN;
+#pragma unroll
+    for (int k = 0; k < (ROWS * BN + NT - 1) / NT; ++k) {
+        const int e = threadIdx.x + k * NT, cls = e / BN, n = n0 + e - cls * BN;
         float v = 0.f;
-        if (n < p.Cout) {
-            if (fold) v = DS_LD(float, p.fold_t1 + cls * p.Cout + n, DS_BX_T1) - gam * DS_LD(float, p.fold_t2 + cls * p.Cout + n, DS_BX_T2);
-            else if (p.bias) v = DS_LD(float, p.bias + n, DS_BX_BIAS);
+        if (e < ncls * BN) {
+            v = conv_shift_entry(p, fold, cls, n, gam);
+            if (add && n < p.Cout) v += DS_LD(float, add + n, DS_BX_AUX2);
         }
-        shl[e] = v;
+        if (e < ROWS * BN) shl[e] = v;
     }
 }
 
@@ -198,7 +229,7 @@ __device__ __forceinline__ void conv_epilogue_t_body(const ds_conv_params& p, f3
     for (int i = 0; i < FM; ++i) {
         const ConvCoord c = coord(ml_base + i * 32 + px);
         int cls = 0;
-        if constexpr (NCLS9) cls = (c.ho == 0 ? 0 : (c.ho == p.Ho - 1 ? 2 : 1)) * 3 + (c.wo == 0 ? 0 : (c.wo == p.Wo - 1 ? 2 : 1));
+        if constexpr (NCLS9) cls = conv_border_class(c.ho, c.wo, p.Ho, p.Wo);
         const float* shrow = shl + cls * BN + n_loc + 8 * fh;
         const size_t obase = ((size_t)b * outHW + c.pix) * p.out_C + p.out_c0 + n0 + n_loc + 8 * fh;
 #pragma unroll
@@ -226,12 +257,7 @@ __device__ __forceinline__ void conv_epilogue_t_body(const ds_conv_params& p, f3
                     const size_t o = obase + cofs;
                     if (has_res) {
                         if constexpr (!RAW && sizeof(T) == 2) {
-                            const u32x4 rr = rres[(i * FN + j) * 2 + q];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                v[2 * k] += __uint_as_float(rr[k] << 16);              // bf16 -> fp32: the low / high half of each dword
-                                v[2 * k + 1] += __uint_as_float(rr[k] & 0xffff0000u);
-                            }
+                            add_bf16x8(v, rres[(i * FN + j) * 2 + q]);
                         } else {
 #pragma unroll
                             for (int q2 = 0; q2 < 8; q2 += V) {
@@ -259,7 +285,7 @@ __device__ __forceinline__ void conv_epilogue_t_body(const ds_conv_params& p, f3
 template <typename T, int FM, int FN, int BN, typename CoordFn>
 __device__ __forceinline__ void conv_epilogue_t(const ds_conv_params& p, f32x16 (&acc)[FM][FN], int b, int n0, int n_loc, int ml_base, int outHW,
                                                 const float* shl, CoordFn coord, float& s1, float& s2, float ga) {
-    const bool fold = p.gn_ab != nullptr || p.gn_part != nullptr;
+    const bool fold = CONV_FOLD(p);
     if (p.act == DS_ACT_GELU) {
         if (fold && p.ncls == 9) conv_epilogue_t_body<T, FM, FN, BN, DS_ACT_GELU, true, false>(p, acc, b, n0, n_loc, ml_base, outHW, shl, coord, s1, s2, ga);
         else conv_epilogue_t_body<T, FM, FN, BN, DS_ACT_GELU, false, false>(p, acc, b, n0, n_loc, ml_base, outHW, shl, coord, s1, s2, ga);

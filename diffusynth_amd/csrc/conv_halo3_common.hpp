@@ -124,96 +124,162 @@ __device__ __forceinline__ void buf_st16(rsrc_t rs, const char* base, unsigned v
     __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)voff, 0, 0);
 }
 
-// ---- register epilogue: lane = pixel (lane & 15) of each of the wave's 4 pixel tiles, channels EPI_CH(j) + 8 * (lane >> 4) + r of accumulator tile j (three runs of 8 consecutive channels per lane).
+// Tile width of a W-wide image (log2): 8, 16 or 32 pixels of the 256-pixel block tile
+inline int halo_twl(int W) {
+    int twl = 3;
+    while ((1 << twl) < W && twl < 5) ++twl;
+    return twl;
+}
+
+// Pixel of (tile i, lane m) of wave `wave`: tile-local (row, col) in the block's (256 >> TWL) x (1 << TWL) tile
+template <int TWL> __device__ __forceinline__ void halo_tile_rc(int wave, int i, int m, int& row_l, int& col_l) {
+    if constexpr (TWL == 5) { row_l = 2 * wave + (i >> 1); col_l = 16 * (i & 1) + m; }
+    else if constexpr (TWL == 4) { row_l = 4 * wave + i; col_l = m; }
+    else { row_l = 8 * wave + i + 4 * (m >> 3); col_l = m & 7; }      // rows (i, i + 4): conflict-free with the 12-pixel pitch
+}
+
+// ---- register epilogues: lane = pixel (lane & 15) of each of the wave's 4 pixel tiles, channels EPI_CH(j) + 8 * (lane >> 4) + r of accumulator tile j (three runs of 8 consecutive channels per lane).
 // Branch-free: a lane without an output pixel (ragged tile) computes on a zero factor, the zero row of the shift table and a zero
 // residual, and its stores / residual loads carry an out-of-range buffer offset (dropped / zeros by the range check) — the
 // exec-masked version spent more time in s_and_saveexec / s_cbranch than in arithmetic (12 masked regions per wave tile).
-// TAB: the GELU comes from the LDS table at `lut` (gelu_tab8) — a template parameter, not a runtime test of the pointer (the table's LDS
-// address then folds into the gathers' immediate offset).  Issuing the gathers of group g+1 under the arithmetic of group g (hand
-// software-pipelined, sched_barrier-fenced) measured the same: the partner wave already covers that latency.
+// The four entry points below are built from these pieces.
+
+// `out` / `res` of sample b (es bytes per element) as buffers, the channel bound of the stores and whether the table has nine classes
+template <bool HAS_RES> struct EpiBufs {
+    const unsigned sample_bytes;
+    char* const obase;
+    const char* const rbase;
+    const rsrc_t rs_o, rs_r;
+    const int cout_v;
+    const bool nine;
+    __device__ __forceinline__ EpiBufs(const ds_conv_params& p, int b, int outHW, unsigned es)
+        : sample_bytes((unsigned)outHW * p.out_C * es),
+          obase(reinterpret_cast<char*>(p.out) + (size_t)b * sample_bytes),
+          rbase(reinterpret_cast<const char*>(p.res) + (size_t)b * sample_bytes),
+          rs_o(__builtin_amdgcn_make_buffer_rsrc(obase, (short)0, (int)sample_bytes, 0x00020000)),
+          rs_r(__builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(HAS_RES ? rbase : obase), (short)0, HAS_RES ? (int)sample_bytes : 0, 0x00020000)),
+          cout_v((p.Cout + 7) / 8 * 8),
+          nine(CONV_FOLD(p) && p.ncls == 9) {}
+};
+
+// pixel tile of coordinate c: its border-class row of the shift table (row 9, zeros, for a lane without a pixel) and its GroupNorm factor (0 there)
+template <bool NCLS9>
+__device__ __forceinline__ void epi_tile_shift(const ds_conv_params& p, const ConvCoord& c, bool nine, const float* shl, int n_loc, float ga,
+                                               const float*& shrow, float& gi) {
+    int cls = 0;
+    if constexpr (NCLS9) cls = conv_border_class(c.ho, c.wo, p.Ho, p.Wo);
+    if (!nine) cls = 0;                                    // bias-only table: one row
+    shrow = shl + (c.ok ? cls : 9) * BN + n_loc;
+    gi = c.ok ? ga : 0.f;
+}
+
+// 8 consecutive channels = accumulator tiles 2k, 2k + 1: w = gi * acc + shift.  Plain fp32 VALU (never packed: see gelu_poly8)
+__device__ __forceinline__ void epi_affine8(float gi, const f32x4& a0, const f32x4& a1, const float* sh, float (&w)[8]) {
+    const f32x4 sa = *reinterpret_cast<const f32x4*>(sh), sb = *reinterpret_cast<const f32x4*>(sh + 4);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        w[r] = fmaf(gi, a0[r], sa[r]);
+        w[4 + r] = fmaf(gi, a1[r], sb[r]);
+    }
+}
+
+// the bf16 tier's GELU of 8 values.  TAB: from the LDS table at `lut` (gelu_tab8) — a template parameter, not a runtime test of the pointer
+// (the table's LDS address then folds into the gathers' immediate offset); the table exists for the 32- / 16-wide tiles
+template <int ACT, bool TAB> __device__ __forceinline__ void epi_gelu8(float (&w)[8], const char* lut) {
+    if constexpr (ACT == DS_ACT_GELU) {
+        if constexpr (TAB) gelu_tab8(w, lut);
+        else gelu_poly8(w);
+    }
+}
+
+// count 8 values into the four independent statistics chains (even / odd channels) and round them to bf16: the counted values are fp32
+__device__ __forceinline__ u32x4 epi_count_pack8(const float (&w)[8], float& s1a, float& s1b, float& s2a, float& s2b) {
+    bf16x8 o8;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        s1a += w[2 * e];
+        s1b += w[2 * e + 1];
+        s2a = fmaf(w[2 * e], w[2 * e], s2a);
+        s2b = fmaf(w[2 * e + 1], w[2 * e + 1], s2b);
+        o8[2 * e] = (bf16)w[2 * e];
+        o8[2 * e + 1] = (bf16)w[2 * e + 1];
+    }
+    return __builtin_bit_cast(u32x4, o8);
+}
+
+__device__ __forceinline__ void epi_stage_f32x8(char* dst, const float (&w)[8]) {
+    *reinterpret_cast<f32x4*>(dst) = f32x4{w[0], w[1], w[2], w[3]};
+    *reinterpret_cast<f32x4*>(dst + 16) = f32x4{w[4], w[5], w[6], w[7]};
+}
+
+// Contiguous side of the staged epilogues: the 16 pixels x 96 channels (ES bytes each) of a tile row leave as 16-byte pieces, PP per pixel;
+// piece lane + 64 t of the row = pixel pxl[t], channels CH pq[t] .. CH pq[t] + CH - 1
+template <int ES> struct RowPieces {
+    static constexpr int PP = BN * ES / 16, N = PP / 4, CH = 16 / ES;      // bf16: 12 pieces per pixel, 3 per lane, 8 channels; fp32: 24, 6, 4
+    int pxl[N], pq[N];
+    __device__ __forceinline__ explicit RowPieces(int lane) {
+#pragma unroll
+        for (int t = 0; t < N; ++t) {
+            const int pc = lane + 64 * t;
+            pxl[t] = pc / PP;
+            pq[t] = pc - PP * pxl[t];
+        }
+    }
+    // byte offset of piece t of tile row i inside the sample (bit 31 = VOFF_NONE: no pixel there, or beyond the valid channels)
+    template <typename Coord2Fn>
+    __device__ __forceinline__ unsigned off(const ds_conv_params& p, int cout_v, int n0, Coord2Fn coord2, int i, int t) const {
+        const ConvCoord c2 = coord2(i, pxl[t]);
+        const unsigned bad = (unsigned)!c2.ok | (unsigned)(n0 + CH * pq[t] >= cout_v);
+        return (((unsigned)(c2.pix * p.out_C + p.out_c0 + n0 + CH * pq[t]) * (unsigned)ES) & 0x7fffffffu) | (bad << 31);
+    }
+};
+
+// ---- bf16 output straight from the registers: 64-byte runs per pixel (EPI_CH).  Issuing the table gathers of group g+1 under the arithmetic
+// of group g (hand software-pipelined, sched_barrier-fenced) measured the same: the partner wave already covers that latency.
 template <int ACT, bool NCLS9, bool HAS_RES, bool TAB = false, typename CoordFn>
 __device__ __forceinline__ void halo3_epilogue(const ds_conv_params& p, f32x4 (&acc)[XT][WT], int b, int n0, int outHW, const float* shl,
                                                CoordFn coord, float& s1, float& s2, float ga, int lane, const char* lut = nullptr) {
-    const int g = lane >> 4, n_loc = 8 * g;                 // channels 32 k + 8 g .. + 7 of store k (EPI_CH)
-    const unsigned sample_bytes = (unsigned)outHW * p.out_C * 2u;
-    char* const obase = reinterpret_cast<char*>(p.out) + (size_t)b * sample_bytes;
-    const char* const rbase = reinterpret_cast<const char*>(p.res) + (size_t)b * sample_bytes;
-    const rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(obase, (short)0, (int)sample_bytes, 0x00020000);
-    const rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(HAS_RES ? rbase : obase), (short)0, HAS_RES ? (int)sample_bytes : 0, 0x00020000);
-    const int cout_v = (p.Cout + 7) / 8 * 8;
-    const bool nine = (p.gn_ab != nullptr || p.gn_part != nullptr) && p.ncls == 9;
-    // per pixel tile i: border-class row of the shift table, GroupNorm factor (0 for lanes without a pixel) and the three 16-byte store /
-    // residual offsets — set up tile by tile, the residual vectors of tile i + 1 requested while tile i is computed (24 registers of
-    // residuals in flight instead of 48 for the whole wave tile)
+    const int n_loc = 8 * (lane >> 4);                      // channels 32 k + 8 g .. + 7 of store k (EPI_CH)
+    const EpiBufs<HAS_RES> io(p, b, outHW, 2u);
+    // per pixel tile i: shift row, factor and the three 16-byte store / residual offsets — set up tile by tile, the residual vectors of
+    // tile i + 1 requested while tile i is computed (24 registers of residuals in flight instead of 48 for the whole wave tile)
     unsigned voff[2][3];
     float gai[2];
     const float* shrow[2];
     u32x4 rres[HAS_RES ? 2 : 1][3];
     auto setup = [&](int i) {
         const ConvCoord c = coord(i);
-        int cls = 0;
-        if constexpr (NCLS9) cls = (c.ho == 0 ? 0 : (c.ho == p.Ho - 1 ? 2 : 1)) * 3 + (c.wo == 0 ? 0 : (c.wo == p.Wo - 1 ? 2 : 1));
-        if (!nine) cls = 0;                                    // bias-only table: one row
-        shrow[i & 1] = shl + (c.ok ? cls : 9) * BN + n_loc;    // row 9 of the table is zero
-        gai[i & 1] = c.ok ? ga : 0.f;
+        epi_tile_shift<NCLS9>(p, c, io.nine, shl, n_loc, ga, shrow[i & 1], gai[i & 1]);
         // (arithmetic, not a select: the compiler turns the select into exec-masked branches, 12 masked regions per wave tile; an offset with
         // bit 31 set is beyond every buffer = VOFF_NONE)
         const unsigned o = ((unsigned)(c.pix * p.out_C + p.out_c0 + n0 + n_loc) * 2u) & 0x7fffffffu, nok = (unsigned)!c.ok;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            voff[i & 1][k] = (o + 64u * k) | ((nok | (unsigned)(n0 + n_loc + 32 * k >= cout_v)) << 31);
-            if constexpr (HAS_RES) rres[i & 1][k] = (DS_EPI_ABL & 2) ? u32x4{0u, 0u, 0u, 0u} : buf_ld16(rs_r, rbase, voff[i & 1][k], 0u, DS_BX_RES);
+            voff[i & 1][k] = (o + 64u * k) | ((nok | (unsigned)(n0 + n_loc + 32 * k >= io.cout_v)) << 31);
+            if constexpr (HAS_RES) rres[i & 1][k] = (DS_EPI_ABL & 2) ? u32x4{0u, 0u, 0u, 0u} : buf_ld16(io.rs_r, io.rbase, voff[i & 1][k], 0u, DS_BX_RES);
         }
     };
     setup(0);
-    // plain fp32 VALU (never packed: see gelu_poly8), four independent statistics chains
     float s1a = 0.f, s1b = 0.f, s2a = 0.f, s2b = 0.f;
 #pragma unroll
     for (int i = 0; i < XT; ++i) {
         if (i + 1 < XT) setup(i + 1);
-        const float gi = gai[i & 1];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {                      // 8 channels = accumulator tiles 2k, 2k+1
-            const f32x4 sa = *reinterpret_cast<const f32x4*>(shrow[i & 1] + 32 * k), sb = *reinterpret_cast<const f32x4*>(shrow[i & 1] + 32 * k + 4);
-            const f32x4 a0 = acc[i][2 * k], a1 = acc[i][2 * k + 1];
+        for (int k = 0; k < 3; ++k) {
             float w[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                w[r] = fmaf(gi, a0[r], sa[r]);
-                w[4 + r] = fmaf(gi, a1[r], sb[r]);
-            }
-            if constexpr (ACT == DS_ACT_GELU && !(DS_EPI_ABL & 4)) {
-                if constexpr (TAB) gelu_tab8(w, lut);       // (the table exists for the 32- / 16-wide tiles)
-                else gelu_poly8(w);
-            }
-            if constexpr (HAS_RES) {                       // bf16 -> fp32: the low / high half of each dword
-                const u32x4 rr = rres[i & 1][k];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    w[2 * e] += __uint_as_float(rr[e] << 16);
-                    w[2 * e + 1] += __uint_as_float(rr[e] & 0xffff0000u);
-                }
-            }
-            bf16x8 o8;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                s1a += w[2 * e];
-                s1b += w[2 * e + 1];
-                s2a = fmaf(w[2 * e], w[2 * e], s2a);
-                s2b = fmaf(w[2 * e + 1], w[2 * e + 1], s2b);
-                o8[2 * e] = (bf16)w[2 * e];
-                o8[2 * e + 1] = (bf16)w[2 * e + 1];
-            }
-            if constexpr (!(DS_EPI_ABL & 1)) buf_st16(rs_o, obase, voff[i & 1][k], __builtin_bit_cast(u32x4, o8), DS_BX_OUT);
+            epi_affine8(gai[i & 1], acc[i][2 * k], acc[i][2 * k + 1], shrow[i & 1] + 32 * k, w);
+            epi_gelu8<(DS_EPI_ABL & 4) ? DS_ACT_NONE : ACT, TAB>(w, lut);
+            if constexpr (HAS_RES) add_bf16x8(w, rres[i & 1][k]);
+            const u32x4 o8 = epi_count_pack8(w, s1a, s1b, s2a, s2b);
+            if constexpr (!(DS_EPI_ABL & 1)) buf_st16(io.rs_o, io.obase, voff[i & 1][k], o8, DS_BX_OUT);
         }
     }
     s1 += s1a + s1b;
     s2 += s2a + s2b;
 }
 
-// ---- the same epilogue with LINE-SIZED stores (r03).  Above, a 16-byte store instruction is 64 separate pieces (a lane owns one pixel and 24
-// consecutive channels: its three pieces are 16 bytes apart, the four lane groups of a pixel 48 bytes apart, pixels a row apart), and so is a
-// residual load: 64 L2 requests per kilobyte.  Here the 16 pixels x 96 channels of one accumulator tile row go through a wave-private LDS tile
+// ---- the same epilogue with LINE-SIZED stores (r03).  Above, a 16-byte store instruction is 64 separate pieces (a lane owns one pixel and three
+// runs of 8 channels), and so is a residual load.  Here the 16 pixels x 96 channels of one accumulator tile row go through a wave-private LDS tile
 // (the halo buffers are dead after the K loop; every wave is past the loop's last barrier) and leave as 192 consecutive 16-byte pieces, 12 per
 // pixel: whole 128-byte lines per instruction where the block's 96 channels are the tensor's row (out_C = 96), 192-byte runs otherwise.
 // Without a residual the tile is staged as bf16 (pitch 208 B, statistics taken in the accumulator layout as before); with one it is staged as
@@ -223,21 +289,9 @@ __device__ __forceinline__ void halo3_epilogue_rows(const ds_conv_params& p, f32
                                                     CoordFn coord, Coord2Fn coord2, char* stage, float& s1, float& s2, float ga, int lane,
                                                     const char* lut = nullptr) {
     constexpr int PITCH = HAS_RES ? 400 : 208;
-    const int m = lane & 15, g = lane >> 4, n_loc = 8 * g;
-    const unsigned sample_bytes = (unsigned)outHW * p.out_C * 2u;
-    char* const obase = reinterpret_cast<char*>(p.out) + (size_t)b * sample_bytes;
-    const char* const rbase = reinterpret_cast<const char*>(p.res) + (size_t)b * sample_bytes;
-    const rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(obase, (short)0, (int)sample_bytes, 0x00020000);
-    const rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(HAS_RES ? rbase : obase), (short)0, HAS_RES ? (int)sample_bytes : 0, 0x00020000);
-    const int cout_v = (p.Cout + 7) / 8 * 8;
-    const bool nine = (p.gn_ab != nullptr || p.gn_part != nullptr) && p.ncls == 9;
-    int pxl[3], pq[3];                                       // contiguous side: piece lane + 64 t of the tile row = pixel pxl, channels 8 pq .. 8 pq + 7
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const int pc = lane + 64 * t;
-        pxl[t] = pc / 12;
-        pq[t] = pc - 12 * pxl[t];
-    }
+    const int m = lane & 15, n_loc = 8 * (lane >> 4);
+    const EpiBufs<HAS_RES> io(p, b, outHW, 2u);
+    const RowPieces<2> pc(lane);
     char* const wr = stage + m * PITCH + n_loc * (HAS_RES ? 4 : 2);          // + 32 channels per k
     float s1a = 0.f, s1b = 0.f, s2a = 0.f, s2b = 0.f;
 #pragma unroll
@@ -246,70 +300,30 @@ __device__ __forceinline__ void halo3_epilogue_rows(const ds_conv_params& p, f32
         u32x4 rres[HAS_RES ? 3 : 1];
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            const ConvCoord c2 = coord2(i, pxl[t]);
-            const unsigned bad = (unsigned)!c2.ok | (unsigned)(n0 + 8 * pq[t] >= cout_v);
-            off[t] = (((unsigned)(c2.pix * p.out_C + p.out_c0 + n0 + 8 * pq[t]) * 2u) & 0x7fffffffu) | (bad << 31);
-            if constexpr (HAS_RES) rres[t] = buf_ld16(rs_r, rbase, off[t], 0u, DS_BX_RES);
+            off[t] = pc.off(p, io.cout_v, n0, coord2, i, t);
+            if constexpr (HAS_RES) rres[t] = buf_ld16(io.rs_r, io.rbase, off[t], 0u, DS_BX_RES);
         }
-        const ConvCoord c = coord(i);
-        int cls = 0;
-        if constexpr (NCLS9) cls = (c.ho == 0 ? 0 : (c.ho == p.Ho - 1 ? 2 : 1)) * 3 + (c.wo == 0 ? 0 : (c.wo == p.Wo - 1 ? 2 : 1));
-        if (!nine) cls = 0;
-        const float* const shrow = shl + (c.ok ? cls : 9) * BN + n_loc;
-        const float gi = c.ok ? ga : 0.f;
+        const float* shrow;
+        float gi;
+        epi_tile_shift<NCLS9>(p, coord(i), io.nine, shl, n_loc, ga, shrow, gi);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const f32x4 sa = *reinterpret_cast<const f32x4*>(shrow + 32 * k), sb = *reinterpret_cast<const f32x4*>(shrow + 32 * k + 4);
-            const f32x4 a0 = acc[i][2 * k], a1 = acc[i][2 * k + 1];
             float w[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                w[r] = fmaf(gi, a0[r], sa[r]);
-                w[4 + r] = fmaf(gi, a1[r], sb[r]);
-            }
-            if constexpr (ACT == DS_ACT_GELU) {
-                if constexpr (TAB) gelu_tab8(w, lut);
-                else gelu_poly8(w);
-            }
-            if constexpr (HAS_RES) {
-                *reinterpret_cast<f32x4*>(wr + 128 * k) = f32x4{w[0], w[1], w[2], w[3]};
-                *reinterpret_cast<f32x4*>(wr + 128 * k + 16) = f32x4{w[4], w[5], w[6], w[7]};
-            } else {
-                bf16x8 o8;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    s1a += w[2 * e];
-                    s1b += w[2 * e + 1];
-                    s2a = fmaf(w[2 * e], w[2 * e], s2a);
-                    s2b = fmaf(w[2 * e + 1], w[2 * e + 1], s2b);
-                    o8[2 * e] = (bf16)w[2 * e];
-                    o8[2 * e + 1] = (bf16)w[2 * e + 1];
-                }
-                *reinterpret_cast<u32x4*>(wr + 64 * k) = __builtin_bit_cast(u32x4, o8);
-            }
+            epi_affine8(gi, acc[i][2 * k], acc[i][2 * k + 1], shrow + 32 * k, w);
+            epi_gelu8<ACT, TAB>(w, lut);
+            if constexpr (HAS_RES) epi_stage_f32x8(wr + 128 * k, w);
+            else *reinterpret_cast<u32x4*>(wr + 64 * k) = epi_count_pack8(w, s1a, s1b, s2a, s2b);
         }
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             if constexpr (HAS_RES) {
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + pxl[t] * PITCH + pq[t] * 32), hi = *reinterpret_cast<const f32x4*>(stage + pxl[t] * PITCH + pq[t] * 32 + 16);
+                const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + pc.pxl[t] * PITCH + pc.pq[t] * 32), hi = *reinterpret_cast<const f32x4*>(stage + pc.pxl[t] * PITCH + pc.pq[t] * 32 + 16);
                 float w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                const u32x4 rr = rres[t];
-                bf16x8 o8;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    w[2 * e] += __uint_as_float(rr[e] << 16);
-                    w[2 * e + 1] += __uint_as_float(rr[e] & 0xffff0000u);
-                    s1a += w[2 * e];
-                    s1b += w[2 * e + 1];
-                    s2a = fmaf(w[2 * e], w[2 * e], s2a);
-                    s2b = fmaf(w[2 * e + 1], w[2 * e + 1], s2b);
-                    o8[2 * e] = (bf16)w[2 * e];
-                    o8[2 * e + 1] = (bf16)w[2 * e + 1];
-                }
-                buf_st16(rs_o, obase, off[t], __builtin_bit_cast(u32x4, o8), DS_BX_OUT);
+                add_bf16x8(w, rres[t]);
+                buf_st16(io.rs_o, io.obase, off[t], epi_count_pack8(w, s1a, s1b, s2a, s2b), DS_BX_OUT);
             } else {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(stage + pxl[t] * PITCH + pq[t] * 16);
-                buf_st16(rs_o, obase, off[t], v, DS_BX_OUT);
+                const u32x4 v = *reinterpret_cast<const u32x4*>(stage + pc.pxl[t] * PITCH + pc.pq[t] * 16);
+                buf_st16(io.rs_o, io.obase, off[t], v, DS_BX_OUT);
             }
         }
     }
@@ -317,69 +331,44 @@ __device__ __forceinline__ void halo3_epilogue_rows(const ds_conv_params& p, f32
     s2 += s2a + s2b;
 }
 
-// ---- epilogue of the split-precision tier (ds_conv_params.flags, DS_CONV_F_OUT_*): the same lane layout, fp32 results stored either
-// as TWO bf16 planes (hi = bf16(v) at channel n, lo = bf16(v - hi) at channel Cout + n of an image with 2 * Cout bf16 channels: the
-// input format of the next split convolution) or as plain fp32 (with an optional fp32 residual: what the fp32 kernels around the
-// 3x3 convolutions read).  Exact-erf GELU (gelu_fast: 1.5e-7), not the polynomial of the bf16 tier.
-template <int ACT, int OUT_MODE, bool HAS_RES, typename CoordFn>
+// ---- epilogue of the split-precision tier (ds_conv_params.flags, DS_CONV_F_OUT_*) from the registers: the same lane layout, fp32 results
+// stored either as TWO bf16 planes (hi = bf16(v) at channel n, lo = bf16(v - hi) at channel Cout + n of an image with 2 * Cout bf16 channels:
+// the input format of the next split convolution) or as plain fp32 (the raw partial sums of a K slice; fp32 images take the line-sized form
+// below).  Exact-erf GELU (gelu_fast: 1.5e-7), not the polynomial of the bf16 tier.
+template <int ACT, int OUT_MODE, typename CoordFn>
 __device__ __forceinline__ void halo3_epilogue_hp(const ds_conv_params& p, f32x4 (&acc)[XT][WT], int b, int n0, int outHW, const float* shl,
                                                   CoordFn coord, float& s1, float& s2, float ga, int lane) {
     static_assert(OUT_MODE == 1 || OUT_MODE == 2, "1 = split bf16 planes, 2 = fp32");
-    const int g = lane >> 4, n_loc = 8 * g;                  // channels 32 k + 8 g .. + 7 of group k (EPI_CH)
+    const int n_loc = 8 * (lane >> 4);                               // channels 32 k + 8 g .. + 7 of group k (EPI_CH)
     constexpr unsigned ES = OUT_MODE == 2 ? 4u : 2u;                 // bytes per element of the out tensor as described by out_C
-    const unsigned sample_bytes = (unsigned)outHW * p.out_C * ES;
-    char* const obase = reinterpret_cast<char*>(p.out) + (size_t)b * sample_bytes;
-    const char* const rbase = reinterpret_cast<const char*>(p.res) + (size_t)b * sample_bytes;
-    const rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(obase, (short)0, (int)sample_bytes, 0x00020000);
-    const rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(HAS_RES ? rbase : obase), (short)0, HAS_RES ? (int)sample_bytes : 0, 0x00020000);
-    const int cout_v = (p.Cout + 7) / 8 * 8;
-    const bool nine = (p.gn_ab != nullptr || p.gn_part != nullptr) && p.ncls == 9;
+    const EpiBufs<false> io(p, b, outHW, ES);
     const unsigned lo_off = (unsigned)p.Cout * 2u;                    // split planes: the lo plane starts Cout channels further
 #pragma unroll
     for (int i = 0; i < XT; ++i) {
         const ConvCoord c = coord(i);
-        int cls = (c.ho == 0 ? 0 : (c.ho == p.Ho - 1 ? 2 : 1)) * 3 + (c.wo == 0 ? 0 : (c.wo == p.Wo - 1 ? 2 : 1));
-        if (!nine) cls = 0;
-        const float* shrow = shl + (c.ok ? cls : 9) * BN + n_loc;
-        const float gai = c.ok ? ga : 0.f;
+        const float* shrow;
+        float gai;
+        epi_tile_shift<true>(p, c, io.nine, shl, n_loc, ga, shrow, gai);
         const unsigned o = (unsigned)(c.pix * p.out_C + p.out_c0 + n0 + n_loc) * ES;
-        u32x4 rres[HAS_RES ? 6 : 1];
-        if constexpr (HAS_RES) {                                      // fp32 residual: 3 x 8 channels = 6 x 16 B (tile k: channel EPI_CH(k) + 8 g)
-            static_assert(!HAS_RES || OUT_MODE == 2, "a residual comes with the fp32 output mode");
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                rres[k] = buf_ld16(rs_r, rbase, (c.ok && n0 + n_loc + EPI_CH(k) < cout_v) ? o + (unsigned)EPI_CH(k) * 4u : VOFF_NONE, 0u, DS_BX_RES);
-        }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const f32x4 sa = *reinterpret_cast<const f32x4*>(shrow + 32 * k), sb = *reinterpret_cast<const f32x4*>(shrow + 32 * k + 4);
             float v[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[r] = act_const<ACT>(fmaf(gai, acc[i][2 * k][r], sa[r]));
-                v[4 + r] = act_const<ACT>(fmaf(gai, acc[i][2 * k + 1][r], sb[r]));
-            }
-            if constexpr (HAS_RES) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] += __uint_as_float(rres[2 * k][r]);
-                    v[4 + r] += __uint_as_float(rres[2 * k + 1][r]);
-                }
-            }
+            epi_affine8(gai, acc[i][2 * k], acc[i][2 * k + 1], shrow + 32 * k, v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
+                v[e] = act_const<ACT>(v[e]);
                 s1 += v[e];
                 s2 = fmaf(v[e], v[e], s2);
             }
-            const bool okk = c.ok && n0 + n_loc + 32 * k < cout_v;
+            const bool okk = c.ok && n0 + n_loc + 32 * k < io.cout_v;
             if constexpr (OUT_MODE == 2) {
-                buf_st16(rs_o, obase, okk ? o + 128u * k : VOFF_NONE, u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, DS_BX_OUT);
-                buf_st16(rs_o, obase, okk ? o + 128u * k + 16u : VOFF_NONE, u32x4{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])}, DS_BX_OUT);
+                buf_st16(io.rs_o, io.obase, okk ? o + 128u * k : VOFF_NONE, u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, DS_BX_OUT);
+                buf_st16(io.rs_o, io.obase, okk ? o + 128u * k + 16u : VOFF_NONE, u32x4{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])}, DS_BX_OUT);
             } else {
                 u32x4 hi8, lo8;
                 ds_split8(v, hi8, lo8);
-                buf_st16(rs_o, obase, okk ? o + 64u * k : VOFF_NONE, hi8, DS_BX_OUT);
-                buf_st16(rs_o, obase, okk ? o + 64u * k + lo_off : VOFF_NONE, lo8, DS_BX_OUT);
+                buf_st16(io.rs_o, io.obase, okk ? o + 64u * k : VOFF_NONE, hi8, DS_BX_OUT);
+                buf_st16(io.rs_o, io.obase, okk ? o + 64u * k + lo_off : VOFF_NONE, lo8, DS_BX_OUT);
             }
         }
     }
@@ -393,21 +382,10 @@ constexpr int EPI_F32_PITCH = 400, EPI_F32_WAVE = 16 * EPI_F32_PITCH;
 template <bool NCLS9, bool HAS_RES, typename CoordFn, typename Coord2Fn>
 __device__ __forceinline__ void halo3_epilogue_rows_f32(const ds_conv_params& p, f32x4 (&acc)[XT][WT], int b, int n0, int outHW, const float* shl,
                                                         CoordFn coord, Coord2Fn coord2, char* stage, float& s1, float& s2, float ga, int lane) {
-    const int m = lane & 15, g = lane >> 4, n_loc = 8 * g;
-    const unsigned sample_bytes = (unsigned)outHW * p.out_C * 4u;
-    char* const obase = reinterpret_cast<char*>(p.out) + (size_t)b * sample_bytes;
-    const char* const rbase = reinterpret_cast<const char*>(p.res) + (size_t)b * sample_bytes;
-    const rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(obase, (short)0, (int)sample_bytes, 0x00020000);
-    const rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(HAS_RES ? rbase : obase), (short)0, HAS_RES ? (int)sample_bytes : 0, 0x00020000);
-    const int cout_v = (p.Cout + 7) / 8 * 8;
-    const bool nine = (p.gn_ab != nullptr || p.gn_part != nullptr) && p.ncls == 9;
-    int pxl[6], pq[6];                                       // contiguous side: piece lane + 64 t of the tile row = pixel pxl, channels 4 pq .. 4 pq + 3
-#pragma unroll
-    for (int t = 0; t < 6; ++t) {
-        const int pc = lane + 64 * t;
-        pxl[t] = pc / 24;
-        pq[t] = pc - 24 * pxl[t];
-    }
+    const int m = lane & 15, n_loc = 8 * (lane >> 4);
+    const EpiBufs<HAS_RES> io(p, b, outHW, 4u);
+    const RowPieces<4> pc(lane);
+    char* const wr = stage + m * EPI_F32_PITCH + n_loc * 4;          // + 32 channels per k
     float s1a = 0.f, s1b = 0.f, s2a = 0.f, s2b = 0.f;
 #pragma unroll
     for (int i = 0; i < XT; ++i) {
@@ -415,28 +393,21 @@ __device__ __forceinline__ void halo3_epilogue_rows_f32(const ds_conv_params& p,
         u32x4 rres[HAS_RES ? 6 : 1];
 #pragma unroll
         for (int t = 0; t < 6; ++t) {
-            const ConvCoord c2 = coord2(i, pxl[t]);
-            const unsigned bad = (unsigned)!c2.ok | (unsigned)(n0 + 4 * pq[t] >= cout_v);
-            off[t] = (((unsigned)(c2.pix * p.out_C + p.out_c0 + n0 + 4 * pq[t]) * 4u) & 0x7fffffffu) | (bad << 31);
-            if constexpr (HAS_RES) rres[t] = buf_ld16(rs_r, rbase, off[t], 0u, DS_BX_RES);
+            off[t] = pc.off(p, io.cout_v, n0, coord2, i, t);
+            if constexpr (HAS_RES) rres[t] = buf_ld16(io.rs_r, io.rbase, off[t], 0u, DS_BX_RES);
         }
-        const ConvCoord c = coord(i);
-        int cls = 0;
-        if constexpr (NCLS9) cls = (c.ho == 0 ? 0 : (c.ho == p.Ho - 1 ? 2 : 1)) * 3 + (c.wo == 0 ? 0 : (c.wo == p.Wo - 1 ? 2 : 1));
-        if (!nine) cls = 0;
-        const float* const shrow = shl + (c.ok ? cls : 9) * BN + n_loc;
-        const float gi = c.ok ? ga : 0.f;
+        const float* shrow;
+        float gi;
+        epi_tile_shift<NCLS9>(p, coord(i), io.nine, shl, n_loc, ga, shrow, gi);
 #pragma unroll
-        for (int k = 0; k < WT; ++k) {
-            const f32x4 sh = *reinterpret_cast<const f32x4*>(shrow + EPI_CH(k));
-            f32x4 v;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = fmaf(gi, acc[i][k][r], sh[r]);
-            *reinterpret_cast<f32x4*>(stage + m * EPI_F32_PITCH + (n_loc + EPI_CH(k)) * 4) = v;
+        for (int k = 0; k < 3; ++k) {
+            float w[8];
+            epi_affine8(gi, acc[i][2 * k], acc[i][2 * k + 1], shrow + 32 * k, w);
+            epi_stage_f32x8(wr + 128 * k, w);
         }
 #pragma unroll
         for (int t = 0; t < 6; ++t) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(stage + pxl[t] * EPI_F32_PITCH + pq[t] * 16);
+            f32x4 v = *reinterpret_cast<const f32x4*>(stage + pc.pxl[t] * EPI_F32_PITCH + pc.pq[t] * 16);
             if constexpr (HAS_RES) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] += __uint_as_float(rres[t][r]);
@@ -447,7 +418,7 @@ __device__ __forceinline__ void halo3_epilogue_rows_f32(const ds_conv_params& p,
             s1b += v[1] + v[3];
             s2a = fmaf(v[0], v[0], fmaf(v[2], v[2], s2a));
             s2b = fmaf(v[1], v[1], fmaf(v[3], v[3], s2b));
-            buf_st16(rs_o, obase, off[t], __builtin_bit_cast(u32x4, v), DS_BX_OUT);
+            buf_st16(io.rs_o, io.obase, off[t], __builtin_bit_cast(u32x4, v), DS_BX_OUT);
         }
     }
     s1 += s1a + s1b;

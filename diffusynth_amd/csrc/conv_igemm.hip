@@ -251,17 +251,11 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 && BM == 256) ? 1 : 2) void co
     float s1 = 0.f, s2 = 0.f;
     float* stage = reinterpret_cast<float*>(smem) + wave * (32 * (TN + 4));
     if (ksplit > 1) {
-        // raw fp32 partial sums of this K slice -> slab[kz][b]; bias / fold / activation / residual / statistics
-        // happen in ds_conv_splitk_reduce
-        ds_conv_params q = p;
-        q.out = p.slab;
-        q.out_C = (p.Cout + 7) / 8 * 8;
-        q.out_c0 = 0;
-        q.bias = nullptr; q.gn_ab = nullptr; q.gn_part = nullptr; q.res = nullptr;
+        const ds_conv_params q = conv_kslice_view(p);
         conv_epilogue_body<float, FM, FN, DS_ACT_NONE, false>(q, acc, kz * p.B + b, n0 + wn * TN, wm * TM, outHW, stage, coord, s1, s2);
         return;
     }
-    if constexpr (!(DS_ABLATE & 64)) conv_epilogue<T, FM, FN>(p, acc, b, n0 + wn * TN, wm * TM, outHW, stage, coord, s1, s2, gn_a, gn_am);
+    conv_epilogue<T, FM, FN>(p, acc, b, n0 + wn * TN, wm * TM, outHW, stage, coord, s1, s2, gn_a, gn_am);
     __syncthreads();   // stage regions overlap `red`
     if (p.stats_part) {
         const int parts = gridDim.x * gridDim.y * nphase;

@@ -26,13 +26,6 @@ void ds_conv_bounds_table(const ds_conv_params& p, int kernel, int stats_parts, 
 
 #include "conv_halo3_common.hpp"
 
-#ifndef DS_QUAD_ROWS
-#define DS_QUAD_ROWS 1          // fp32 output mode: line-sized stores through an LDS tile (a lane's fp32 run is 32 bytes, two instructions)
-#endif
-#ifndef DS_QUAD_ROWS_BF16
-#define DS_QUAD_ROWS_BF16 0     // bf16: 64-byte runs straight from the registers (EPI_CH map) measure the same as the staged form
-#endif
-
 namespace {
 
 constexpr int QHALO_BYTES = HALO_BYTES + 1024;            // + 16 pixels: the shifted store of a strided plane (up to one row + one pixel)
@@ -155,9 +148,7 @@ __global__ __launch_bounds__(NT, DS_MINBLK) void conv_quad_halo3_kernel(const ds
 #pragma unroll
     for (int i = 0; i < XT; ++i) {
         int row_l, col_l;
-        if constexpr (TWL == 5) { row_l = 2 * wave + (i >> 1); col_l = 16 * (i & 1) + m; }
-        else if constexpr (TWL == 4) { row_l = 4 * wave + i; col_l = m; }
-        else { row_l = 8 * wave + i + 4 * (m >> 3); col_l = m & 7; }
+        halo_tile_rc<TWL>(wave, i, m, row_l, col_l);
         hp0[i] = row_l * HCP + col_l;
     }
     // Fragment addresses (halo buffer 0) of the four taps of window origin (oy, ox) = (py, px) resp. (1, 1): ONE base per pixel tile (tap 0)
@@ -327,11 +318,7 @@ __global__ __launch_bounds__(NT, DS_MINBLK) void conv_quad_halo3_kernel(const ds
     // m kept nine registers alive across the K loop, in scratch (the kernel is at its 256-register budget; zero scratch is pinned by
     // tests/test_isa_schedule_cpu.py).
     const int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), wave_e = wave_s, m_e = lane_e & 15;
-    auto coord = [&](int i) {
-        int row_l, col_l;
-        if constexpr (TWL == 5) { row_l = 2 * wave_e + (i >> 1); col_l = 16 * (i & 1) + m_e; }
-        else if constexpr (TWL == 4) { row_l = 4 * wave_e + i; col_l = m_e; }
-        else { row_l = 8 * wave_e + i + 4 * (m_e >> 3); col_l = m_e & 7; }
+    auto at = [&](int row_l, int col_l) {
         ConvCoord c;
         c.ho = h0 + row_l;
         c.wo = w0 + col_l;
@@ -339,45 +326,24 @@ __global__ __launch_bounds__(NT, DS_MINBLK) void conv_quad_halo3_kernel(const ds
         c.pix = tr ? (2 * c.ho + (phase >> 1)) * (2 * Wg) + 2 * c.wo + (phase & 1) : c.ho * Wg + c.wo;
         return c;
     };
-    auto coord2 = [&](int i, int mm) {                                  // pixel (tile i, lane mm): the contiguous side of halo3_epilogue_rows
-        int row_l, col_l;
-        if constexpr (TWL == 5) { row_l = 2 * wave_e + (i >> 1); col_l = 16 * (i & 1) + mm; }
-        else if constexpr (TWL == 4) { row_l = 4 * wave_e + i; col_l = mm; }
-        else { row_l = 8 * wave_e + i + 4 * (mm >> 3); col_l = mm & 7; }
-        ConvCoord c;
-        c.ho = h0 + row_l;
-        c.wo = w0 + col_l;
-        c.ok = c.ho < Hg && c.wo < Wg;
-        c.pix = tr ? (2 * c.ho + (phase >> 1)) * (2 * Wg) + 2 * c.wo + (phase & 1) : c.ho * Wg + c.wo;
-        return c;
-    };
-    ds_conv_params qp = p;
+    auto coord2 = [&](int i, int mm) { int row_l, col_l; halo_tile_rc<TWL>(wave_e, i, mm, row_l, col_l); return at(row_l, col_l); };      // pixel (tile i, lane mm)
+    auto coord = [&](int i) { return coord2(i, m_e); };
+    // K slice: fp32 partial sums -> slab[kz][b][pixel][roundup(Cout, 8)] through the fp32 epilogue.  (No fold and no residual in this kernel:
+    // the launcher requires it, the compiler is told.)  Transposed: the block's channels are those of ONE phase.
+    const bool raw = p.ksplit > 1;
+    ds_conv_params qp = raw ? conv_kslice_view(p) : p;
     qp.gn_ab = nullptr;
     qp.gn_part = nullptr;
     qp.res = nullptr;
     if (tr) {
-        qp.out_c0 = p.out_c0 - phase * p.Cout;
+        qp.out_c0 -= phase * p.Cout;
         qp.Cout = p.cout_pad;
     }
     float s1 = 0.f, s2 = 0.f;
     const int outHW = tr ? 4 * Hg * Wg : Hg * Wg;
-    const bool raw = p.ksplit > 1;
-    if (raw) {                               // fp32 partial sums of this K slice -> slab[kz][b][pixel][roundup(Cout, 8)] through the fp32 epilogue
-        qp.out = p.slab;
-        qp.out_C = (p.Cout + 7) / 8 * 8;
-        qp.out_c0 = tr ? -phase * p.Cout : 0;
-    }
-#if DS_QUAD_ROWS
     if (raw || (p.flags & DS_CONV_F_OUT_F32)) halo3_epilogue_rows_f32<true, false>(qp, acc, bz, n0, outHW, shl, coord, coord2, smem + OFF_H + wave_e * EPI_F32_WAVE, s1, s2, 1.0f, lane_e);
-#else
-    if (raw || (p.flags & DS_CONV_F_OUT_F32)) halo3_epilogue_hp<DS_ACT_NONE, 2, false>(qp, acc, bz, n0, outHW, shl, coord, s1, s2, 1.0f, lane_e);
-#endif
     else if (p.act == DS_ACT_GELU) halo3_epilogue<DS_ACT_GELU, true, false>(qp, acc, bz, n0, outHW, shl, coord, s1, s2, 1.0f, lane_e);
-#if DS_QUAD_ROWS_BF16
-    else halo3_epilogue_rows<DS_ACT_NONE, true, false>(qp, acc, bz, n0, outHW, shl, coord, coord2, smem + OFF_H + wave_e * (16 * 208), s1, s2, 1.0f, lane_e);
-#else
     else halo3_epilogue<DS_ACT_NONE, true, false>(qp, acc, bz, n0, outHW, shl, coord, s1, s2, 1.0f, lane_e);
-#endif
     __syncthreads();
     if (p.stats_part && !raw) {
         const int parts = gx * gy;
@@ -385,16 +351,10 @@ __global__ __launch_bounds__(NT, DS_MINBLK) void conv_quad_halo3_kernel(const ds
     }
 }
 
-int quad_twl(int W) {
-    int twl = 3;
-    while ((1 << twl) < W && twl < 5) ++twl;
-    return twl;
-}
-
 }  // namespace
 
 int ds_conv_quad_halo3_parts(const ds_conv_params* p) {
-    const int twl = quad_twl(p->Wo), TW = 1 << twl, TH = BM >> twl;
+    const int twl = halo_twl(p->Wo), TW = 1 << twl, TH = BM >> twl;
     return ((p->Ho + TH - 1) / TH) * ((p->Wo + TW - 1) / TW) * (p->cout_pad / BN);
 }
 
@@ -424,7 +384,7 @@ int ds_conv_quad_halo3_launch(const ds_conv_params* p, hipStream_t st) {
     DS_REQUIRE((long long)p->H * p->W * p->C0 * 2 < (1ll << 31) && oHW * p->out_C * (out_f32 ? 4 : 2) < (1ll << 31) &&
                    (long long)(p->transposed ? 1 : 4) * plane_chunks * 4 * p->cout_pad * 64 < (1ll << 31),
                "conv_quad_halo3: one sample / the packed weights must stay below 2 GiB (32-bit buffer offsets)");
-    const int twl = quad_twl(p->Wo), TW = 1 << twl, TH = BM >> twl;
+    const int twl = halo_twl(p->Wo), TW = 1 << twl, TH = BM >> twl;
     dim3 grid(((p->Ho + TH - 1) / TH) * ((p->Wo + TW - 1) / TW), p->cout_pad / BN, p->B * (p->ksplit > 1 ? p->ksplit : 1));
 #if DS_BOUNDS
     {

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(RED_BLOCK) void splitk_reduce_kernel(const ds_conv_
     }
     // the statistics reduction is a WAVE collective (every lane contributes partials): all threads run it, also those of a ragged last wave
     float ga = 1.f, gam = 0.f;
-    const bool fold = p.gn_ab || p.gn_part;
+    const bool fold = CONV_FOLD(p);
     if (fold) {
         if (p.gn_part) {
             gn_from_partials(p.gn_part, p.gn_parts, p.gn_count, p.gn_eps, b, ga, gam);
@@ -54,17 +54,12 @@ __global__ __launch_bounds__(RED_BLOCK) void splitk_reduce_kernel(const ds_conv_
         if (fold) {
             if (p.ncls == 9) {
                 const int ho = pix / oW, wo = pix - ho * oW;
-                cls = (ho == 0 ? 0 : (ho == oH - 1 ? 2 : 1)) * 3 + (wo == 0 ? 0 : (wo == oW - 1 ? 2 : 1));
+                cls = conv_border_class(ho, wo, oH, oW);
             }
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            float sh = 0.f;
-            if (n + q < p.Cout) {
-                if (fold) sh = DS_LD(float, p.fold_t1 + cls * p.Cout + n + q, DS_BX_T1) - gam * DS_LD(float, p.fold_t2 + cls * p.Cout + n + q, DS_BX_T2);
-                else if (p.bias) sh = DS_LD(float, p.bias + n + q, DS_BX_BIAS);
-            }
-            v[q] = ga * v[q] + sh;
+            v[q] = ga * v[q] + conv_shift_entry(p, fold, cls, n, gam, q);
             if (p.act == DS_ACT_GELU) v[q] = gelu_fast(v[q]);
         }
         const int out_mode = (p.flags >> 1) & 3;                     // DS_CONV_F_*: 1 = hi / lo bf16 planes (exact-erf GELU upstream), 2 = fp32 (+ fp32 residual)
