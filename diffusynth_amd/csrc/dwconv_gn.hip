@@ -12,6 +12,71 @@ namespace {
 constexpr int DW_TH = 4;
 constexpr int DW_BLOCK = 256;
 
+// The source the channels from c0 on come from (the skip concat is two sources, the second one shorter and offset): one sample's base, its
+// extents, the channel inside it, the offset of its origin in output coordinates and its DS_BOUNDS buffer.  ES = bytes per element.
+struct DwSrc { const char* base; int Cs, cc, Hs, Ws, oh, ow, buf; };
+template <int ES>
+__device__ __forceinline__ DwSrc dw_src(const ds_dwconv_params& p, int b, int c0) {
+    if (c0 < p.C0) return {reinterpret_cast<const char*>(p.src0) + (size_t)b * p.H * p.W * p.C0 * ES, p.C0, c0, p.H, p.W, 0, 0, DS_BX_SRC0};
+    return {reinterpret_cast<const char*>(p.src1) + (size_t)b * p.H1 * p.W1 * p.C1 * ES, p.C1, c0 - p.C0, p.H1, p.W1, p.off_h1, p.off_w1, DS_BX_SRC1};
+}
+
+// One tap column of the stencil for a thread that owns SR consecutive output rows of one channel vector: the column's 7 weights from LDS
+// (wcol = the column's first tap at the thread's channels, `pitch` floats from one tap row to the next), then SR + 6 input rows
+// (load_row(r, x)), every value feeding up to 7 outputs.  The tile and the strip kernel share it: the same operation order per output.
+template <int SR, int V, typename LoadRow>
+__device__ __forceinline__ void dw_tap_column(float (&acc)[SR][V], const float* wcol, int pitch, LoadRow load_row) {
+    float wv[7][V];
+#pragma unroll
+    for (int dh = 0; dh < 7; ++dh)
+#pragma unroll
+        for (int v = 0; v < V; v += 4) {
+            const f32x4 t4 = *reinterpret_cast<const f32x4*>(wcol + dh * pitch + v);
+            wv[dh][v] = t4[0]; wv[dh][v + 1] = t4[1]; wv[dh][v + 2] = t4[2]; wv[dh][v + 3] = t4[3];
+        }
+#pragma unroll
+    for (int r = 0; r < SR + 6; ++r) {
+        float x[V];
+        load_row(r, x);
+#pragma unroll
+        for (int dh = 0; dh < 7; ++dh) {
+            const int o = r - dh;
+            if (o >= 0 && o < SR) {
+#pragma unroll
+                for (int v = 0; v < V; ++v) acc[o][v] = fmaf(x[v], wv[dh][v], acc[o][v]);
+            }
+        }
+    }
+}
+
+// Stores the channel vector a[] at channel c of output pixel (h, w) of sample b and adds it to the GroupNorm sums s = (sum, sum of squares),
+// which it returns.  The direct, the tile and the strip kernel share it: one statistics order.  `split` (fp32 only, the
+// split-precision tier): the result as two bf16 planes (hi, then lo = v - hi) of a 2C-channel image, the input format of the split 3x3
+// convolution that follows (DS_CONV_F_SPLIT_IN).  (r05 ablation: hi | lo of a block's 32 channels as ONE 128-byte line per pixel instead
+// of two 64-byte runs in two planes: no consistent gain, 613 vs 595 and 591 vs 623 us on the two layer shapes tried — the plane layout stays)
+// The sums go in and out by value and the row comes as a plain pointer: with reference parameters hipcc pairs the sums differently in
+// its SLP pass (other floating-point instructions in the fp32 kernels, so possibly other bits in stats_part).
+template <typename T>
+__device__ __forceinline__ float2 dw_store_row(const ds_dwconv_params& p, bool split, int b, int h, int w, int C, int c, const float* a, float2 s) {
+    if (split) {
+        bf16* o2 = reinterpret_cast<bf16*>(p.out) + ((size_t)b * p.H * p.W + (size_t)(h * p.W + w)) * (2 * C) + c;
+        uint2 hi, lo;
+        ds_split2(a[0], a[1], hi.x, lo.x);
+        ds_split2(a[2], a[3], hi.y, lo.y);
+        DS_ST(bf16x4, o2, DS_BX_OUT, __builtin_bit_cast(bf16x4, hi));
+        DS_ST(bf16x4, o2 + C, DS_BX_OUT, __builtin_bit_cast(bf16x4, lo));
+    } else {
+        T* outp = reinterpret_cast<T*>(p.out) + (size_t)b * p.H * p.W * C;
+        vec16_store<T>(outp + ((size_t)(h * p.W + w) * C + c), a, DS_BX_OUT);
+    }
+#pragma unroll
+    for (int v = 0; v < Vec16<T>::N; ++v) {
+        s.x += a[v];
+        s.y += a[v] * a[v];
+    }
+    return s;
+}
+
 template <typename T>
 __global__ __launch_bounds__(DW_BLOCK) void dwconv7_kernel(const ds_dwconv_params p, int nstrip, int CV) {
     constexpr int V = Vec16<T>::N;
@@ -20,22 +85,15 @@ __global__ __launch_bounds__(DW_BLOCK) void dwconv7_kernel(const ds_dwconv_param
     const int b = blockIdx.y;
     const long gid = (long)blockIdx.x * DW_BLOCK + threadIdx.x;
     const long total = (long)nstrip * p.W * CV;
-    float s1 = 0.f, s2 = 0.f;
+    float2 st = {0.f, 0.f};                                   // the block's GroupNorm sums (sum, sum of squares)
     if (gid < total) {
         const int cv = gid % CV;
         const int w = (gid / CV) % p.W;
         const int strip = gid / ((long)CV * p.W);
         const int h0 = strip * DW_TH;
         const int c = cv * V;
-        const T* base;
-        int Cs, cc, Hs, Ws, oh, ow;
-        if (c < p.C0) {
-            base = reinterpret_cast<const T*>(p.src0) + (size_t)b * p.H * p.W * p.C0;
-            Cs = p.C0; cc = c; Hs = p.H; Ws = p.W; oh = 0; ow = 0;
-        } else {
-            base = reinterpret_cast<const T*>(p.src1) + (size_t)b * p.H1 * p.W1 * p.C1;
-            Cs = p.C1; cc = c - p.C0; Hs = p.H1; Ws = p.W1; oh = p.off_h1; ow = p.off_w1;
-        }
+        const DwSrc s = dw_src<sizeof(T)>(p, b, c);
+        const T* base = reinterpret_cast<const T*>(s.base);
         float acc[DW_TH][V];
         float init[V];
 #pragma unroll
@@ -49,14 +107,14 @@ __global__ __launch_bounds__(DW_BLOCK) void dwconv7_kernel(const ds_dwconv_param
             for (int v = 0; v < V; ++v) acc[t][v] = init[v];
 
         for (int dw = 0; dw < 7; ++dw) {
-            const int wi = w + dw - 3 - ow;
-            if ((unsigned)wi >= (unsigned)Ws) continue;  // zero column
+            const int wi = w + dw - 3 - s.ow;
+            if ((unsigned)wi >= (unsigned)s.Ws) continue;  // zero column
             float col[DW_TH + 6][V];
 #pragma unroll
             for (int r = 0; r < DW_TH + 6; ++r) {
-                const int hi = h0 + r - 3 - oh;
-                if ((unsigned)hi < (unsigned)Hs) {
-                    vec16_load<T>(base + ((size_t)(hi * Ws + wi) * Cs + cc), col[r], c < p.C0 ? DS_BX_SRC0 : DS_BX_SRC1);
+                const int hi = h0 + r - 3 - s.oh;
+                if ((unsigned)hi < (unsigned)s.Hs) {
+                    vec16_load<T>(base + ((size_t)(hi * s.Ws + wi) * s.Cs + s.cc), col[r], s.buf);
                 } else {
 #pragma unroll
                     for (int v = 0; v < V; ++v) col[r][v] = 0.f;
@@ -77,21 +135,11 @@ __global__ __launch_bounds__(DW_BLOCK) void dwconv7_kernel(const ds_dwconv_param
                     for (int v = 0; v < V; ++v) acc[t][v] = fmaf(col[t + dh][v], wv[v], acc[t][v]);
             }
         }
-        T* outp = reinterpret_cast<T*>(p.out) + (size_t)b * p.H * p.W * C;
 #pragma unroll
-        for (int t = 0; t < DW_TH; ++t) {
-            const int h = h0 + t;
-            if (h < p.H) {
-                vec16_store<T>(outp + ((size_t)(h * p.W + w) * C + c), acc[t], DS_BX_OUT);
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    s1 += acc[t][v];
-                    s2 += acc[t][v] * acc[t][v];
-                }
-            }
-        }
+        for (int t = 0; t < DW_TH; ++t)
+            if (h0 + t < p.H) st = dw_store_row<T>(p, false, b, h0 + t, w, C, c, acc[t], st);
     }
-    if (p.stats_part) block_stats_write(s1, s2, red, p.stats_part + ((size_t)b * gridDim.x + blockIdx.x) * 2);
+    if (p.stats_part) block_stats_write(st.x, st.y, red, p.stats_part + ((size_t)b * gridDim.x + blockIdx.x) * 2);
 }
 
 // ------------------------------------------------------------------------------------------------ dwconv7, LDS-tiled
@@ -105,13 +153,9 @@ __global__ __launch_bounds__(DW_BLOCK) void dwconv7_kernel(const ds_dwconv_param
 // end of r03; fp32 tensors whose channel counts allow it now take NV = 8 (32 channels = one whole 128-byte line per pixel, a 256-pixel tile):
 // with 16 channels the kernel moved 64-byte load pieces and 32-byte store pieces and sat at the L2's REQUEST rate (C = 192 at 256x64: 182 M
 // requests in 1360 us = 134 G/s with six of its seven tap columns removed, i.e. without its arithmetic) — not at a byte rate.  2 measured slower.
-#ifndef DS_DW_SR
-// output rows per thread of the LDS-tile kernel.  r04: 8 (256 threads per block) — per tap column a thread reads 7 weight + 14 input vectors for
-// 8 x 7 outputs instead of 7 + 10 for 4 x 7 (38 % fewer LDS reads per output; the kernel is LDS-bound where it is not HBM-bound): 4 - 6 % per
-// layer at the split-precision tier's shapes (same box, tools/ab.sh -m dw -a "--dtype fp32split"); 16 rows (128 threads: too few waves) is 12 - 25 % slower than 4
-#define DS_DW_SR 8
-#endif
-constexpr int LT_SR = DS_DW_SR;
+// Output rows per thread of the tile and the strip kernel: per tap column a thread reads 7 weight + 14 input vectors for 8 x 7 outputs
+// (38 % fewer LDS reads per output than at 4 rows; the kernels are LDS-bound where they are not HBM-bound).  4 and 16 rows: DESIGN, retired switches.
+constexpr int LT_SR = 8;
 constexpr int LT_NT = 2048 / LT_SR;                             // threads: channel vectors x tile columns x row strips = NV x (2048 / NV pixels) / LT_SR
 template <int TWL, int NV>
 struct LT {
@@ -130,41 +174,26 @@ __global__ __launch_bounds__(LT_NT) void dwconv7_lds_kernel(const ds_dwconv_para
     float* wsm = reinterpret_cast<float*>(dsm + (size_t)LT_NPX * LT_NV * 16);          // [49][CB]
     float* red = wsm + 49 * CB;
     const int tid = threadIdx.x;
-    // Block order: channel block fastest, then the tile, then the sample (plain hardware order).  r04 tried the XCD-chunked order of the 3x3
-    // kernels here (-DDS_DW_XCD: the tiles of one (sample, channel block) plane consecutive on ONE XCD, so that the 6 halo rows / columns a
-    // tile shares with its neighbours come from that XCD's L2 — the kernel fetches 1.47 x its input from HBM in plain order, PMC FETCH_SIZE):
-    // 456 -> 483 us average on the fp32 levels, same box.  A plane's tiles then stream from the same few HBM channels at once; the plain
-    // order spreads every moment's requests over all of them, and this kernel is bound by bytes in flight, not by bytes.
-    const int gx0 = gridDim.x, nwg = gx0 * gridDim.y;
-    int wid = blockIdx.x + gx0 * blockIdx.y;
-#ifdef DS_DW_XCD
-    if ((nwg & 7) == 0) wid = (wid & 7) * (nwg >> 3) + (wid >> 3);
-    const int tile = wid % tiles_hw, cblk = (wid / tiles_hw) % ncblk, b = wid / (tiles_hw * ncblk);
-#else
-    (void)nwg;
+    // Block order: channel block fastest, then the tile, then the sample (plain hardware order).  The XCD-chunked order of the 3x3 kernels
+    // (a plane's tiles consecutive on ONE XCD, for the halo rows / columns they share) measured slower (DESIGN, retired switches): a plane's
+    // tiles then stream from the same few HBM channels at once; the plain order spreads every moment's requests over all of them, and this
+    // kernel is bound by bytes in flight, not by bytes.
+    const int wid = blockIdx.x + gridDim.x * blockIdx.y;
     const int cblk = wid % ncblk, tile = (wid / ncblk) % tiles_hw, b = wid / (tiles_hw * ncblk);
-#endif
     const int bix = tile * ncblk + cblk;                      // (the block's slot in its sample's statistics partials: order-independent sum)
     const int th = tile / tiles_w, tw = tile - th * tiles_w;
     const int h0 = th * LT_H, w0 = tw * LT_W, c0 = cblk * CB;
     const int C = p.C0 + p.C1;
-    const T* base;
-    int Cs, cc, Hs, Ws, oh, ow;
-    if (c0 < p.C0) {
-        base = reinterpret_cast<const T*>(p.src0) + (size_t)b * p.H * p.W * p.C0;
-        Cs = p.C0; cc = c0; Hs = p.H; Ws = p.W; oh = 0; ow = 0;
-    } else {
-        base = reinterpret_cast<const T*>(p.src1) + (size_t)b * p.H1 * p.W1 * p.C1;
-        Cs = p.C1; cc = c0 - p.C0; Hs = p.H1; Ws = p.W1; oh = p.off_h1; ow = p.off_w1;
-    }
+    const DwSrc s = dw_src<sizeof(T)>(p, b, c0);
+    const T* base = reinterpret_cast<const T*>(s.base);
 #if DS_BOUNDS
     for (int slot = tid; slot < LT_NPX * LT_NV; slot += LT_NT) {
         const int px = slot / LT_NV, v = slot - px * LT_NV;
         const int hr = px / LT_HC, hc = px - hr * LT_HC;
-        const int hi = h0 + hr - 3 - oh, wi = w0 + hc - 3 - ow;
+        const int hi = h0 + hr - 3 - s.oh, wi = w0 + hc - 3 - s.ow;
         uint4 val = make_uint4(0, 0, 0, 0);
-        if ((unsigned)hi < (unsigned)Hs && (unsigned)wi < (unsigned)Ws)
-            val = DS_LD(uint4, base + ((size_t)(hi * Ws + wi) * Cs + cc + v * V), c0 < p.C0 ? DS_BX_SRC0 : DS_BX_SRC1);
+        if ((unsigned)hi < (unsigned)s.Hs && (unsigned)wi < (unsigned)s.Ws)
+            val = DS_LD(uint4, base + ((size_t)(hi * s.Ws + wi) * s.Cs + s.cc + v * V), s.buf);
         xs[slot] = val;
     }
     for (int i = tid; i < 49 * CB; i += LT_NT) wsm[i] = DS_LD(float, p.wt + (size_t)(i / CB) * C + c0 + (i % CB), DS_BX_W);
@@ -174,7 +203,7 @@ __global__ __launch_bounds__(LT_NT) void dwconv7_lds_kernel(const ds_dwconv_para
         // out-of-range offsets (bit 31 set = beyond any sample; the launcher keeps samples below 2 GB) — `if (inside) v = load` is an
         // exec-masked region per iteration that waits for its own load before the next one is issued (seven serial round trips)
         constexpr int SLOTS = LT_NPX * LT_NV, ITS = (SLOTS + LT_NT - 1) / LT_NT;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), (short)0, (int)((size_t)Hs * Ws * Cs * sizeof(T)), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), (short)0, (int)((size_t)s.Hs * s.Ws * s.Cs * sizeof(T)), 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wt), (short)0, 49 * C * 4, 0x00020000);
         u32x4 hv[ITS];
 #pragma unroll
@@ -182,9 +211,9 @@ __global__ __launch_bounds__(LT_NT) void dwconv7_lds_kernel(const ds_dwconv_para
             const int slot = tid + it * LT_NT;
             const int px = slot / LT_NV, v = slot - px * LT_NV;
             const int hr = px / LT_HC, hc = px - hr * LT_HC;
-            const int hi = h0 + hr - 3 - oh, wi = w0 + hc - 3 - ow;
-            const unsigned bad = (unsigned)(slot >= SLOTS) | (unsigned)((unsigned)hi >= (unsigned)Hs) | (unsigned)((unsigned)wi >= (unsigned)Ws);
-            const unsigned off = (unsigned)((hi * Ws + wi) * Cs + cc + v * V) * (unsigned)sizeof(T);
+            const int hi = h0 + hr - 3 - s.oh, wi = w0 + hc - 3 - s.ow;
+            const unsigned bad = (unsigned)(slot >= SLOTS) | (unsigned)((unsigned)hi >= (unsigned)s.Hs) | (unsigned)((unsigned)wi >= (unsigned)s.Ws);
+            const unsigned off = (unsigned)((hi * s.Ws + wi) * s.Cs + s.cc + v * V) * (unsigned)sizeof(T);
             hv[it] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((off & 0x7fffffffu) | (bad << 31)), 0, 0);
         }
         // the block's 49 x CB weights: one 16-byte piece per thread (CB / 4 pieces per tap)
@@ -236,56 +265,18 @@ __global__ __launch_bounds__(LT_NT) void dwconv7_lds_kernel(const ds_dwconv_para
             for (int v = 0; v < V; ++v) acc[o][v] = init[v];
     }
 #pragma unroll 1
-    for (int dw = 0; dw < 7; ++dw) {   // not unrolled: keeps only one tap column of weights + inputs live
-        float wv[7][V];
-#pragma unroll
-        for (int dh = 0; dh < 7; ++dh)
-#pragma unroll
-            for (int v = 0; v < V; v += 4) {
-                const f32x4 t4 = *reinterpret_cast<const f32x4*>(wsm + (dh * 7 + dw) * CB + cv * V + v);
-                wv[dh][v] = t4[0]; wv[dh][v + 1] = t4[1]; wv[dh][v + 2] = t4[2]; wv[dh][v + 3] = t4[3];
-            }
-#pragma unroll
-        for (int r = 0; r < LT_SR + 6; ++r) {
-            float x[V];
+    for (int dw = 0; dw < 7; ++dw)     // not unrolled: keeps only one tap column of weights + inputs live
+        dw_tap_column<LT_SR, V>(acc, wsm + dw * CB + cv * V, 7 * CB, [&](int r, float* x) {
             Vec16<T>::load(reinterpret_cast<const T*>(xs + ((strip * LT_SR + r) * LT_HC + wl + dw) * LT_NV + cv), x);
-#pragma unroll
-            for (int dh = 0; dh < 7; ++dh) {
-                const int o = r - dh;
-                if (o >= 0 && o < LT_SR) {
-#pragma unroll
-                    for (int v = 0; v < V; ++v) acc[o][v] = fmaf(x[v], wv[dh][v], acc[o][v]);
-                }
-            }
-        }
-    }
-    float s1 = 0.f, s2 = 0.f;
-    T* outp = reinterpret_cast<T*>(p.out) + (size_t)b * p.H * p.W * C;
+        });
+    float2 st = {0.f, 0.f};
     const int w = w0 + wl;
 #pragma unroll
     for (int o = 0; o < LT_SR; ++o) {
         const int h = h0 + strip * LT_SR + o;
-        if (h < p.H && w < p.W) {
-            if constexpr (sizeof(T) == 4) {
-                if (p.out_split) {
-                    // split-precision tier: the fp32 result as two bf16 planes (hi, then lo = v - hi) of a 2C-channel image,
-                    // the input format of the split 3x3 convolution that follows (DS_CONV_F_SPLIT_IN)
-                    bf16* o2 = reinterpret_cast<bf16*>(p.out) + ((size_t)b * p.H * p.W + (size_t)(h * p.W + w)) * (2 * C) + c;
-                    uint2 hi, lo;
-                    ds_split2(acc[o][0], acc[o][1], hi.x, lo.x);
-                    ds_split2(acc[o][2], acc[o][3], hi.y, lo.y);
-                    DS_ST(bf16x4, o2, DS_BX_OUT, __builtin_bit_cast(bf16x4, hi));
-                    DS_ST(bf16x4, o2 + C, DS_BX_OUT, __builtin_bit_cast(bf16x4, lo));
-                } else vec16_store<T>(outp + ((size_t)(h * p.W + w) * C + c), acc[o], DS_BX_OUT);
-            } else vec16_store<T>(outp + ((size_t)(h * p.W + w) * C + c), acc[o], DS_BX_OUT);
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                s1 += acc[o][v];
-                s2 += acc[o][v] * acc[o][v];
-            }
-        }
+        if (h < p.H && w < p.W) st = dw_store_row<T>(p, sizeof(T) == 4 && p.out_split, b, h, w, C, c, acc[o], st);
     }
-    if (p.stats_part) block_stats_write(s1, s2, red, p.stats_part + ((size_t)b * gridDim.x + bix) * 2);
+    if (p.stats_part) block_stats_write(st.x, st.y, red, p.stats_part + ((size_t)b * gridDim.x + bix) * 2);
 }
 
 // ------------------------------------------------------------------------------------------------ dwconv7, LDS ring over a column strip (r05)
@@ -295,14 +286,13 @@ __global__ __launch_bounds__(LT_NT) void dwconv7_lds_kernel(const ds_dwconv_para
 // block) and WALKS DOWN it, 16 output rows per iteration, over a ring of 22 input rows in LDS: every input row of the strip leaves HBM once,
 // whatever the caches do (only the 6 halo COLUMNS of a strip are read twice, by its neighbour strips: 22 / 16 from L2, 19 - 22 of 16 real).
 // The 16 new rows of iteration t + 1 are requested BEFORE the arithmetic of iteration t (64 registers in flight per lane) and enter the ring
-// after it; the outputs of iteration t leave after that refill, so the refill waits for its loads only, not for stores.  Same thread map,
-// same per-output operation order as the tile kernel (bit-identical outputs); one statistics partial per strip instead of per tile.
+// after it; the outputs of iteration t leave after that refill, so the refill waits for its loads only, not for stores.  The tile kernel's
+// thread map and its stencil (dw_tap_column): bit-identical outputs; one statistics partial per strip instead of per tile.
 // fp32 tensors with 32-channel blocks (NV = 8) and the split-precision tier's plane output only: that is where the bytes are.
 constexpr int ST_W = 16, ST_R = 16, ST_HC = ST_W + 6, ST_HR = ST_R + 6, ST_NT = 256;
 constexpr int ST_ROWB = ST_HC * 8 * 16;                 // bytes per ring row: 22 pixels x 128 B
 constexpr int ST_XS = ST_HR * ST_ROWB;                  // 61 952
 constexpr int ST_LDS = ST_XS + 49 * 32 * 4 + 64;
-static_assert(LT_SR == 8, "the strip kernel's thread map is the tile kernel's at eight rows per thread");
 
 __global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv_params p, int strips_w, int ncblk, int hparts, int rows_per_part) {
     extern __shared__ __attribute__((aligned(16))) char dsm[];
@@ -320,35 +310,27 @@ __global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv
     const int hbeg = hp * rows_per_part, hend = min(p.H, hbeg + rows_per_part);
     const int ntile = (hend - hbeg + ST_R - 1) / ST_R;
     const int C = p.C0 + p.C1;
-    const float* base;
-    int Cs, cc, Hs, Ws, oh, ow;
-    if (c0 < p.C0) {
-        base = reinterpret_cast<const float*>(p.src0) + (size_t)b * p.H * p.W * p.C0;
-        Cs = p.C0; cc = c0; Hs = p.H; Ws = p.W; oh = 0; ow = 0;
-    } else {
-        base = reinterpret_cast<const float*>(p.src1) + (size_t)b * p.H1 * p.W1 * p.C1;
-        Cs = p.C1; cc = c0 - p.C0; Hs = p.H1; Ws = p.W1; oh = p.off_h1; ow = p.off_w1;
-    }
+    const DwSrc s = dw_src<4>(p, b, c0);
     // ---- staging map: thread -> (halo column hc = tid >> 3 < 22, 16-byte piece v = tid & 7); row `it` of a batch of rows.  Waves 0, 1 are
     // fully active, wave 2 three quarters, wave 3 not at all (its branch is wave-uniform)
     const int hc = tid >> 3, sv = tid & 7;
     const bool stager = hc < ST_HC;
-    const int wi = w0 + hc - 3 - ow;
-    const bool col_ok = stager && (unsigned)wi < (unsigned)Ws;
-    const unsigned colbyte = (unsigned)((wi * Cs + cc + sv * 4) * 4);       // byte offset inside an image row (garbage when !col_ok: masked below)
-    const unsigned rowpitch = (unsigned)(Ws * Cs * 4);
+    const int wi = w0 + hc - 3 - s.ow;
+    const bool col_ok = stager && (unsigned)wi < (unsigned)s.Ws;
+    const unsigned colbyte = (unsigned)((wi * s.Cs + s.cc + sv * 4) * 4);   // byte offset inside an image row (garbage when !col_ok: masked below)
+    const unsigned rowpitch = (unsigned)(s.Ws * s.Cs * 4);
 #if !DS_BOUNDS
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, (int)((size_t)Hs * Ws * Cs * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(s.base), (short)0, (int)((size_t)s.Hs * s.Ws * s.Cs * 4), 0x00020000);
 #endif
     auto load_rows = [&](u32x4* dst, int row0, auto nc) {                    // image rows row0 .. row0 + n - 1 (this source's coordinates: - oh)
         constexpr int n = decltype(nc)::value;
 #pragma unroll
         for (int it = 0; it < n; ++it) {
-            const int hi = row0 + it - oh;
-            const unsigned bad = (unsigned)(!col_ok) | (unsigned)((unsigned)hi >= (unsigned)Hs);
+            const int hi = row0 + it - s.oh;
+            const unsigned bad = (unsigned)(!col_ok) | (unsigned)((unsigned)hi >= (unsigned)s.Hs);
 #if DS_BOUNDS
             dst[it] = u32x4{0u, 0u, 0u, 0u};
-            if (!bad) dst[it] = DS_LD(u32x4, reinterpret_cast<const char*>(base) + (size_t)hi * rowpitch + colbyte, c0 < p.C0 ? DS_BX_SRC0 : DS_BX_SRC1);
+            if (!bad) dst[it] = DS_LD(u32x4, s.base + (size_t)hi * rowpitch + colbyte, s.buf);
 #else
             const unsigned off = (unsigned)hi * rowpitch + colbyte;
             dst[it] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((off & 0x7fffffffu) | (bad << 31)), 0, 0);
@@ -403,7 +385,7 @@ __global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv
     }
     lds_barrier();
 
-    float s1 = 0.f, s2 = 0.f;
+    float2 st = {0.f, 0.f};
     int rbase = 0;                                               // ring slot of the tile's first input row (output row - 3)
     const int w = w0 + wl;
     const int colb = wl * 128 + cv * 16;
@@ -427,26 +409,10 @@ __global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv
 #pragma unroll
             for (int v = 0; v < 4; ++v) acc[o][v] = init[v];
 #pragma unroll 1
-        for (int dw = 0; dw < 7; ++dw) {   // not unrolled: keeps only one tap column of weights + inputs live
-            float wv[7][4];
-#pragma unroll
-            for (int dh = 0; dh < 7; ++dh) {
-                const f32x4 t4 = *reinterpret_cast<const f32x4*>(wsm + (dh * 7 + dw) * 32 + cv * 4);
-                wv[dh][0] = t4[0]; wv[dh][1] = t4[1]; wv[dh][2] = t4[2]; wv[dh][3] = t4[3];
-            }
-#pragma unroll
-            for (int r = 0; r < LT_SR + 6; ++r) {
-                const f32x4 x = *reinterpret_cast<const f32x4*>(xs + roff[r] + dw * 128);
-#pragma unroll
-                for (int dh = 0; dh < 7; ++dh) {
-                    const int o = r - dh;
-                    if (o >= 0 && o < LT_SR) {
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) acc[o][v] = fmaf(x[v], wv[dh][v], acc[o][v]);
-                    }
-                }
-            }
-        }
+        for (int dw = 0; dw < 7; ++dw)     // not unrolled: keeps only one tap column of weights + inputs live
+            dw_tap_column<LT_SR, 4>(acc, wsm + dw * 32 + cv * 4, 7 * 32, [&](int r, float* x) {
+                Vec16<float>::load(reinterpret_cast<const float*>(xs + roff[r] + dw * 128), x);
+            });
         lds_barrier();                                           // every wave has read what it needs of this tile's rows
         if (more) {
             int ws = rbase + ST_R + 6;                           // slot of the next tile's row 6 = this tile's row 22 -> (rbase + 22) mod 22 = rbase
@@ -459,34 +425,15 @@ __global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv
 #pragma unroll
         for (int o = 0; o < LT_SR; ++o) {
             const int h = htop + strip * LT_SR + o;
-            if (h < hend && w < p.W) {
-                if (p.out_split) {
-                    bf16* o2 = reinterpret_cast<bf16*>(p.out) + ((size_t)b * p.H * p.W + (size_t)(h * p.W + w)) * (2 * C) + c;
-                    uint2 hi, lo;
-                    ds_split2(acc[o][0], acc[o][1], hi.x, lo.x);
-                    ds_split2(acc[o][2], acc[o][3], hi.y, lo.y);
-                    // (r05 ablation: hi | lo of the block's 32 channels as ONE 128-byte line per pixel instead of two 64-byte runs in two planes:
-                    // no consistent gain, 613 vs 595 and 591 vs 623 us on the two layer shapes tried — the plane layout stays)
-                    DS_ST(bf16x4, o2, DS_BX_OUT, __builtin_bit_cast(bf16x4, hi));
-                    DS_ST(bf16x4, o2 + C, DS_BX_OUT, __builtin_bit_cast(bf16x4, lo));
-                } else {
-                    float* o4 = reinterpret_cast<float*>(p.out) + ((size_t)b * p.H * p.W + (size_t)(h * p.W + w)) * C + c;
-                    DS_ST(f32x4, o4, DS_BX_OUT, (f32x4{acc[o][0], acc[o][1], acc[o][2], acc[o][3]}));
-                }
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    s1 += acc[o][v];
-                    s2 += acc[o][v] * acc[o][v];
-                }
-            }
+            if (h < hend && w < p.W) st = dw_store_row<float>(p, p.out_split, b, h, w, C, c, acc[o], st);
         }
         if (more) lds_barrier();                                 // the refilled rows are visible
     }
     __syncthreads();
-    if (p.stats_part) block_stats_write(s1, s2, red, p.stats_part + ((size_t)b * (hparts * strips_w * ncblk) + bix) * 2);
+    if (p.stats_part) block_stats_write(st.x, st.y, red, p.stats_part + ((size_t)b * (hparts * strips_w * ncblk) + bix) * 2);
 }
 
-// ------------------------------------------------------------------------------------------------ dwconv7 on MFMA
+// ------------------------------------------------------------------------------------------------ dwconv7 on MFMA, persistent blocks
 // The VALU stencil above needs 49 fma + conversions per output and is issue-bound at ~2x its own floor.  Here the
 // horizontal part of the stencil becomes a banded (Toeplitz) matrix, so one channel's 16x16 output block is
 //     out[h][w] = sum_{dh} sum_{w'} x[h+dh][w'] * T_c[(dh,w')][w],   T_c[(dh,w')][w] = k_c[dh][w'-w]  (0 <= w'-w < 7)
@@ -497,11 +444,7 @@ __global__ __launch_bounds__(ST_NT, 2) void dwconv7_strip_kernel(const ds_dwconv
 //   K order: MFMA ks, lane group kq -> (dh, wg) = (4 * (ks & 1) + kq, ks >> 1): the four lane groups of one read differ by whole plane
 //   rows only, so the 16 lanes of every ds_read_b128 group touch distinct (or identical) rows and, with the 80- / 48-byte row pitch,
 //   distinct bank slots (the order (dh, wg) = (G / 3, G % 3) made every read a 2-way conflict).  dh = 7 is padding: row 6 again, zero weights.
-// (The first generation of this kernel — one block per tile and 32 channels, two blocks per CU, 2.65 TB/s — is in the history up to round 3.)
-constexpr int MF_CB = 32;
-
-// ------------------------------------------------------------------------------------------------ dwconv7 on MFMA, persistent blocks
-// One block per tile (the first generation) is bound by latency and instruction issue, not by a
+// One block per tile of 32 channels (the first generation: two blocks per CU, 2.65 TB/s) is bound by latency and instruction issue, not by a
 // pipe (profiles/r03_dw_pmc.txt: 48 % of wave cycles in s_waitcnt, MFMA pipe 11 % busy, LDS 42 %): every block pays one exposed memory round
 // trip for its halo and re-fetches 24 KB of Toeplitz fragments per wave (192 KB per block against 53 KB of input).  Here ONE block per CU
 // walks over CHUNKS of up to 8 tiles of one (sample, 32-channel block):
@@ -516,6 +459,7 @@ constexpr int MF_CB = 32;
 // Chunks are dealt round-robin to the blocks in the XCD-chunked block order, channel block fastest: the blocks of one XCD work on the
 // channel blocks of the same tiles at the same time (they share every 128-byte line of the input).
 // two tile shapes of 512 pixels (two 16 x 16 MFMA blocks): WIDE 16 rows x 32 columns, TALL 32 rows x 16 columns for images at most 16 wide
+constexpr int MF_CB = 32;
 template <bool TALL> struct M2 {
     static constexpr int W = TALL ? 16 : 32, H = TALL ? 32 : 16;
     static constexpr int HR = H + 6;                                   // halo rows
@@ -559,18 +503,12 @@ __global__ __launch_bounds__(NW * 64, 1) void dwconv7_mfma2_kernel(const ds_dwco
     // ---- a tile of the sequence: channel block, sample, origin, source (the skip concat is two sources with an offset).  A chunk is
     // g.tpc consecutive (sample, tile) items of ONE channel block — part of a sample's tiles, or several whole samples where an image has
     // only one or two tiles; the divisions run once per chunk, inside a chunk the position advances incrementally (all scalar: wave-uniform)
-    struct Tile { const char* base; dw_rsrc_t rs; int c, j, tile, th, tw, b, c0, h0, w0, Cs, cc, Hs, Ws, oh, ow, sbuf; };
+    struct Tile { dw_rsrc_t rs; int c, j, tile, th, tw, b, c0, h0, w0; DwSrc s; };
     auto set_sample = [&](Tile& t) {
-        if (t.c0 < p.C0) {
-            t.base = reinterpret_cast<const char*>(p.src0) + (size_t)t.b * p.H * p.W * p.C0 * 2;
-            t.Cs = p.C0; t.cc = t.c0; t.Hs = p.H; t.Ws = p.W; t.oh = 0; t.ow = 0; t.sbuf = DS_BX_SRC0;
-        } else {
-            t.base = reinterpret_cast<const char*>(p.src1) + (size_t)t.b * p.H1 * p.W1 * p.C1 * 2;
-            t.Cs = p.C1; t.cc = t.c0 - p.C0; t.Hs = p.H1; t.Ws = p.W1; t.oh = p.off_h1; t.ow = p.off_w1; t.sbuf = DS_BX_SRC1;
-        }
+        t.s = dw_src<2>(p, t.b, t.c0);
         // one sample of the source as a range-checked buffer: halo pixels outside the image carry an out-of-range offset and read as zeros
         // (no select on the loaded data: a select would make the wave wait for the halo right where it is requested)
-        t.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(t.base), (short)0, t.Hs * t.Ws * t.Cs * 2, 0x00020000);
+        t.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(t.s.base), (short)0, t.s.Hs * t.s.Ws * t.s.Cs * 2, 0x00020000);
     };
     auto start_chunk = [&](int c) {
         Tile t;
@@ -616,15 +554,15 @@ __global__ __launch_bounds__(NW * 64, 1) void dwconv7_mfma2_kernel(const ds_dwco
     auto issue_halo = [&](const Tile& t) {
 #pragma unroll
         for (int it = 0; it < SIT; ++it) {
-            const int hi = t.h0 + s_hr[it] - 3 - t.oh, wi = t.w0 + s_hc[it] - 3 - t.ow;
+            const int hi = t.h0 + s_hr[it] - 3 - t.s.oh, wi = t.w0 + s_hc[it] - 3 - t.s.ow;
             // (arithmetic, not a select: any offset with bit 31 set is beyond the buffer.  The offset of a row above the image is garbage: every
             // offset is cut to 28 bits — a sample is far below 256 MB — so that bit 31 plus it plus 16 bytes cannot wrap around 2^32 into the buffer)
-            const unsigned badr = (unsigned)(!s_ok[it]) | (unsigned)((unsigned)hi >= (unsigned)t.Hs);
-            const unsigned o = (unsigned)((hi * t.Ws + wi) * t.Cs + t.cc + sv * 8) * 2u;       // (may be "negative": pixel quads straddle the left edge)
+            const unsigned badr = (unsigned)(!s_ok[it]) | (unsigned)((unsigned)hi >= (unsigned)t.s.Hs);
+            const unsigned o = (unsigned)((hi * t.s.Ws + wi) * t.s.Cs + t.s.cc + sv * 8) * 2u;       // (may be "negative": pixel quads straddle the left edge)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const unsigned bad = badr | (unsigned)((unsigned)(wi + e) >= (unsigned)t.Ws);
-                fv[it][e] = dw_buf_ld16(t.rs, t.base, ((o + (unsigned)(e * t.Cs) * 2u) & 0x0fffffffu) | (bad << 31), t.sbuf);
+                const unsigned bad = badr | (unsigned)((unsigned)(wi + e) >= (unsigned)t.s.Ws);
+                fv[it][e] = dw_buf_ld16(t.rs, t.s.base, ((o + (unsigned)(e * t.s.Cs) * 2u) & 0x0fffffffu) | (bad << 31), t.s.buf);
             }
         }
     };
@@ -802,7 +740,6 @@ static Dw2Geo dw2_geo(const ds_dwconv_params* p) {
     g.total = g.nchunk * g.ncblk;
     return g;
 }
-static int dw2_parts(const Dw2Geo& g) { return (g.tiles >= g.tpc ? g.tiles / g.tpc : 1) * g.ncblk; }   // GroupNorm partials per sample
 
 __global__ void pack_dw_mfma_kernel(const float* w, int C, bf16* dst) {
     // dst[c][ks][lane][j]: B operand of 16x16x32 — lane = (n = lane & 15, kq = lane >> 4), k = ks*32 + kq*8 + j
@@ -1193,35 +1130,62 @@ static DwStrip dw_strip(const ds_dwconv_params* p) {
     return g;
 }
 
-extern "C" int ds_dwconv_stats_parts(const ds_dwconv_params* p) {
-    const int V = p->dtype == DS_BF16 ? 8 : 4;
-    const int C = p->C0 + p->C1;
+// What ds_dwconv7 launches for p: the kernel family, its geometry and the GroupNorm partials per sample that follow from it.  The one place
+// where the families are told apart and a tile or a block is counted: the launcher's grids, the size ds_dwconv_stats_parts gives the
+// partials buffer and the answers of ds_dwconv_launch_choice all read it.
+struct DwPlan {
+    int family;                                   // DS_DW_DIRECT / TILE / STRIP / MFMA
+    int parts;                                    // partials per sample = the per-sample stride of stats_part (tile, direct: blocks per sample)
+    int ranges, samples_per_chunk;                // what ds_dwconv_launch_choice reports
+    Dw2Geo mfma;                                  // the geometry of `family`; the others stay zero
+    DwStrip strip;
+    struct { int nv, twl, tiles_w, tiles_h, ncblk; size_t lds; } tile;
+    struct { int nstrip, CV; } direct;
+};
+static DwPlan dw_plan(const ds_dwconv_params* p) {
+    const int V = p->dtype == DS_BF16 ? 8 : 4, C = p->C0 + p->C1;
+    DwPlan pl{};
+    pl.ranges = pl.samples_per_chunk = 1;
     if (dw_use_mfma(p)) {
-        return dw2_parts(dw2_geo(p));
+        const Dw2Geo& g = pl.mfma = dw2_geo(p);
+        pl.family = DS_DW_MFMA;
+        pl.ranges = g.tiles >= g.tpc ? g.tiles / g.tpc : 1;            // chunks per image, or chunks of whole samples: one partial each
+        pl.samples_per_chunk = g.tpc > g.tiles ? g.tpc / g.tiles : 1;
+        pl.parts = pl.ranges * g.ncblk;
+    } else if (const DwStrip g = dw_strip(p); g.on) {
+        pl.family = DS_DW_STRIP;
+        pl.strip = g;
+        pl.ranges = g.hparts;
+        pl.parts = g.hparts * g.strips_w * g.ncblk;
+    } else if (dw_use_lds(p)) {
+        auto& t = pl.tile;
+        pl.family = DS_DW_TILE;
+        t.nv = lt_nv(p);
+        t.twl = lt_twl(p->W, t.nv);
+        const int tw = 1 << t.twl, th = (2048 / t.nv) >> t.twl;
+        t.tiles_w = (p->W + tw - 1) / tw;
+        t.tiles_h = (p->H + th - 1) / th;
+        t.ncblk = C / (t.nv * V);
+        t.lds = (size_t)(tw + 6) * (th + 6) * t.nv * 16 + (size_t)49 * t.nv * V * sizeof(float) + 64;
+        pl.parts = t.tiles_h * t.tiles_w * t.ncblk;
+    } else {
+        auto& d = pl.direct;
+        pl.family = DS_DW_DIRECT;
+        d.nstrip = (p->H + DW_TH - 1) / DW_TH;
+        d.CV = C / V;
+        pl.parts = (int)(((long)d.nstrip * p->W * d.CV + DW_BLOCK - 1) / DW_BLOCK);         // one partial per block
     }
-    if (const DwStrip g = dw_strip(p); g.on) return g.hparts * g.strips_w * g.ncblk;
-    if (dw_use_lds(p)) {
-        const int nv = lt_nv(p), tw = 1 << lt_twl(p->W, nv), th = 2048 / nv / tw;
-        return ((p->H + th - 1) / th) * ((p->W + tw - 1) / tw) * (C / (nv * V));
-    }
-    const long total = (long)((p->H + DW_TH - 1) / DW_TH) * p->W * (C / V);
-    return (int)((total + DW_BLOCK - 1) / DW_BLOCK);
+    return pl;
 }
+
+extern "C" int ds_dwconv_stats_parts(const ds_dwconv_params* p) { return dw_plan(p).parts; }
 
 extern "C" int ds_dwconv_launch_choice(const ds_dwconv_params* p, int32_t* family, int32_t* ranges, int32_t* samples_per_chunk) {
     DS_REQUIRE(p && family && ranges && samples_per_chunk, "dwconv_launch_choice: null pointer");
-    *ranges = *samples_per_chunk = 1;
-    if (dw_use_mfma(p)) {
-        const Dw2Geo g = dw2_geo(p);
-        *family = DS_DW_MFMA;
-        *ranges = g.tiles >= g.tpc ? g.tiles / g.tpc : 1;
-        *samples_per_chunk = g.tpc > g.tiles ? g.tpc / g.tiles : 1;
-    } else if (const DwStrip g = dw_strip(p); g.on) {
-        *family = DS_DW_STRIP;
-        *ranges = g.hparts;
-    } else {
-        *family = dw_use_lds(p) ? DS_DW_TILE : DS_DW_DIRECT;
-    }
+    const DwPlan pl = dw_plan(p);
+    *family = pl.family;
+    *ranges = pl.ranges;
+    *samples_per_chunk = pl.samples_per_chunk;
     return DS_OK;
 }
 
@@ -1235,17 +1199,16 @@ extern "C" int ds_dwconv7(const ds_dwconv_params* p, void* stream) {
     DS_REQUIRE(p->B > 0 && p->H > 0 && p->W > 0, "dwconv7: empty problem");
     DS_REQUIRE(p->batch_hint >= 0, "dwconv7: batch_hint must be 0 (use B) or the batch the launch decisions look at, got %d", p->batch_hint);
     DS_REQUIRE(p->strip >= 0 && p->strip <= 2, "dwconv7: strip must be 0 (library's choice), 1 (strip kernel) or 2 (tile kernel), got %d", p->strip);
-    DS_REQUIRE(!p->out_split || (p->dtype == DS_F32 && dw_use_lds(p)), "dwconv7: out_split needs the fp32 LDS-tile kernel (channels multiples of %d, samples below 2 GB)", 16);
+    const DwPlan pl = dw_plan(p);
+    DS_REQUIRE(!p->out_split || (p->dtype == DS_F32 && (pl.family == DS_DW_TILE || pl.family == DS_DW_STRIP)),
+               "dwconv7: out_split needs the fp32 LDS-tile kernel (channels multiples of %d, samples below 2 GB)", 16);
     if (!ds_aligned16(p->src0) || !ds_aligned16(p->out) || !ds_aligned16(p->wt) || (p->C1 && !ds_aligned16(p->src1)))
         DS_FAIL(DS_EALIGN, "dwconv7: pointers must be 16-byte aligned");
-    const int nstrip = (p->H + DW_TH - 1) / DW_TH;
-    const int CV = C / V;
-    const int blocks = ds_dwconv_stats_parts(p);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #if DS_BOUNDS
     {
         const long long es = V == 8 ? 2 : 4;
-        DsBxHost h(dw_use_mfma(p) ? DS_K_DWCONV_MFMA : (dw_use_lds(p) ? DS_K_DWCONV_LDS : DS_K_DWCONV));
+        DsBxHost h(pl.family == DS_DW_MFMA ? DS_K_DWCONV_MFMA : (pl.family == DS_DW_DIRECT ? DS_K_DWCONV : DS_K_DWCONV_LDS));   // (the strip kernel reports as the tile kernel)
         h.set(DS_BX_SRC0, p->src0, (long long)p->B * p->H * p->W * p->C0 * es);
         h.set(DS_BX_SRC1, p->C1 ? p->src1 : nullptr, (long long)p->B * p->H1 * p->W1 * p->C1 * es);
         h.set(DS_BX_W, p->wt, (long long)49 * C * 4);
@@ -1253,12 +1216,12 @@ extern "C" int ds_dwconv7(const ds_dwconv_params* p, void* stream) {
         h.set(DS_BX_BIAS, p->bias, (long long)C * 4);
         h.set(DS_BX_AUX1, p->tbias, p->tbias ? ((long long)(p->B - 1) * p->tb_stride + C) * 4 : 0);
         h.set(DS_BX_OUT, p->out, (long long)p->B * p->H * p->W * C * es);
-        h.set(DS_BX_STATS, p->stats_part, (long long)p->B * blocks * 2 * 4);
+        h.set(DS_BX_STATS, p->stats_part, (long long)p->B * pl.parts * 2 * 4);
         h.publish(st);
     }
 #endif
-    if (dw_use_mfma(p)) {
-        const Dw2Geo g = dw2_geo(p);
+    if (pl.family == DS_DW_MFMA) {
+        const Dw2Geo& g = pl.mfma;
         const int nb = g.total < 256 ? g.total : 256;           // one block per CU
         // 16 waves of 2 channels (128 registers per lane); 8 waves of 4 channels (256) measured 25 % slower: too few waves to cover a phase
         if (dw_tall(p)) {
@@ -1269,42 +1232,38 @@ extern "C" int ds_dwconv7(const ds_dwconv_params* p, void* stream) {
             hipLaunchKernelGGL((dwconv7_mfma2_kernel<16, false>), dim3(nb), dim3(1024), M2<false>::LDS, st, *p, g);
         }
         DS_CHECK_LAUNCH("dwconv7_mfma2");
-        return DS_OK;
-    }
-    if (const DwStrip g = dw_strip(p); g.on) {
+    } else if (pl.family == DS_DW_STRIP) {
+        const DwStrip& g = pl.strip;
         // XCD-chunked item order (consecutive items = the channel blocks of one strip on ONE XCD: the 64-byte halves of an output line two
         // channel blocks share merge in that L2; +2 % on 8 of 9 layer shapes, same box; strip fastest instead of channel block fastest: no
         // consistent gain).  r05 timing ablations at C = 96, 256 x 64, batch 128: 555 us whole; arithmetic alone 347 (784 v_pk_fma_f32 per
         // thread and tile: ~12 k cycles per pair of co-resident tiles against 6.3 k of issue slots), stores alone 264, loads alone 157, none 111
         DS_SET_MAX_LDS(dwconv7_strip_kernel, ST_LDS, "dwconv7_strip");
-        hipLaunchKernelGGL(dwconv7_strip_kernel, dim3(blocks * p->B), dim3(ST_NT), ST_LDS, st, *p, g.strips_w, g.ncblk, g.hparts, g.rows_per_part);
+        hipLaunchKernelGGL(dwconv7_strip_kernel, dim3(pl.parts * p->B), dim3(ST_NT), ST_LDS, st, *p, g.strips_w, g.ncblk, g.hparts, g.rows_per_part);
         DS_CHECK_LAUNCH("dwconv7_strip");
-        return DS_OK;
-    }
-    if (dw_use_lds(p)) {
-        const int nv = lt_nv(p), twl = lt_twl(p->W, nv), tw = 1 << twl, th = (2048 / nv) >> twl;
-        const int tiles_w = (p->W + tw - 1) / tw, tiles_h = (p->H + th - 1) / th, ncblk = C / (nv * V);
-        const size_t lds = (size_t)(tw + 6) * (th + 6) * nv * 16 + (size_t)49 * nv * V * sizeof(float) + 64;
+    } else if (pl.family == DS_DW_TILE) {
+        const auto& t = pl.tile;
         // (above 64 KB — the 8-wide tile of NV = 4 and both NV = 8 tiles — a kernel has to ask for its dynamic LDS)
-#define DS_DW_LDS_LAUNCH(T_, TWL_, NV_)                                                                                                            \
-        do {                                                                                                                                      \
-            if (lds > 65536) DS_SET_MAX_LDS((dwconv7_lds_kernel<T_, TWL_, NV_>), lds, "dwconv7_lds");                                              \
-            hipLaunchKernelGGL((dwconv7_lds_kernel<T_, TWL_, NV_>), dim3(blocks, p->B), dim3(LT_NT), lds, st, *p, tiles_w, tiles_w * tiles_h, ncblk); \
+#define DS_DW_LDS_LAUNCH(T_, TWL_, NV_)                                                                                                                        \
+        do {                                                                                                                                                  \
+            if (t.lds > 65536) DS_SET_MAX_LDS((dwconv7_lds_kernel<T_, TWL_, NV_>), t.lds, "dwconv7_lds");                                                      \
+            hipLaunchKernelGGL((dwconv7_lds_kernel<T_, TWL_, NV_>), dim3(pl.parts, p->B), dim3(LT_NT), t.lds, st, *p, t.tiles_w, t.tiles_w * t.tiles_h, t.ncblk); \
         } while (0)
         if (p->dtype == DS_BF16) {
-            if (twl == 5) DS_DW_LDS_LAUNCH(bf16, 5, 4); else if (twl == 4) DS_DW_LDS_LAUNCH(bf16, 4, 4); else DS_DW_LDS_LAUNCH(bf16, 3, 4);
-        } else if (nv == 8) {
-            if (twl == 4) DS_DW_LDS_LAUNCH(float, 4, 8); else DS_DW_LDS_LAUNCH(float, 3, 8);
+            if (t.twl == 5) DS_DW_LDS_LAUNCH(bf16, 5, 4); else if (t.twl == 4) DS_DW_LDS_LAUNCH(bf16, 4, 4); else DS_DW_LDS_LAUNCH(bf16, 3, 4);
+        } else if (t.nv == 8) {
+            if (t.twl == 4) DS_DW_LDS_LAUNCH(float, 4, 8); else DS_DW_LDS_LAUNCH(float, 3, 8);
         } else {
-            if (twl == 5) DS_DW_LDS_LAUNCH(float, 5, 4); else if (twl == 4) DS_DW_LDS_LAUNCH(float, 4, 4); else DS_DW_LDS_LAUNCH(float, 3, 4);
+            if (t.twl == 5) DS_DW_LDS_LAUNCH(float, 5, 4); else if (t.twl == 4) DS_DW_LDS_LAUNCH(float, 4, 4); else DS_DW_LDS_LAUNCH(float, 3, 4);
         }
 #undef DS_DW_LDS_LAUNCH
         DS_CHECK_LAUNCH("dwconv7_lds");
-        return DS_OK;
+    } else {
+        const auto& d = pl.direct;
+        if (p->dtype == DS_BF16) hipLaunchKernelGGL(dwconv7_kernel<bf16>, dim3(pl.parts, p->B), dim3(DW_BLOCK), 0, st, *p, d.nstrip, d.CV);
+        else hipLaunchKernelGGL(dwconv7_kernel<float>, dim3(pl.parts, p->B), dim3(DW_BLOCK), 0, st, *p, d.nstrip, d.CV);
+        DS_CHECK_LAUNCH("dwconv7");
     }
-    if (p->dtype == DS_BF16) hipLaunchKernelGGL(dwconv7_kernel<bf16>, dim3(blocks, p->B), dim3(DW_BLOCK), 0, st, *p, nstrip, CV);
-    else hipLaunchKernelGGL(dwconv7_kernel<float>, dim3(blocks, p->B), dim3(DW_BLOCK), 0, st, *p, nstrip, CV);
-    DS_CHECK_LAUNCH("dwconv7");
     return DS_OK;
 }
 

@@ -557,7 +557,9 @@ def ceil_div(a, b):
 # Tile kernels (dwconv_gn.hip: a block holds 2048 / NV pixels of NV channel vectors; columns 8 / 16 / 32 by lt_twl): bf16 and fp32 NV = 4
 # 512 pixels = 64 x 8 (W <= 8), 32 x 16 (W <= 16), 16 x 32; fp32 NV = 8 256 pixels = 32 x 8 (W <= 8), 16 x 16.
 DW_ROWS = [("direct", L.DS_BF16, (40, 0), (10, 9), False, 0, 0, "direct", None),
-           ("direct", L.DS_F32, (20, 0), (10, 9), False, 0, 0, "direct", None)]
+           ("direct", L.DS_F32, (20, 0), (10, 9), False, 0, 0, "direct", None),
+           ("direct", L.DS_BF16, (24, 40), (10, 9), False, 0, 0, "direct", None),              # (the direct kernel's second-source branch)
+           ("direct", L.DS_F32, (12, 20), (10, 9), False, 0, 0, "direct", None)]
 for _w, _tile in ((7, (64, 8)), (12, (32, 16)), (40, (16, 32))):
     DW_ROWS.append(("tile", L.DS_BF16, (32, 64), (19, _w), False, 0, 0, "tile", _tile + (32,)))
     DW_ROWS.append(("tile", L.DS_F32, (48, 0), (19, _w), False, 0, 0, "tile", _tile + (16,)))
