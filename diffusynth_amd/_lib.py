@@ -60,6 +60,7 @@ GnApplyParams = _STRUCTS["ds_gn_apply_params"]
 AttnParams = _STRUCTS["ds_attn_params"]
 StepParams = _STRUCTS["ds_step_params"]
 StepRowsParams = _STRUCTS["ds_step_rows_params"]
+DpmStepParams = _STRUCTS["ds_dpm_step_params"]
 AttnFusedParams = _STRUCTS["ds_attn_fused_params"]
 AttnX3Params = _STRUCTS["ds_attn_x3_params"]
 VqAttnParams = _STRUCTS["ds_vq_attn_params"]
@@ -122,6 +123,8 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_nhwc_to_nchw": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "ds_ddim_step": (C.c_int, [C.POINTER(StepParams), _P]),
     "ds_step_rows": (C.c_int, [C.POINTER(StepRowsParams), _P]),
+    "ds_dpm_step": (C.c_int, [C.POINTER(DpmStepParams), _P]),
+    "ds_dpm_step_rows": (C.c_int, [C.POINTER(StepRowsParams), _P, _P]),
     "ds_philox_normal": (C.c_int, [_P, _SZ, _U64, _U64, _P]),
     "ds_gather_cols": (C.c_int, [_P, _I, _I, _P, _I, _P, _P]),
     "ds_vq_nearest": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

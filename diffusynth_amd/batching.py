@@ -4,7 +4,9 @@ Every caller of the reference builds its own DiffSynthSampler and runs one call 
 inpainting, one batch-1 ``inpaint_sample`` per note of the MIDI arranger).  A batch-1 step leaves most of the card idle
 (DESIGN.md §5), so this module runs many such calls together: each call is submitted with the sampler it would have been
 run on, and every tick advances every active call by one step with ONE U-Net forward per bucket and ONE ``ds_step_rows``
-launch per bucket that applies each row's own guidance scale, coefficients, inpaint blend and step noise.
+launch per bucket that applies each row's own guidance scale, coefficients, inpaint blend and step noise.  Requests of the
+"dpmpp_2m" sampler share buckets and U-Net batches with the others: their rows are stepped by one ``ds_dpm_step_rows`` launch per
+bucket, each request on history rows of its own that stay where they are for the request's lifetime.
 
     b = SamplingBatcher(unet, max_rows=128)
     h = b.submit(dss, "inpaint_sample", shape, 0.7, guide, mask, condition=c, sampler="ddpm", use_dynamic_mask=True, seed=7)
@@ -91,6 +93,9 @@ class _Request:
         self.out = None
         if self.sampler == "ddpm":
             self.draw_w, self.cols = dss._step_noise_layout(self.W)
+        self.solver = self.sampler == "dpmpp_2m"
+        # the solver's history (the previous step's x0 prediction): the request's own rows, never part of the bucket's re-laid tensors
+        self.hist = torch.empty(prog.shape, dtype=torch.float32, device=self.state.device) if self.solver else None
         self.mapped = [int(dss.timestep_map[i]) for i in prog.steps]
 
 
@@ -275,6 +280,7 @@ class SamplingBatcher:
         H, W = b.key[0], b.key[1]
         Cc = reqs[0].C
         R = sum(r.B for r in reqs)
+        R1 = sum(r.B for r in reqs if not r.solver)       # table rows [0, R1): ds_step_rows; [R1, R): ds_dpm_step_rows
         ni, nf, npp = L.SR["DS_SR_NI"], L.SR["DS_SR_NF"], L.SR["DS_SR_NP"]
         # column tables of the DDPM requests (one per distinct layout)
         col_tabs, col_off, n_cols = {}, {}, 0
@@ -291,7 +297,8 @@ class SamplingBatcher:
         o_t, o_i = 0, up(8 * Bu)
         o_f = o_i + up(4 * R * ni)
         o_p = o_f + up(4 * R * nf)
-        o_c = o_p + up(8 * R * npp)
+        o_h = o_p + up(8 * R * npp)
+        o_c = o_h + up(8 * max(R - R1, 1))
         nbytes = o_c + up(4 * max(n_cols, 1))
         host, ev = self._staging(nbytes)
         hb = host.numpy()
@@ -299,15 +306,18 @@ class SamplingBatcher:
         irow = hb[o_i:o_i + 4 * R * ni].view(np.int32).reshape(R, ni)
         frow = hb[o_f:o_f + 4 * R * nf].view(np.float32).reshape(R, nf)
         prow = hb[o_p:o_p + 8 * R * npp].view(np.uint64).reshape(R, npp)
+        hrow = hb[o_h:o_h + 8 * (R - R1)].view(np.uint64)
         cols = hb[o_c:o_c + 4 * max(n_cols, 1)].view(np.int32)
         for key, off in col_tabs.items():
             cols[off:off + len(key)] = key
         S = L.SR
         keep = []
-        row = 0
+        nxt = [0, R1]                   # next table row of a ds_step_rows request, of a solver request
         CHW = Cc * H * W
         for r, (x0, e0, ec0, d0) in zip(reqs, b.lay):
             k, B, prog = r.k, r.B, r.prog
+            row = nxt[r.solver]
+            nxt[r.solver] += B
             sl = slice(row, row + B)
             ar = np.arange(B, dtype=np.int32)
             ar64 = ar.astype(np.uint64)
@@ -334,6 +344,8 @@ class SamplingBatcher:
                     prow[sl, S["DS_SR_INIT"]] = np.uint64(prog.init.data_ptr()) + np.uint64(4 * CHW) * ar64
                 prow[sl, S["DS_SR_GUIDE"]] = np.uint64(prog.guide.data_ptr()) + np.uint64(4 * CHW) * ar64
                 prow[sl, S["DS_SR_MASKP"]] = np.uint64(m.data_ptr()) + np.uint64(4 * (CHW if chw else H * W)) * ar64
+            if r.solver:
+                hrow[row - R1:row - R1 + B] = np.uint64(r.hist.data_ptr()) + np.uint64(4 * CHW) * ar64
             if r.sampler == "ddpm":
                 dss = r.dss
                 draw_shape = (dss.max_batchsize, Cc, H, r.draw_w)
@@ -350,7 +362,6 @@ class SamplingBatcher:
                     keep.append(raw)
                     irow[sl, S["DS_SR_NOISE"]] = _NOISE_DRAW
                     prow[sl, S["DS_SR_DRAW"]] = raw.data_ptr()
-            row += B
         dev = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
         dev.copy_(host[:nbytes], non_blocking=True)
         ev.record()
@@ -362,10 +373,17 @@ class SamplingBatcher:
         else:
             eps = self.unet(b.x, t_dev, b.cond)
         out = torch.empty_like(b.x)
-        p = L.StepRowsParams(x=b.x.data_ptr(), eps=eps.data_ptr(), out=out.data_ptr(), irow=dev.data_ptr() + o_i,
-                             frow=dev.data_ptr() + o_f, prow=dev.data_ptr() + o_p, cols=(dev.data_ptr() + o_c) if n_cols else None,
-                             R=R, C=Cc, H=H, W=W, Bx=Bu, Beps=eps.shape[0], Bout=Bu, n_cols=n_cols)
-        L.call("ds_step_rows", C.byref(p), L.current_stream())
+        for name, first, n in (("ds_step_rows", 0, R1), ("ds_dpm_step_rows", R1, R - R1)):
+            if n == 0:
+                continue
+            p = L.StepRowsParams(x=b.x.data_ptr(), eps=eps.data_ptr(), out=out.data_ptr(), irow=dev.data_ptr() + o_i + 4 * ni * first,
+                                 frow=dev.data_ptr() + o_f + 4 * nf * first, prow=dev.data_ptr() + o_p + 8 * npp * first,
+                                 cols=(dev.data_ptr() + o_c) if n_cols else None,
+                                 R=n, C=Cc, H=H, W=W, Bx=Bu, Beps=eps.shape[0], Bout=Bu, n_cols=n_cols)
+            if name == "ds_step_rows":
+                L.call(name, C.byref(p), L.current_stream())
+            else:
+                L.call(name, C.byref(p), dev.data_ptr() + o_h, L.current_stream())
         del keep
         b.x = out
         done = []

@@ -194,20 +194,20 @@ __global__ void nhwc_to_nchw_kernel(const T* x, int C, int Cs, int HW, float* ou
 #pragma clang fp contract(off)
 // cf: sqrt(1-a_t), sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma; qc: sqrt(acp[t-1]), sqrt(1-acp[t-1]) (blend mode 1 only);
 // m / g / n0: mask, guide and initial noise of the element (blend modes 1 / 2 only)
-__device__ __forceinline__ float step_element(float x, float eps, bool cfg, float eps_c, float cfg_scale, const float (&cf)[5], float noise,
-                                              int blend_mode, float m, float g, float n0, float q0, float q1) {
+__device__ __forceinline__ float guided_eps(float eps, bool cfg, float eps_c, float cfg_scale) {
     if (cfg) {
         const float d = eps_c - eps;
         const float sd = cfg_scale * d;
         eps = eps + sd;
     }
-    const float t0 = cf[0] * eps;
+    return eps;
+}
+__device__ __forceinline__ float predicted_x0(float x, float eps, float sigma_t, float alpha_t) {
+    const float t0 = sigma_t * eps;
     const float t1 = x - t0;
-    const float x0 = t1 / cf[1];
-    const float u0 = cf[2] * x0;
-    const float u1 = cf[3] * eps;
-    const float u2 = cf[4] * noise;
-    float v = (u0 + u1) + u2;
+    return t1 / alpha_t;
+}
+__device__ __forceinline__ float inpaint_blend(float v, int blend_mode, float m, float g, float n0, float q0, float q1) {
     if (blend_mode) {
         if (blend_mode == 1) {
             const float g0 = q0 * g;
@@ -219,6 +219,31 @@ __device__ __forceinline__ float step_element(float x, float eps, bool cfg, floa
         v = w0 + w1;
     }
     return v;
+}
+__device__ __forceinline__ float step_element(float x, float eps, bool cfg, float eps_c, float cfg_scale, const float (&cf)[5], float noise,
+                                              int blend_mode, float m, float g, float n0, float q0, float q1) {
+    eps = guided_eps(eps, cfg, eps_c, cfg_scale);
+    const float x0 = predicted_x0(x, eps, cf[0], cf[1]);
+    const float u0 = cf[2] * x0;
+    const float u1 = cf[3] * eps;
+    const float u2 = cf[4] * noise;
+    return inpaint_blend((u0 + u1) + u2, blend_mode, m, g, n0, q0, q1);
+}
+// "dpmpp_2m" (DPM-Solver++(2M)): cf = sigma_t, alpha_t, c_x, c_0, c_1 (sampler.py: _solver_coefficients); x0 is step_element's.  `hist` is the
+// previous step's x0 (used only where second, i.e. c_1 != 0) and receives this step's: the blend changes the state, never the history
+__device__ __forceinline__ float dpm_element(float x, float eps, bool cfg, float eps_c, float cfg_scale, const float (&cf)[5], bool second,
+                                             float& hist, int blend_mode, float m, float g, float n0, float q0, float q1) {
+    eps = guided_eps(eps, cfg, eps_c, cfg_scale);
+    const float x0 = predicted_x0(x, eps, cf[0], cf[1]);
+    const float u0 = cf[2] * x;
+    const float u1 = cf[3] * x0;
+    float v = u0 + u1;
+    if (second) {
+        const float u2 = cf[4] * hist;
+        v = v + u2;
+    }
+    hist = x0;
+    return inpaint_blend(v, blend_mode, m, g, n0, q0, q1);
 }
 
 __global__ __launch_bounds__(256) void ddim_step_kernel(const ds_step_params p, size_t total) {
@@ -391,6 +416,138 @@ __global__ __launch_bounds__(256) void step_rows_kernel(const ds_step_rows_param
         store_v<V>(orow_p + i0, o);
         if (drow_p) store_v<V>(drow_p + i0, o);
     }
+}
+
+// One row of the solver step: pieces of V elements, grid-strided along x.  ds_dpm_step_kernel and dpm_step_rows_kernel both run this
+// loop, so a row of ds_dpm_step_rows is the same bits as ds_dpm_step given the same inputs.  hist may be null only where cf[4] == 0;
+// avec / hvec: the blend operands / the history are 16-byte aligned (V == 4 only).
+struct dpm_row_args {
+    const float* x; const float* eps; const float* eps_c; float* hist; float* out; float* dup;
+    const float* mask; const float* guide; const float* init;
+    float cf[5], q0, q1, scale;
+    int blend, mask_chw;
+};
+template <int V>
+__device__ __forceinline__ void dpm_row(const dpm_row_args& a, int HW, size_t CHW, bool avec, bool hvec) {
+    const bool second = a.cf[4] != 0.f;
+    const size_t nv = CHW / V;
+    for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < nv; v += (size_t)gridDim.x * blockDim.x) {
+        const size_t i0 = v * V;
+        float xv[V], ev[V], ecv[V], hv[V], mv[V], gv[V], n0[V];
+        load_v<V>(a.x + i0, true, xv);
+        load_v<V>(a.eps + i0, true, ev);
+        if (a.eps_c) load_v<V>(a.eps_c + i0, true, ecv);
+        else
+#pragma unroll
+            for (int k = 0; k < V; ++k) ecv[k] = 0.f;
+        if (second) load_v<V>(a.hist + i0, hvec, hv);
+        else
+#pragma unroll
+            for (int k = 0; k < V; ++k) hv[k] = 0.f;
+#pragma unroll
+        for (int k = 0; k < V; ++k) mv[k] = gv[k] = n0[k] = 0.f;
+        if (a.blend) {
+            load_v<V>(a.mask + (a.mask_chw ? i0 : i0 % HW), avec, mv);
+            load_v<V>(a.guide + i0, avec, gv);
+            if (a.blend == 1) load_v<V>(a.init + i0, avec, n0);
+        }
+        float o[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            o[k] = dpm_element(xv[k], ev[k], a.eps_c != nullptr, ecv[k], a.scale, a.cf, second, hv[k], a.blend, mv[k], gv[k], n0[k], a.q0, a.q1);
+        store_v<V>(a.out + i0, o);
+        if (a.dup) store_v<V>(a.dup + i0, o);
+        if (a.hist) {
+            if (hvec) store_v<V>(a.hist + i0, hv);
+            else
+#pragma unroll
+                for (int k = 0; k < V; ++k) a.hist[i0 + k] = hv[k];
+        }
+    }
+}
+__device__ __forceinline__ void nan_row(float* out, float* dup, size_t CHW) {
+    const float nan = __builtin_nanf("");
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < CHW; i += (size_t)gridDim.x * blockDim.x) {
+        out[i] = nan;
+        if (dup) dup[i] = nan;
+    }
+}
+
+// grid (x: pieces of a row, y: sample).  V == 4 only when W % 4 == 0 and every pointer given is 16-byte aligned
+template <int V>
+__global__ __launch_bounds__(256) void dpm_step_kernel(const ds_dpm_step_params p) {
+    const int b = blockIdx.y;
+    const int HW = p.H * p.W;
+    const size_t CHW = (size_t)p.C * HW;
+    dpm_row_args a;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) a.cf[k] = p.coef[(size_t)b * 5 + k];
+    a.out = p.out + (size_t)b * CHW;
+    a.dup = nullptr;
+    if (!p.hist && a.cf[4] != 0.f) {                // a second-order row without a history: shown in the result, nothing is read
+        nan_row(a.out, nullptr, CHW);
+        return;
+    }
+    a.x = p.x + (size_t)b * CHW;
+    a.eps = p.eps + (size_t)b * CHW;
+    a.eps_c = p.eps_cond ? p.eps_cond + (size_t)b * CHW : nullptr;
+    a.hist = p.hist ? p.hist + (size_t)b * CHW : nullptr;
+    a.blend = p.blend_mode;
+    a.mask_chw = p.mask_chw;
+    a.mask = a.guide = a.init = nullptr;
+    a.q0 = a.q1 = 0.f;
+    if (p.blend_mode) {
+        a.mask = p.mask + (size_t)b * (p.mask_chw ? CHW : (size_t)HW);
+        a.guide = p.guide + (size_t)b * CHW;
+        if (p.blend_mode == 1) {
+            a.init = p.init_noise + (size_t)b * CHW;
+            a.q0 = p.qcoef[(size_t)b * 2];
+            a.q1 = p.qcoef[(size_t)b * 2 + 1];
+        }
+    }
+    a.scale = p.cfg_scale;
+    dpm_row<V>(a, HW, CHW, V == 4, V == 4);
+}
+
+// ds_step_rows' tables and bounds contract (see step_rows_kernel) plus one history address per row
+template <int V>
+__global__ __launch_bounds__(256) void dpm_step_rows_kernel(const ds_step_rows_params p, const uint64_t* hrow) {
+    const int r = blockIdx.y;
+    const int32_t* ir = p.irow + (size_t)r * DS_SR_NI;
+    const float* fr = p.frow + (size_t)r * DS_SR_NF;
+    const uint64_t* pr = p.prow + (size_t)r * DS_SR_NP;
+    const int xr = ir[DS_SR_X], er = ir[DS_SR_EPS], ecr = ir[DS_SR_EPSC], orow = ir[DS_SR_OUT], dup = ir[DS_SR_DUP];
+    const int blend = ir[DS_SR_BLEND], nmode = ir[DS_SR_NOISE];
+    dpm_row_args a;
+    a.guide = reinterpret_cast<const float*>(pr[DS_SR_GUIDE]);
+    a.init = reinterpret_cast<const float*>(pr[DS_SR_INIT]);
+    a.mask = reinterpret_cast<const float*>(pr[DS_SR_MASKP]);
+    a.hist = reinterpret_cast<float*>(hrow[r]);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) a.cf[k] = fr[DS_SR_COEF + k];
+    const int HW = p.H * p.W;
+    const size_t CHW = (size_t)p.C * HW;
+    if (orow < 0 || orow >= p.Bout) return;
+    a.out = p.out + (size_t)orow * CHW;
+    const bool bad = xr < 0 || xr >= p.Bx || er < 0 || er >= p.Beps || ecr >= p.Beps || dup >= p.Bout || blend < 0 || blend > 2 ||
+                     nmode != 0 || (blend && (!a.guide || !a.mask || (blend == 1 && !a.init))) || (!a.hist && a.cf[4] != 0.f);
+    if (bad) {
+        nan_row(a.out, dup >= 0 && dup < p.Bout ? p.out + (size_t)dup * CHW : nullptr, CHW);
+        return;
+    }
+    a.dup = dup >= 0 ? p.out + (size_t)dup * CHW : nullptr;
+    a.x = p.x + (size_t)xr * CHW;
+    a.eps = p.eps + (size_t)er * CHW;
+    a.eps_c = ecr >= 0 ? p.eps + (size_t)ecr * CHW : nullptr;
+    a.blend = blend;
+    a.mask_chw = ir[DS_SR_MASK_CHW];
+    a.q0 = fr[DS_SR_Q0];
+    a.q1 = fr[DS_SR_Q1];
+    a.scale = fr[DS_SR_CFG];
+    // (a history row is a request's own allocation: its alignment is looked at per row, like the blend operands')
+    const bool hvec = V == 4 && (((uint64_t)a.hist) & 15) == 0;
+    const bool avec = V == 4 && ((((uint64_t)a.guide | (uint64_t)a.init | (uint64_t)a.mask) & 15) == 0);
+    dpm_row<V>(a, HW, CHW, avec, hvec);
 }
 #pragma clang fp contract(fast)
 
@@ -624,6 +781,38 @@ extern "C" int ds_step_rows(const ds_step_rows_params* p, void* stream) {
     if (vec) hipLaunchKernelGGL(step_rows_kernel<4>, grid, dim3(256), 0, st, *p);
     else hipLaunchKernelGGL(step_rows_kernel<1>, grid, dim3(256), 0, st, *p);
     DS_CHECK_LAUNCH("step_rows");
+    return DS_OK;
+}
+
+extern "C" int ds_dpm_step(const ds_dpm_step_params* p, void* stream) {
+    DS_REQUIRE(p && p->x && p->eps && p->out && p->coef, "dpm_step: null pointer");
+    DS_REQUIRE(p->B > 0 && p->B <= 65535 && p->C > 0 && p->H > 0 && p->W > 0, "dpm_step: bad sizes (B=%d C=%d H=%d W=%d)", p->B, p->C, p->H, p->W);
+    DS_REQUIRE(p->blend_mode >= 0 && p->blend_mode <= 2, "dpm_step: blend_mode %d", p->blend_mode);
+    DS_REQUIRE(p->blend_mode == 0 || (p->guide && p->mask), "dpm_step: blend needs guide and mask");
+    DS_REQUIRE(p->blend_mode != 1 || (p->init_noise && p->qcoef), "dpm_step: blend 1 needs init_noise and qcoef");
+    const size_t CHW = (size_t)p->C * p->H * p->W;
+    // (NULL is 16-byte aligned: an operand that is not given does not decide the path)
+    const bool vec = p->W % 4 == 0 && ds_aligned16(p->x) && ds_aligned16(p->eps) && ds_aligned16(p->eps_cond) && ds_aligned16(p->hist) &&
+                     ds_aligned16(p->out) && ds_aligned16(p->guide) && ds_aligned16(p->init_noise) && ds_aligned16(p->mask);
+    const dim3 grid((unsigned)blocks_for(vec ? CHW / 4 : CHW, 4096), (unsigned)p->B);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL(dpm_step_kernel<4>, grid, dim3(256), 0, st, *p);
+    else hipLaunchKernelGGL(dpm_step_kernel<1>, grid, dim3(256), 0, st, *p);
+    DS_CHECK_LAUNCH("dpm_step");
+    return DS_OK;
+}
+
+extern "C" int ds_dpm_step_rows(const ds_step_rows_params* p, const uint64_t* hrow, void* stream) {
+    DS_REQUIRE(p && p->x && p->eps && p->out && p->irow && p->frow && p->prow && hrow, "dpm_step_rows: null pointer");
+    DS_REQUIRE(p->R > 0 && p->R <= 65535 && p->C > 0 && p->H > 0 && p->W > 0, "dpm_step_rows: bad sizes (R=%d C=%d H=%d W=%d)", p->R, p->C, p->H, p->W);
+    DS_REQUIRE(p->Bx > 0 && p->Beps > 0 && p->Bout > 0, "dpm_step_rows: bad row counts (Bx=%d Beps=%d Bout=%d)", p->Bx, p->Beps, p->Bout);
+    const size_t CHW = (size_t)p->C * p->H * p->W;
+    const bool vec = p->W % 4 == 0 && ds_aligned16(p->x) && ds_aligned16(p->eps) && ds_aligned16(p->out);
+    const dim3 grid((unsigned)blocks_for(vec ? CHW / 4 : CHW, 4096), (unsigned)p->R);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL(dpm_step_rows_kernel<4>, grid, dim3(256), 0, st, *p, hrow);
+    else hipLaunchKernelGGL(dpm_step_rows_kernel<1>, grid, dim3(256), 0, st, *p, hrow);
+    DS_CHECK_LAUNCH("dpm_step_rows");
     return DS_OK;
 }
 

@@ -8,7 +8,7 @@ one U-Net batch (one plan of the engine, which keeps all plans in one bounded ar
 the results come back in request order.
 No padding to a common width is involved: a note's convolution borders, GroupNorm counts and attention length are those
 of its own width, so each request's result is what its own single-sample call would have produced (bit for bit in the
-fp32 tier with the deterministic DDIM sampler, where no per-step noise is drawn)."""
+fp32 tier with the deterministic samplers, "ddim" and "dpmpp_2m", where a request's result does not depend on per-step noise)."""
 import numpy as np
 import torch
 
@@ -17,20 +17,21 @@ from .sampler import DiffSynthSampler
 
 @torch.no_grad()
 def sample_mixed_widths(model, requests, steps, *, timesteps=1000, height=128, channels=4, sampler="ddim", cfg_scale=1.0,
-                        unconditional_condition=None, device="cuda", noise_device=None, return_trajectory=False):
+                        unconditional_condition=None, device="cuda", noise_device=None, return_trajectory=False, use_timesteps=None):
     """requests: list of dicts ``{"width": int, "condition": (label_dim,) tensor or None, "seed": int}``.
     Returns a list (request order) of final latents (4, height, width) — or of trajectories when asked.
 
     Each request's initial noise is drawn like a batch-1 reference call with its seed would draw it
     (``torch.manual_seed(seed)``; ``randn((1, C, H, train_width))``, on a private generator); requests of one width then share the
-    loop.
+    loop.  ``use_timesteps`` (a list for ``DiffSynthSampler.respace``, e.g. ``logsnr_timesteps(steps)``) replaces the default
+    ``linspace(0, timesteps - 1, steps)``.
 
-    Only the deterministic sampler is served this way: with ``"ddpm"`` the per-step noise of a bucket would come from ONE
+    Only the deterministic samplers ("ddim", "dpmpp_2m") are served this way: with ``"ddpm"`` the per-step noise of a bucket would come from ONE
     generator stream, so a request's result would depend on which other requests share its width and on their order (the
     reference serves one call per note, so that case has no reference behaviour to match)."""
-    if sampler != "ddim":
-        raise NotImplementedError("sample_mixed_widths serves the deterministic 'ddim' sampler only: per-step noise of a shared "
-                                  "bucket would make a request's result depend on its bucket mates (got %r)" % (sampler,))
+    if sampler not in ("ddim", "dpmpp_2m"):
+        raise NotImplementedError("sample_mixed_widths serves the deterministic samplers ('ddim', 'dpmpp_2m') only: per-step noise of a "
+                                  "shared bucket would make a request's result depend on its bucket mates (got %r)" % (sampler,))
     if cfg_scale != 1.0 and unconditional_condition is None:
         raise ValueError("cfg_scale != 1 needs an unconditional_condition (the negative-prompt embedding)")
     from .batching import SamplingBatcher
@@ -47,7 +48,7 @@ def sample_mixed_widths(model, requests, steps, *, timesteps=1000, height=128, c
         for i in idxs:
             s = DiffSynthSampler(timesteps, mute=True, device=device, height=height, max_batchsize=1, channels=channels,
                                  noise_device=noise_device)
-            s.respace(list(np.linspace(0, timesteps - 1, steps, dtype=np.int32)))
+            s.respace(list(np.linspace(0, timesteps - 1, steps, dtype=np.int32)) if use_timesteps is None else list(use_timesteps))
             if cfg_scale != 1.0:
                 s.activate_classifier_free_guidance(cfg_scale, unconditional_condition)
             c = None if nocond else requests[i]["condition"].to(device).float()[None]

@@ -472,6 +472,33 @@ typedef struct {
     int32_t Bx, Beps, Bout, n_cols;
 } ds_step_rows_params;
 int ds_step_rows(const ds_step_rows_params* p, void* stream);
+/* One step of the "dpmpp_2m" sampler (DPM-Solver++(2M): data prediction, second-order multistep, deterministic).  With the
+ * guidance combine and the blend of ds_ddim_step:
+ *     x0  = (x - coef[0] * eps') / coef[1]                     (ds_ddim_step's x0: same operations, same two coefficients)
+ *     out = (coef[2] * x + coef[3] * x0) + coef[4] * hist      (the last term only where coef[4] != 0: hist is not read otherwise)
+ *     out = blend(out);  hist = x0
+ * coef [B][5] = sigma_t, alpha_t, c_x, c_0, c_1 (diffusynth_amd/sampler.py builds them in float64).  hist [B][C*H*W] is the x0
+ * prediction of the previous step, updated in place (each element is read and written by the same thread); it may be NULL
+ * when no row has coef[4] != 0 — a row that needs a history it was not given is filled with NaN.  fp32 NCHW, no fused
+ * multiply-add; 16-byte accesses when W % 4 == 0 and x / eps / eps_cond / hist / out are 16-byte aligned. */
+typedef struct {
+    const float* x; const float* eps; const float* eps_cond; /* eps_cond != NULL => eps is the uncond half */
+    float* hist; float* out;
+    const float* coef;           /* [B][5] */
+    float cfg_scale;
+    int32_t blend_mode;          /* as ds_step_params */
+    const float* guide; const float* init_noise; const float* mask;
+    const float* qcoef;          /* [B][2] */
+    int32_t B, C, H, W;
+    int32_t mask_chw;
+} ds_dpm_step_params;
+int ds_dpm_step(const ds_dpm_step_params* p, void* stream);
+/* ds_dpm_step over R rows that belong to different requests: ds_step_rows' tables, bounds contract, duplicate write and 16-byte
+ * paths, with frow's coef[5] holding the solver's five numbers and irow DS_SR_NOISE == 0 (the solver draws no step noise; any
+ * other value makes the row malformed).  hrow [R] holds each row's history address (C*H*W floats, updated in place); 0 is allowed
+ * only where the row's coef[4] == 0, anywhere else the row is malformed.  A malformed row reads nothing, writes no history and
+ * fills its output row (and its duplicate, when in range) with NaN.  A row is the same bits as ds_dpm_step on the same inputs. */
+int ds_dpm_step_rows(const ds_step_rows_params* p, const uint64_t* hrow, void* stream);
 /* counter-based N(0,1) generator (Philox4x32-10 + Box-Muller) for the throughput mode */
 int ds_philox_normal(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 /* column gather of the "repeat" noise layout (DiffSynthSampler.py:97-167): out[b][c][h][j] = src[b][c][h][cols[j]] */
