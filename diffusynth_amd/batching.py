@@ -17,7 +17,9 @@ A call's arguments and return values are those of ``getattr(dss, method)(unet, .
 guide, q_sample, masks, step list, coefficient tables) is the sampler's own (``DiffSynthSampler._loop_prologue``); its draws
 come from a private ``torch.Generator`` (or the sampler's Philox stream), so a request's noise does not depend on the other
 requests.  In the fp32 tier no tiling choice of the U-Net depends on the batch, so a request's result is the same bits as the
-call run alone; in the bf16x3 / bf16 tiers split-K factors and attention segment counts follow the U-Net batch, so a result
+call run alone — and so it is in the bf16x3 / bf16 tiers on a model pinned with ``unet.pin_launch_batch(max_rows)`` (every launch
+decision then looks at the pin, not at the batch; the batcher needs no argument for it).  Unpinned, in the bf16x3 / bf16 tiers
+split-K factors and attention segment counts follow the U-Net batch, so a result
 depends on its batch mates within the tier's error contract (a batcher that holds one request is the standalone call).
 
 Buckets: one per (height, width, has_condition).  A tick runs every non-empty bucket: the U-Net batch is every request's rows

@@ -386,10 +386,15 @@ __global__ void pack_attn_kernel(const float* wqkv, const float* gamma, const fl
     }
 }
 
+// The batch the batch-dependent choices of this file and attn_out2.hpp look at (generation, blocks per sample of the output pass):
+// ds_attn_fused_params.batch_hint where the caller gives one, else B.
+int fused_batch(const ds_attn_fused_params* p) { return p->batch_hint > 0 ? p->batch_hint : p->B; }
+
 int check(const ds_attn_fused_params* p) {
     DS_REQUIRE(p && p->x && p->wqkv && p->t1 && p->t2 && (p->gn_ab || p->gn_part) && p->part && p->ctx, "attn_fused: null pointer");
     DS_REQUIRE(p->C == 96 || p->C == 192 || p->C == 384, "attn_fused: C=%d unsupported (96, 192, 384)", p->C);
     DS_REQUIRE(p->B > 0 && p->N > 0 && p->nseg > 0, "attn_fused: bad sizes");
+    DS_REQUIRE(p->batch_hint >= 0, "attn_fused: batch_hint must be 0 (use B) or the batch the launch decisions look at, got %d", p->batch_hint);
     if (!ds_aligned16(p->x) || !ds_aligned16(p->wqkv)) DS_FAIL(DS_EALIGN, "attn_fused: pointers must be 16-byte aligned");
     return DS_OK;
 }
@@ -447,9 +452,9 @@ int launch_out(const ds_attn_fused_params* p, hipStream_t st) {
     DS_SET_MAX_LDS(kern, lds, "attn_fused_out");
     const int ngroups = (p->N + 32 * T - 1) / (32 * T);
 #if DS_BOUNDS
-    attn_publish_bounds(p, DS_K_ATTN_OUT, out_blocks(ngroups, p->B, p->C), st);
+    attn_publish_bounds(p, DS_K_ATTN_OUT, out_blocks(ngroups, fused_batch(p), p->C), st);
 #endif
-    hipLaunchKernelGGL(kern, dim3(out_blocks(ngroups, p->B, p->C), p->B), dim3(256), lds, st, *p);
+    hipLaunchKernelGGL(kern, dim3(out_blocks(ngroups, fused_batch(p), p->C), p->B), dim3(256), lds, st, *p);
     DS_CHECK_LAUNCH("attn_fused_out");
     return DS_OK;
 }
@@ -464,11 +469,11 @@ namespace {
 static inline bool ctx2_exists(int C, int N) { return C == 96 || C == 192 || (C == 384 && N >= 1024); }
 static inline bool use_ctx2(const ds_attn_fused_params* p) {
     if (p->gen == 1 || !ctx2_exists(p->C, p->N)) return false;
-    return p->gen == 2 || p->B >= 96;
+    return p->gen == 2 || fused_batch(p) >= 96;
 }
 static inline bool use_out2(const ds_attn_fused_params* p) {
     if (p->gen == 1 || !p->mfold || !(p->C == 96 || p->C == 192)) return false;
-    return p->gen == 2 || p->B >= (p->C == 96 ? 32 : 96);
+    return p->gen == 2 || fused_batch(p) >= (p->C == 96 ? 32 : 96);
 }
 
 // pixels per group: 64 where the image is large enough to keep every CU busy with fewer, longer iterations
@@ -508,7 +513,7 @@ extern "C" int ds_attn_fused_output(const ds_attn_fused_params* p, void* stream)
     if (use_out2(p)) {
         DS_REQUIRE(ds_aligned16(p->mfold) && ds_aligned16(p->y), "attn_fused_output: mfold / y must be 16-byte aligned");
 #if DS_BOUNDS
-        attn_publish_bounds(p, DS_K_ATTN_OUT, attn_out2_blocks(p->N, p->B, p->C), st);
+        attn_publish_bounds(p, DS_K_ATTN_OUT, attn_out2_blocks(p->N, fused_batch(p), p->C), st);
 #endif
         return attn_out2_launch(p, st);
     }
@@ -539,7 +544,7 @@ extern "C" int ds_attn_fused_segments(int B, int N, int C) { return ds_attn_fuse
 extern "C" int ds_attn_fused_generations(const ds_attn_fused_params* p) { return (use_ctx2(p) ? 1 : 0) | (use_out2(p) ? 2 : 0); }
 
 extern "C" int ds_attn_fused_stats_parts(const ds_attn_fused_params* p) {
-    if (use_out2(p)) return attn_out2_blocks(p->N, p->B, p->C);
+    if (use_out2(p)) return attn_out2_blocks(p->N, fused_batch(p), p->C);
     const int tp = 32 * group_t(p->C, p->N);
-    return out_blocks((p->N + tp - 1) / tp, p->B, p->C);
+    return out_blocks((p->N + tp - 1) / tp, fused_batch(p), p->C);
 }

@@ -448,7 +448,7 @@ static int attn_out2_blocks(int N, int B, int C) {
 
 static int attn_out2_launch(const ds_attn_fused_params* p, hipStream_t st) {
     void* const mfold = p->mfold;
-    const int C = p->C, nb = attn_out2_blocks(p->N, p->B, C);
+    const int C = p->C, nb = attn_out2_blocks(p->N, fused_batch(p), C);
     const int ntiles = (p->N + 31) / 32, per = (ntiles + nb - 1) / nb;
     hipLaunchKernelGGL(attn_fold_out_kernel, dim3(C / 32, p->B), dim3(256), 0, st, p->ctx, reinterpret_cast<const bf16*>(p->wout_perm),
                        reinterpret_cast<bf16*>(mfold), C);

@@ -801,10 +801,14 @@ int check(const ds_attn_x3_params* p) {
                "attn_x3: null pointer");
     DS_REQUIRE(p->C == 96 || p->C == 192 || p->C == 384, "attn_x3: C=%d unsupported (96, 192, 384)", p->C);
     DS_REQUIRE(p->B > 0 && p->N > 0 && p->nseg > 0, "attn_x3: bad sizes");
+    DS_REQUIRE(p->batch_hint >= 0, "attn_x3: batch_hint must be 0 (use B) or the batch the launch decisions look at, got %d", p->batch_hint);
     if (!ds_aligned16(p->x) || !ds_aligned16(p->wqkv_hl) || (p->qplanes && !ds_aligned16(p->qplanes)) || !ds_aligned16(p->mfold))
         DS_FAIL(DS_EALIGN, "attn_x3: pointers must be 16-byte aligned");
     return DS_OK;
 }
+
+// The batch the batch-dependent choice below looks at: ds_attn_x3_params.batch_hint where the caller gives one, else B.
+int x3_batch(const ds_attn_x3_params* p) { return p->batch_hint > 0 ? p->batch_hint : p->B; }
 
 int z_tiles_per_block(int N, int B, int C) {
     // blocks per (sample, channel group): every CU busy with few, long-lived blocks (a block stages 52 KB of M_b), at least one tile per wave
@@ -886,7 +890,7 @@ extern "C" size_t ds_attn_x3_qplane_bytes(int B, int N) { return (size_t)B * ((N
 extern "C" size_t ds_attn_x3_mfold_bytes(int B, int C) { return (size_t)B * 2 * C * 256; }
 
 extern "C" int ds_attn_x3_stats_parts(const ds_attn_x3_params* p) {
-    const int ntiles = (p->N + 31) / 32, per = z_tiles_per_block(p->N, p->B, p->C);
+    const int ntiles = (p->N + 31) / 32, per = z_tiles_per_block(p->N, x3_batch(p), p->C);
     return ((ntiles + per - 1) / per) * (p->C / 96);
 }
 
@@ -923,7 +927,7 @@ extern "C" int ds_attn_x3_output(const ds_attn_x3_params* p, void* stream) {
                "attn_x3_output: form B needs out and / or out_planes (16-byte aligned), stats_part, on_gamma, on_beta");
     DS_REQUIRE(formb || ds_aligned16(p->y), "attn_x3_output: y must be 16-byte aligned");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int ntiles = (p->N + 31) / 32, per = z_tiles_per_block(p->N, p->B, p->C), nb = (ntiles + per - 1) / per;
+    const int ntiles = (p->N + 31) / 32, per = z_tiles_per_block(p->N, x3_batch(p), p->C), nb = (ntiles + per - 1) / per;
 #if DS_BOUNDS
     x3_publish_bounds(p, DS_K_ATTN_OUT, nb * (p->C / 96), st);
 #endif

@@ -207,6 +207,7 @@ extern "C" int ds_conv1x1_x3(const ds_conv_params* p, void* stream) {
     DS_REQUIRE(p->KH == 1 && p->KW == 1 && p->stride == 1 && p->pad_h == 0 && p->pad_w == 0 && !p->transposed && p->Ho == p->H && p->Wo == p->W,
                "conv1x1_x3: 1x1 stride 1 only");
     DS_REQUIRE(p->B > 0 && p->H > 0 && p->W > 0 && p->Cout > 0, "conv1x1_x3: empty problem");
+    DS_REQUIRE(p->batch_hint >= 0, "conv1x1_x3: batch_hint must be 0 or a batch (this launcher takes no decision from either), got %d", p->batch_hint);
     DS_REQUIRE(p->C0 > 0 && p->C0 % 32 == 0 && p->C1 >= 0 && p->C1 % 32 == 0, "conv1x1_x3: channel counts (%d,%d) must be multiples of 32", p->C0, p->C1);
     DS_REQUIRE(p->C1 == 0 || (p->src1 && p->H1 > 0 && p->W1 > 0), "conv1x1_x3: second source incomplete");
     DS_REQUIRE(p->cout_pad % BN == 0 && p->Cout <= p->cout_pad, "conv1x1_x3: cout_pad %d must be a multiple of %d", p->cout_pad, BN);

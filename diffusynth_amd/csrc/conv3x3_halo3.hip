@@ -656,6 +656,9 @@ int ds_conv3x3_halo3_parts(const ds_conv_params* p) {
     return ((p->H + TH - 1) / TH) * ((p->W + TW - 1) / TW) * (p->cout_pad / BN);
 }
 
+// The batch the pair predicate below looks at: ds_conv_params.batch_hint where the caller gives one, else B.
+static int halo3_batch(const ds_conv_params* p) { return p->batch_hint > 0 ? p->batch_hint : p->B; }
+
 int ds_conv3x3_halo3_launch(const ds_conv_params* p, hipStream_t st) {
     DS_REQUIRE(p->dtype == DS_BF16, "conv3x3_halo3: bf16 only");
     DS_REQUIRE(p->KH == 3 && p->KW == 3 && p->stride == 1 && p->pad_h == 1 && p->pad_w == 1 && !p->transposed,
@@ -689,8 +692,10 @@ int ds_conv3x3_halo3_launch(const ds_conv_params* p, hipStream_t st) {
                "conv3x3_halo3: one sample / the packed weights must stay below 2 GiB (32-bit buffer offsets)");
     DS_REQUIRE((long long)p->H * p->W * p->out_C * (out_mode == 2 ? 4 : 2) < (1ll << 31), "conv3x3_halo3: one output sample must stay below 2 GiB (32-bit buffer offsets)");
     const int twl = halo_twl(p->W), TW = 1 << twl, TH = BM >> twl;
-    // r05: two samples per block where an image fills at most half of the 8 x 32 tile (the deepest level at 128 x 64 latents: 16 x 8)
-    const bool pair = p->flags != 0 && twl == 3 && 2 * p->H <= TH && p->W <= TW && p->ksplit <= 1 && !p->res_steps && p->B >= 2;
+    // r05: two samples per block where an image fills at most half of the 8 x 32 tile (the deepest level at 128 x 64 latents: 16 x 8) — by
+    // the batch the caller decides from (halo3_batch), so that a sample gets the same kernel in every batch; a lone last sample (B odd, or
+    // B = 1 under a larger batch_hint) has its block to itself
+    const bool pair = p->flags != 0 && twl == 3 && 2 * p->H <= TH && p->W <= TW && p->ksplit <= 1 && !p->res_steps && halo3_batch(p) >= 2;
     dim3 grid(((p->H + TH - 1) / TH) * ((p->W + TW - 1) / TW), p->cout_pad / BN, pair ? (p->B + 1) / 2 : p->B * (p->ksplit > 1 ? p->ksplit : 1));
 #if DS_BOUNDS
     {

@@ -357,6 +357,7 @@ int validate(const ds_conv_params* p) {
     const int epc = p->dtype == DS_BF16 ? 8 : 4;
     DS_REQUIRE(p->dtype == DS_F32 || p->dtype == DS_BF16, "conv_igemm: dtype %d", p->dtype);
     DS_REQUIRE(p->B > 0 && p->Ho > 0 && p->Wo > 0 && p->H > 0 && p->W > 0, "conv_igemm: empty problem");
+    DS_REQUIRE(p->batch_hint >= 0, "conv_igemm: batch_hint must be 0 (use B) or the batch the launch decisions look at, got %d", p->batch_hint);
     DS_REQUIRE(p->C0 > 0 && p->C0 % epc == 0 && p->C1 >= 0 && p->C1 % epc == 0,
                "conv_igemm: channel counts (%d,%d) must be multiples of %d", p->C0, p->C1, epc);
     DS_REQUIRE(p->C1 == 0 || (p->src1 && p->H1 > 0 && p->W1 > 0), "conv_igemm: second source incomplete");

@@ -109,6 +109,7 @@ extern "C" int ds_conv_splitk_reduce(const ds_conv_params* p, void* stream) {
     DS_REQUIRE(p && (p->ksplit == 2 || p->ksplit == 3 || p->ksplit == 4 || p->ksplit == 6 || p->ksplit == 8) && p->slab && p->out,
                "splitk_reduce: needs ksplit in {2, 3, 4, 6, 8}, slab and out");
     DS_REQUIRE(p->dtype == DS_BF16, "splitk_reduce: bf16 only");
+    DS_REQUIRE(p->batch_hint >= 0, "splitk_reduce: batch_hint must be 0 or a batch (this launcher takes no decision from either), got %d", p->batch_hint);
     const long nvec = (long)p->Ho * p->Wo * (p->transposed ? 4 : 1) * ((p->Cout + 7) / 8);
     dim3 grid((unsigned)((nvec + RED_BLOCK - 1) / RED_BLOCK), p->B);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

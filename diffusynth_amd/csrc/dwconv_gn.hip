@@ -496,7 +496,9 @@ __global__ __launch_bounds__(NW * 64, 1) void dwconv7_mfma2_kernel(const ds_dwco
     if (NB % 8 == 0) lid = (blockIdx.x & 7) * (NB >> 3) + (blockIdx.x >> 3);
     if (lid >= g.total) return;
     const int nmy = (g.total - lid + NB - 1) / NB;            // this block's chunks: lid, lid + NB, ...
-    const int nt = nmy * g.tpc;                               // ... = nt tiles, walked as one sequence
+    // ... = nt tiles, walked as one sequence.  The last chunk of a channel block is short where chunks of several whole samples do not divide
+    // B (the chunk length is chosen from ds_dwconv_params.batch_hint alone): it is the last chunk of the block that owns it
+    const int nt = nmy * g.tpc - ((lid + (nmy - 1) * NB) / g.ncblk == g.nchunk - 1 ? g.nchunk * g.tpc - p.B * g.tiles : 0);
     const int C = p.C0 + p.C1;
     const bf16* wexp = reinterpret_cast<const bf16*>(p.wexp);
 
@@ -720,7 +722,8 @@ __global__ __launch_bounds__(NW * 64, 1) void dwconv7_mfma2_kernel(const ds_dwco
 }
 
 // The batch the batch-dependent choices below look at: ds_dwconv_params.batch_hint where the caller gives one (the shared prefix of a paired
-// plan runs at half the batch and must group its GroupNorm partials as the plain plan does at the full batch), else B.
+// plan runs at half the batch and must group its GroupNorm partials as the plain plan does at the full batch; a caller that pins one value
+// for every batch it runs), else B.  No choice looks at B itself where a hint is given.
 static int dw_batch(const ds_dwconv_params* p) { return p->batch_hint > 0 ? p->batch_hint : p->B; }
 
 static bool dw_tall(const ds_dwconv_params* p) { return p->W <= 16; }
@@ -731,12 +734,14 @@ static Dw2Geo dw2_geo(const ds_dwconv_params* p) {
     g.tiles = g.tiles_w * ((p->H + th - 1) / th);
     g.ncblk = (p->C0 + p->C1) / MF_CB;
     // chunk = tpc consecutive (sample, tile) items of one channel block: a divisor of a sample's tiles, or whole samples (tpc a multiple
-    // of the tiles of one) — never a run that ends inside one sample and starts inside the next
+    // of the tiles of one, taken where that many samples divide the decision batch) — never a run that ends inside one sample and starts
+    // inside the next.  Where they do not divide B itself (a hint other than B) the last chunk of a channel block is short (the kernel
+    // takes it for the last chunk of its block: at most 256 channel blocks, one per block of the grid at least).
     // The longest such chunk (<= 8 items) that still leaves two chunks per CU: small batches get short chunks (parallelism before amortisation)
     g.tpc = 1;
     for (int d = 2; d <= 8; ++d)
-        if ((g.tiles % d == 0 || (d % g.tiles == 0 && p->B % (d / g.tiles) == 0)) && (long long)dw_batch(p) * g.tiles / d * g.ncblk >= 512) g.tpc = d;
-    g.nchunk = p->B * g.tiles / g.tpc;                        // chunks per channel block
+        if ((g.tiles % d == 0 || (d % g.tiles == 0 && dw_batch(p) % (d / g.tiles) == 0 && g.ncblk <= 256)) && (long long)dw_batch(p) * g.tiles / d * g.ncblk >= 512) g.tpc = d;
+    g.nchunk = (p->B * g.tiles + g.tpc - 1) / g.tpc;          // chunks per channel block (tpc divides B * tiles, or covers whole samples)
     g.total = g.nchunk * g.ncblk;
     return g;
 }

@@ -315,8 +315,12 @@ class _PlanBase:
     def __init__(self, eng, B, H, W):
         self.e, self.B, self.H, self.W = eng, B, H, W
         self.alloc_B = 0         # > B only while a paired plan's shared prefix runs at half the batch (act(): tensors carved at full size)
-        self.Btile = B           # the batch every split-K decision looks at: the FULL batch, also while the shared prefix of a paired (CFG)
-        #                          plan runs at half of it — the prefix then adds its partial sums in the plain plan's order (same bits)
+        self.Btile = getattr(eng, "launch_batch", None) or B
+        #                          the batch every batch-dependent launch decision looks at (split-K factors; through the structs' batch_hint the
+        #                          depthwise family / row ranges / chunks, the halo kernel's pair tile, the attention generations and blocks per
+        #                          sample; the attention segment counts): the FULL batch, also while the shared prefix of a paired (CFG) plan runs
+        #                          at half of it — the prefix then adds its partial sums in the plain plan's order (same bits) — or the engine's
+        #                          pin (UnetEngine.launch_batch), and then never B: workspaces alone are sized from the actual batch
         self.tb_all = self.lab_all = None      # the U-Net's conditioning outputs (time biases, label projections) where its build() makes them
         self.arena = _Arena()
         self.ops = []            # _Op records, in launch order
@@ -506,7 +510,7 @@ class _PlanBase:
                          bias=L.ptr(cw.bias), gn_ab=(gn_ab if gn_src is None else None), fold_t1=L.ptr(cw.t1) if gn_ab else None,
                          fold_t2=L.ptr(cw.t2) if gn_ab else None, ncls=cw.ncls if gn_ab else 1, act=act,
                          res=(res.off if res is not None else None), stats_part=None, B=B, dtype=dtype, tile=tile, wk_order=korder,
-                         flags=flags, **extra)
+                         flags=flags, batch_hint=self.Btile, **extra)
         if want_stats:
             parts = (self.lib.ds_conv1x1_x3_stats_parts if route == "x3" else self.lib.ds_conv_stats_parts)(C.byref(p))
             st = self.raw(B * parts * 2 * 4)
@@ -589,6 +593,10 @@ class UnetEngine(_EngineBase):
     def __init__(self, module, compute_dtype="fp32"):
         self._init_common(module, compute_dtype)
         self.cfg = module.config
+        # None: every plan decides from its own batch.  P >= 1 (ConditionedUnet.pin_launch_batch; U-Net rows, a CFG batch counts double): every
+        # batch-dependent launch decision of every plan is taken as if the batch were P (_PlanBase.Btile), so a sample's partial sums are
+        # grouped — and its result rounded — the same way in whatever batch it travels.  Part of the plan cache key.
+        self.launch_batch = None
         with torch.cuda.device(self.dev):
             self._pack()
             self._pack_done()
@@ -718,6 +726,8 @@ class UnetEngine(_EngineBase):
     # ================================================================== plan
     def _plan(self, B, H, W, has_cond, paired=False):
         key = (B, H, W, has_cond) if not paired else (B, H, W, has_cond, "paired")
+        if self.launch_batch is not None:
+            key += ("pin", self.launch_batch)          # (a plan records the decisions of the pin it was built under)
         return self._cached_plan(key, lambda: _PlanBuilder(self, B, H, W, has_cond, paired))
 
     def forward(self, x, time, condition, paired=False):
@@ -773,7 +783,7 @@ class _PlanBuilder(_PlanBase):
                 ks = max(1, p.ksplit)
                 # conv3x3_halo3.hip, ds_conv_igemm's halo3 dispatch: the 8 x 32 tile holds two images of at most 16 x 8
                 pair = bool(name == "ds_conv_igemm" and p.tile == L.TILE_HALO3_256x96 and p.flags != 0 and p.W <= 8 and 2 * p.H <= 32
-                            and ks == 1 and not p.res_steps and p.B >= 2)
+                            and ks == 1 and not p.res_steps and (p.batch_hint or p.B) >= 2)
                 cat.append((name, p.tile, ks, p.flags, p.res_steps, pair))
             elif name == "ds_dwconv7":
                 fam, ranges, spc = C.c_int32(), C.c_int32(), C.c_int32()
@@ -902,7 +912,7 @@ class _PlanBuilder(_PlanBase):
             # segments of partials: the library's choice for this shape and batch — N / 128 <= 32 for the first-generation context pass, one
             # round of blocks (one segment per wave) for the second generation, which it runs from U-Net batch 96 on (the bf16 tier's second
             # tiling decision that looks at B, after split-K)
-            nseg = self.lib.ds_attn_fused_segments(B, N, Cc)
+            nseg = self.lib.ds_attn_fused_segments(self.Btile, N, Cc)
             part = self.raw(self.lib.ds_linattn_part_floats(B, heads, nseg) * 4)
             ctx = self.raw(B * heads * 1024 * 4)
             y = self.act(Cc, x.H, x.W)
@@ -910,7 +920,8 @@ class _PlanBuilder(_PlanBase):
             fp = L.AttnFusedParams(x=x.off, B=B, N=N, C=Cc, nseg=nseg, wqkv=d["fused"][0].data_ptr(), t1=d["qkv"].t1.data_ptr(),
                                    t2=d["qkv"].t2.data_ptr(), gn_ab=abx[0], label_q=(lab + 4 * d["l_off"]) if lab else None,
                                    lq_stride=e._lab_total, scale=32 ** -0.5, part=part[0], ctx=ctx[0],
-                                   wout_perm=d["fused"][1].data_ptr(), bias_out=d["out"].bias.data_ptr(), y=y.off, stats_part=None)
+                                   wout_perm=d["fused"][1].data_ptr(), bias_out=d["out"].bias.data_ptr(), y=y.off, stats_part=None,
+                                   batch_hint=self.Btile)
             if lazy:
                 fp.gn_ab, fp.gn_part, fp.gn_parts, fp.gn_count, fp.gn_eps = None, xsrc[0], xsrc[1], float(xsrc[2]), xsrc[3]
             mfold = self.raw(B * Cc * 128 * 2) if Cc in (96, 192) else None      # to_out folded into the context (attn_out2.hpp)
@@ -975,7 +986,7 @@ class _PlanBuilder(_PlanBase):
         e, B = self.e, self.B
         N, Cc = x.H * x.W, x.C
         lib, lazy = self.lib, xsrc is not None
-        nseg = lib.ds_attn_x3_segments(B, N, Cc)
+        nseg = lib.ds_attn_x3_segments(self.Btile, N, Cc)          # (segments and blocks per sample by the decision batch; buffers by B)
         part = self.raw(lib.ds_linattn_part_floats(B, 4, nseg) * 4)
         ctx = self.raw(B * 4 * 1024 * 4)
         qpl = self.raw(lib.ds_attn_x3_qplane_bytes(B, N)) if Cc != 96 else None      # (C = 96: q is projected inside the fused pass 2)
@@ -990,7 +1001,7 @@ class _PlanBuilder(_PlanBase):
                             lq_stride=e._lab_total, scale=32 ** -0.5, part=part[0], ctx=ctx[0], qplanes=(qpl[0] if qpl else None), mfold=mf[0],
                             wout=d["x3"][1].data_ptr(), bias_out=d["out"].bias.data_ptr(), y=None, stats_part=None,
                             out=(out.off if out is not None else None), on_gamma=d["on"][0].data_ptr(), on_beta=d["on"][1].data_ptr(), on_eps=1e-5,
-                            out_planes=(pl.off if pl is not None else None))
+                            out_planes=(pl.off if pl is not None else None), batch_hint=self.Btile)
         if lazy:
             fp.gn_ab, fp.gn_part, fp.gn_parts, fp.gn_count, fp.gn_eps = None, xsrc[0], xsrc[1], float(xsrc[2]), xsrc[3]
         parts = lib.ds_attn_x3_stats_parts(C.byref(fp))

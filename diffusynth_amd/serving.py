@@ -8,7 +8,8 @@ one U-Net batch (one plan of the engine, which keeps all plans in one bounded ar
 the results come back in request order.
 No padding to a common width is involved: a note's convolution borders, GroupNorm counts and attention length are those
 of its own width, so each request's result is what its own single-sample call would have produced (bit for bit in the
-fp32 tier with the deterministic samplers, "ddim" and "dpmpp_2m", where a request's result does not depend on per-step noise)."""
+fp32 tier — and in the bf16x3 / bf16 tiers on a model pinned with ``model.pin_launch_batch(n)`` — with the deterministic samplers,
+"ddim" and "dpmpp_2m", where a request's result does not depend on per-step noise)."""
 import numpy as np
 import torch
 

@@ -19,6 +19,7 @@ library or without a GPU ``forward`` raises.
 """
 import ctypes as C
 import math
+import numbers
 import os
 
 import torch
@@ -138,6 +139,7 @@ class ConditionedUnet(nn.Module):
 
         self.compute_dtype = "fp32"   # "fp32" (parity tier) or "bf16" (throughput tier); not part of the state dict
         self.hip_graph = False        # replay each forward plan as one captured HIP graph (small-batch latency path)
+        self.launch_batch = None      # pin_launch_batch(): the batch every launch decision looks at (None: each call's own batch)
         self._engine = None
         self.eval()
 
@@ -163,6 +165,22 @@ class ConditionedUnet(nn.Module):
             self._engine.hip_graph = self.hip_graph
         return self
 
+    def pin_launch_batch(self, n):
+        """Batch-invariant results in every tier: with n >= 1 every batch-dependent launch decision of a forward pass (split-K factors, the
+        depthwise kernel family and its row ranges, the two-samples-per-tile convolution, attention generations, segments and blocks per
+        sample) is taken as if the U-Net batch were n, whatever the batch is.  Then model(x, t, c)[i] is torch.equal to
+        model(x[i:i+1], t[i:i+1], c[i:i+1])[0] at every batch and position, the paired (CFG) plan equals the plain one, and a batch of
+        exactly n gives the bits of the unpinned model at that batch.  n counts U-Net rows: the doubled batch of classifier-free guidance
+        counts double.  The price is speed at batches far from n (DESIGN.md §7b has the table).  None un-pins (the default: every call decides
+        from its own batch).  The fp32 tier takes no batch-dependent decision and is unaffected.  Like use_hip_graph() the pin is not part
+        of the state dict and survives set_compute_dtype(), load_state_dict() and .to()."""
+        if n is not None and (isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1):
+            raise ValueError(f"pin_launch_batch: n must be an integer >= 1 or None, got {n!r}")
+        self.launch_batch = None if n is None else int(n)
+        if self._engine is not None:
+            self._engine.launch_batch = self.launch_batch      # (the pin is part of the plan cache key: no stale plan is replayed)
+        return self
+
     def load_state_dict(self, *a, **k):
         self._engine = None
         return super().load_state_dict(*a, **k)
@@ -185,6 +203,7 @@ class ConditionedUnet(nn.Module):
             from .engine import UnetEngine
             self._engine = UnetEngine(self, self.compute_dtype)
             self._engine.hip_graph = self.hip_graph
+            self._engine.launch_batch = self.launch_batch
         if paired_halves:
             # the contract: x[:B/2] == x[B/2:] and time[:B/2] == time[B/2:]; violating it is undefined behaviour (the
             # first half's prefix is used for both).  What is free on the host is checked; DS_CHECK_PAIRED=1 also compares on the device (a sync).

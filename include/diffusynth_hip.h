@@ -107,6 +107,12 @@ typedef struct {
                                     diffusynth_amd/engine.py:pack_quad_weights),
                                     0 = tap-major [tap*NCC + cc] (generic kernel),
                                     1 = chunk-major [cc*9 + tap] (DS_CONV_TILE_HALO3_256x96 / _N16: one pointer increment per step) */
+    int32_t batch_hint;          /* 0 = B.  The batch the launcher's batch-dependent choice looks at instead of B, as ds_dwconv_params.batch_hint:
+                                    the two-samples-per-block tile of the split-precision DS_CONV_TILE_HALO3_256x96 launches (images of at most
+                                    16 x 8) is taken when this batch is >= 2; the kernel runs any B >= 1 (a lone last sample has its block to
+                                    itself).  Grids, slabs and buffer extents always follow B.  ksplit is the caller's choice already.
+                                    Every entry point that takes this struct rejects a negative value (ds_conv_igemm for all the tiles it
+                                    dispatches, ds_conv1x1_x3, ds_conv_splitk_reduce); only that one launch reads it. */
     float* slab;
     /* alternative to gn_ab: the producer's raw (sum, sumsq) partials [B][gn_parts][2]; every wave reduces them
      * itself (float64) at kernel start, which removes the ds_gn_finalize launch between producer and consumer */
@@ -186,8 +192,10 @@ typedef struct {
     int32_t batch_hint;          /* 0 = B.  The batch every batch-dependent launch decision looks at instead of B (tile or strip kernel and the row
                                     ranges per image of the fp32 kernels, the chunk length of the bf16 matrix-core kernel): the shared prefix of a
                                     paired classifier-free-guidance plan runs at half the batch and passes the FULL batch here, so that its GroupNorm
-                                    partials are grouped - and therefore rounded - exactly as the plain plan's.  Only a chunk of several whole
-                                    samples (bf16, images of fewer than 8 tiles) still has to divide B itself; that does not change the grouping */
+                                    partials are grouped - and therefore rounded - exactly as the plain plan's.  A caller that passes one fixed
+                                    value at every B gets the same choices, and the same bits per sample, at every B: a chunk of several whole
+                                    samples (bf16, images of fewer than 8 tiles) is chosen when it divides THIS batch, and the last chunk of a
+                                    B it does not divide is short (one partial per sample either way) */
 } ds_dwconv_params;
 int ds_dwconv7(const ds_dwconv_params* p, void* stream);
 int ds_dwconv_stats_parts(const ds_dwconv_params* p);
@@ -278,6 +286,10 @@ typedef struct {
                                     LDS, attn_out2.hpp — pay from about 100 samples on: context pass from B >= 96, output pass from B >= 32 at
                                     C = 96 and B >= 96 at C = 192; below that a block stages 50 - 100 KB of weights for a handful of tiles);
                                     1 / 2 = the first / second generation wherever it exists (tests, A/B)                              */
+    int32_t batch_hint;          /* 0 = B.  The batch every batch-dependent launch decision looks at instead of B (gen = 0: which generation runs;
+                                    blocks per sample of the output pass = ds_attn_fused_stats_parts), as ds_dwconv_params.batch_hint: a caller
+                                    that wants a sample's partial sums grouped the same way in every batch passes one fixed value, and takes
+                                    nseg from ds_attn_fused_segments at that same value.  Grids and buffer extents always follow B.     */
 } ds_attn_fused_params;
 int ds_pack_attn_fused(const float* wqkv_384xC, const float* gamma_C, const float* wout_Cx128, void* wqkv_bf16,
                        void* wout_perm_bf16, int C, void* stream);
@@ -350,6 +362,9 @@ typedef struct {
     float* out;                  /* [B][N][C] fp32 or NULL                                              */
     const float* on_gamma; const float* on_beta;   /* [C] affine of the output GroupNorm (to_out.1)     */
     float on_eps;
+    int32_t batch_hint;          /* 0 = B.  The batch the batch-dependent launch decision looks at instead of B (pixel tiles per block of the output
+                                    pass, hence ds_attn_x3_stats_parts), as ds_dwconv_params.batch_hint; nseg is the caller's: from
+                                    ds_attn_x3_segments at that same value.  Grids and buffer extents always follow B. */
     void* out_planes;            /* form B: the block output also (or, with out = NULL, only) as hi / lo bf16 planes [B][N][2C] — the input
                                     format of a DS_CONV_F_SPLIT_IN convolution (the Down / Upsample that follows): no ds_split_planes pass */
 } ds_attn_x3_params;
