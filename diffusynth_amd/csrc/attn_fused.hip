@@ -33,11 +33,9 @@ __device__ __forceinline__ bf16x8 pack8(const float* v) {
     for (int j = 0; j < 8; ++j) o[j] = (bf16)v[j];
     return o;
 }
-__device__ __forceinline__ int acc_row(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }
 
 constexpr int PARTF = 32 + 32 + 1024;
 constexpr float LOG2E = 1.44269504088896340736f;
-__device__ __forceinline__ float exp2f_fast(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32 (flushes denormal results)
 
 // Both passes share one structure: a block is 4 waves = the 4 heads; it walks a contiguous range of 32*T-pixel
 // groups of one sample.  The group's x rows (contiguous in NHWC) are fetched with fully coalesced 16-byte loads one
@@ -157,20 +155,20 @@ __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_ctx_kernel(
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        if (px0 + acc_row(r, fh) >= p.N) ak[r] = -INFINITY;     // exp2(-inf) = 0
+                        if (px0 + acc_row32(r, fh) >= p.N) ak[r] = -INFINITY;     // exp2(-inf) = 0
                         mr = fmaxf(mr, ak[r]);
                     }
                 }
                 mr = fmaxf(mr, __shfl_xor(mr, 32, 64));
                 const float mt = fmaf(ga2, mr, shk2);
                 const float mn = fmaxf(m, mt);                       // finite: every group holds >= 1 real pixel
-                const float sc = exp2f_fast(m - mn);                 // m = -inf on the first tile -> 0
+                const float sc = exp2_hw(m - mn);                 // m = -inf on the first tile -> 0
                 m = mn;
                 const float cexp = shk2 - mn;
                 float P[16], V[16], psum = 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    P[r] = exp2f_fast(fmaf(ga2, ak[r], cexp));
+                    P[r] = exp2_hw(fmaf(ga2, ak[r], cexp));
                     V[r] = ga * av[r] + shv;
                     psum += P[r];
                 }
@@ -193,7 +191,7 @@ __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_ctx_kernel(
         DS_ST(float, out + 32 + frow, DS_BX_AUX0, ls);
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) DS_ST(float, out + 64 + frow * 32 + acc_row(r, fh), DS_BX_AUX0, ctx[r]);   // ctx[d][e]: d on the lane, e in registers
+    for (int r = 0; r < 16; ++r) DS_ST(float, out + 64 + frow * 32 + acc_row32(r, fh), DS_BX_AUX0, ctx[r]);   // ctx[d][e]: d on the lane, e in registers
 }
 
 // ------------------------------------------------------------------------------------------------ pass 2
@@ -260,7 +258,7 @@ __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_out_kernel(
         float shq[16];                                   // additive part of q (fold shift + label_q) for this lane's 16 rows d
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int d = head * 32 + acc_row(r, fh);
+            const int d = head * 32 + acc_row32(r, fh);
             shq[r] = LOG2E * (DS_LD(float, p.t1 + d, DS_BX_T1) - gam * DS_LD(float, p.t2 + d, DS_BX_T2) +
                               (p.label_q ? DS_LD(float, p.label_q + (size_t)b * p.lq_stride + d, DS_BX_AUX3) : 0.f));
         }
@@ -299,7 +297,7 @@ __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_out_kernel(
                 float sq = 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    q[r] = exp2f_fast(q[r] - mxq);
+                    q[r] = exp2_hw(q[r] - mxq);
                     sq += q[r];
                 }
                 sq += __shfl_xor(sq, 32, 64);

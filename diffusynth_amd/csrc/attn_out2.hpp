@@ -24,8 +24,6 @@
 #include <type_traits>
 namespace {
 
-__device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32
-__device__ __forceinline__ int acc_row32(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }   // row of register r in a 32x32 accumulator
 __device__ __forceinline__ bf16x8 pack8f(const float* v) {
     bf16x8 o;
 #pragma unroll

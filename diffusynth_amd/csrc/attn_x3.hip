@@ -16,6 +16,17 @@
 //   pass 2 (attn_x3_z):      Z = M_b . q~ + bias for 96 output channels per block from the q planes (B fragments straight from global
 //                            memory: 1 KB contiguous per instruction), fp32 result through a wave-private LDS transpose as whole 128-byte
 //                            lines, GroupNorm partials of the result.
+//   pass 2 (attn_x3_qz):     C = 96: the q projection of pass 1 and the Z product of pass 2 in one kernel, no q planes.
+//
+// The three big kernels are put together from ONE copy of each part (a fix to a part reaches every kernel that runs it):
+//   XStream::chunk           the chunk step — fence, stage, keep the raw pieces (qz, MODE 2), unconditional refill, fence, operand reads  (pass1, qz)
+//   XStream::for_tiles       the tile driver: the ring slot of a tile's chunk 0 as a compile-time constant                               (pass1, qz)
+//   RowStage                 rows of 16-byte pieces -> LDS, a load half and a store half; load_w_rows (row map), load_mb_rows (c0)      (pass1, z, qz)
+//   read_gn, fill_shq        (a, a . mean) of the input GroupNorm; the additive q table                                                 (pass1, qz)
+//   fill_out_rows            the bias row and, MODE 2, the scale and shift rows of the output GroupNorm                                 (z, qz)
+//   ZOut::block              Z of 32 channels of one tile -> statistics (MODE 1), or transpose, scale / shift / residual, stores         (z, qz)
+//   xcd_block_decode         XCD-aware block order                                                                                      (pass1, z)
+//   launch_pass1, launch_pass2   the launches
 //
 // HBM traffic per pixel at C = 96: 384 B (x) + 512 B (q planes, written) + 512 B (read) + 384 B (y), against 384 + 3 x 1536 + 512 + 512 + 384
 // of the unfused chain.  Where the weights of all four heads do not fit LDS the heads are split over blockIdx.z (x then comes from L2 for
@@ -32,9 +43,6 @@ constexpr int XS = 144;                  // row of a wave's staging tile: 64 B h
 constexpr int XTILE = 32 * XS;           // 4608 B per wave (also the 32 px x 32 ch fp32 transpose tile of pass 2: 128 + 16 B rows)
 constexpr int NW = 8, NT = NW * 64;
 constexpr int QFRAG = 1024, QTILE = 16 * QFRAG;     // q planes: [tile][plane (hi, lo)][head][s][lane half][pixel] x 16 B
-
-__device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32
-__device__ __forceinline__ int acc_row32(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }   // row of register r in a 32x32 accumulator
 
 // v[0..7] -> hi = bf16(v), lo = bf16(v - hi): the two MFMA operands of one fp32 operand (ds_split2: common.hpp)
 __device__ __forceinline__ void split8(const float* v, bf16x8& hi, bf16x8& lo) {
@@ -87,11 +95,15 @@ __device__ __forceinline__ void q_softmax_split(const f32x16& aq, const float* s
 // products (x as A: k / v, x as B: q) are the same 16-byte reads.
 template <int C>
 struct XStream {
+    static constexpr int NCH = C / 32;
     f32x4 raw[2][4];
     const float* x;
     int N, spx, scol;
     char* xs;
-    __device__ __forceinline__ void init(const float* x_, int N_, int lane, char* tile) { x = x_; N = N_; spx = lane >> 3; scol = lane & 7; xs = tile; }
+    const char* xf;      // this lane's operand fragment of the staged chunk (K step ks: + ks * 32, lo: + 64)
+    __device__ __forceinline__ void init(const float* x_, int N_, int lane, char* tile) {
+        x = x_; N = N_; spx = lane >> 3; scol = lane & 7; xs = tile; xf = tile + (lane & 31) * XS + (lane >> 5) * 16;
+    }
     template <int SLOT> __device__ __forceinline__ void issue(int t, int c) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -110,7 +122,110 @@ struct XStream {
             *reinterpret_cast<uint2*>(d + 64) = lo;
         }
     }
+    // The chunk step: stage chunk c of tile t from its ring slot (P0 = slot of the tile's chunk 0, compile time: the ring is two register
+    // sets), hand the raw pieces to keep(), refill the slot with the chunk two ahead in the wave's sequence (the wave's tiles are STRIDE
+    // apart and end before t1), and read the staged chunk back as MFMA operands.
+    // The refill is UNCONDITIONAL — past the wave's last tile it re-reads that tile: under `if (t2 < t1)` the loads sit in a conditional
+    // region, and the wait for the other slot must then also hold on the path that issued nothing: vmcnt(3..0) instead of vmcnt(4),
+    // i.e. every chunk waited for the loads it had just requested.
+    template <int P0, int STRIDE, class Keep>
+    __device__ __forceinline__ void chunk(int c, int t, int t1, bf16x8 (&xh)[2], bf16x8 (&xl)[2], Keep keep) {
+        const int c2 = c + 2 < NCH ? c + 2 : c + 2 - NCH, t2 = c + 2 < NCH ? t : (t + STRIDE < t1 ? t + STRIDE : t);
+        // (scheduling fences: left alone, the scheduler sinks the refill loads to the end of the tile — shorter live ranges — and the
+        // next stage then waits for loads that have only just been requested)
+        __builtin_amdgcn_sched_barrier(0);
+        if (((P0 + c) & 1) == 0) {
+            stage<0>();
+            keep(raw[0]);
+            issue<0>(t2, c2);
+        } else {
+            stage<1>();
+            keep(raw[1]);
+            issue<1>(t2, c2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            xh[ks] = *reinterpret_cast<const bf16x8*>(xf + ks * 32);
+            xl[ks] = *reinterpret_cast<const bf16x8*>(xf + ks * 32 + 64);
+        }
+    }
+    // The tile driver: tile(slot of chunk 0, t) for t = t0, t0 + STRIDE, .. < t1.  With an odd number of chunks per tile the ring slot of
+    // chunk 0 alternates from tile to tile: the loop is unrolled by two so that the slot stays a compile-time constant.
+    template <int STRIDE, class Tile>
+    static __device__ __forceinline__ void for_tiles(int t0, int t1, Tile&& tile) {
+        using I0 = std::integral_constant<int, 0>;
+        using I1 = std::integral_constant<int, 1>;
+        if constexpr (NCH & 1) {
+            for (int t = t0; t < t1; t += 2 * STRIDE) {
+                tile(I0{}, t);
+                if (t + STRIDE < t1) tile(I1{}, t + STRIDE);
+            }
+        } else {
+            for (int t = t0; t < t1; t += STRIDE) tile(I0{}, t);
+        }
+    }
 };
+
+// ---- prologue pieces.  Each staging helper has a load half and a store half: a prologue requests EVERY global load of its tables before
+// its first LDS write (one round trip instead of one per table).
+// Two planes (hi, lo) of ROWS rows of PCS 16-byte pieces, global memory -> LDS rows of `pitch` bytes; src(plane, row) = the row in global memory
+template <int ROWS, int PCS>
+struct RowStage {
+    static constexpr int IT = 2 * ROWS * PCS / NT;
+    static_assert(IT * NT == 2 * ROWS * PCS, "whole staging iterations");
+    u32x4 v[IT];
+    template <int BX, class Src> __device__ __forceinline__ void load(int tid, Src src) {
+#pragma unroll
+        for (int k = 0; k < IT; ++k) {
+            const int i = tid + k * NT, plane = i / (ROWS * PCS), r = (i / PCS) % ROWS, col = i % PCS;
+            v[k] = DS_LD(u32x4, reinterpret_cast<const u32x4*>(src(plane, r) + col * 16), BX);
+        }
+    }
+    __device__ __forceinline__ void store(int tid, char* hi, char* lo, int pitch) const {
+#pragma unroll
+        for (int k = 0; k < IT; ++k) {
+            const int i = tid + k * NT, plane = i / (ROWS * PCS), r = (i / PCS) % ROWS, col = i % PCS;
+            *reinterpret_cast<u32x4*>((plane ? lo : hi) + r * pitch + col * 16) = v[k];
+        }
+    }
+};
+// weight rows of the packed [q | k | v] planes (row map: LDS row -> row of the 384); rows c0 .. c0 + ROWS - 1 of sample b's folded to_out matrix M_b
+template <int C, int ROWS, class RowMap>
+__device__ __forceinline__ void load_w_rows(RowStage<ROWS, C / 8>& s, const ds_attn_x3_params& p, int tid, RowMap row) {
+    const char* const wsrc = reinterpret_cast<const char*>(p.wqkv_hl);
+    s.template load<DS_BX_W>(tid, [&](int plane, int r) { return wsrc + ((size_t)plane * 384 + row(r)) * C * 2; });
+}
+template <int ROWS>
+__device__ __forceinline__ void load_mb_rows(RowStage<ROWS, 16>& s, const ds_attn_x3_params& p, int tid, int b, int C, int c0) {
+    const char* const mb = reinterpret_cast<const char*>(p.mfold) + (size_t)b * 2 * C * 256;
+    s.template load<DS_BX_RES>(tid, [&](int plane, int r) { return mb + ((size_t)plane * C + c0 + r) * 256; });
+}
+
+// (a, a . mean) of the input GroupNorm of sample b: from the raw partials or from finished pairs
+__device__ __forceinline__ void read_gn(const ds_attn_x3_params& p, int b, float& ga, float& gam) {
+    if (p.gn_part) gn_from_partials(p.gn_part, p.gn_parts, p.gn_count, p.gn_eps, b, ga, gam);
+    else { ga = DS_LD(float, p.gn_ab + 2 * b, DS_BX_GNAB); gam = DS_LD(float, p.gn_ab + 2 * b + 1, DS_BX_GNAB); }
+}
+
+// additive part of q (fold + label) in the log2 domain for heads h0 .. h0 + nh - 1, in accumulator order: entry (h, fh, r) = row d =
+// acc_row32(r, fh) of head h0 + h
+__device__ __forceinline__ void fill_shq(const ds_attn_x3_params& p, float* shq, int h0, int nh, int b, float gam, int tid) {
+    for (int i = tid; i < nh * 32; i += NT) {
+        const int d = (h0 + (i >> 5)) * 32 + acc_row32(i & 15, (i >> 4) & 1);
+        shq[i] = LOG2E * (DS_LD(float, p.t1 + d, DS_BX_T1) - gam * DS_LD(float, p.t2 + d, DS_BX_T2) +
+                          (p.label_q ? DS_LD(float, p.label_q + (size_t)b * p.lq_stride + d, DS_BX_AUX3) : 0.f));
+    }
+}
+
+// XCD-aware block order: hardware block L runs on XCD L % 8.  The gridDim.z groups of one (blockIdx.x, sample) read the same stream (x in
+// pass 1, the q planes in pass 2): they are decoded as consecutive work items of ONE XCD (one L2), so the stream leaves HBM once.
+__device__ __forceinline__ void xcd_block_decode(int& group, int& bx, int& b) {
+    const int gx = gridDim.x, gy = gridDim.y, gz = gridDim.z, nwg = gx * gy * gz;
+    int wid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+    if ((nwg & 7) == 0) wid = (wid & 7) * (nwg >> 3) + (wid >> 3);
+    group = wid % gz; bx = (wid / gz) % gx; b = wid / (gz * gx);
+}
 
 // ------------------------------------------------------------------------------------------------ pass 1
 template <int NKS, int HB, bool KV, bool Q>
@@ -129,12 +244,8 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_pass1_kernel(const ds_attn_x3_p
     extern __shared__ __attribute__((aligned(16))) char sm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 31, kg = lane >> 5;
-    // XCD-aware block order: hardware block L runs on XCD L % 8.  The 4 / HB head groups of one (segment block, sample) read the same x:
-    // they are decoded as consecutive work items of ONE XCD (one L2), so x leaves HBM once.
-    const int gx = gridDim.x, gy = gridDim.y, gz = gridDim.z, nwg = gx * gy * gz;
-    int wid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    if ((nwg & 7) == 0) wid = (wid & 7) * (nwg >> 3) + (wid >> 3);
-    const int hg = wid % gz, sb = (wid / gz) % gx, b = wid / (gz * gx);
+    int hg, sb, b;                       // the 4 / HB head groups of one (segment block, sample) read the same x
+    xcd_block_decode(hg, sb, b);
     const int h0 = hg * HB;
     // nseg = p.nseg for a launch that writes partials (one per wave); a q-only launch takes its own count (the launcher's: one round of blocks)
     const int ntiles = (p.N + 31) >> 5, per = (ntiles + nseg - 1) / nseg;
@@ -152,37 +263,17 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_pass1_kernel(const ds_attn_x3_p
 
     // ---- block prologue: the weight rows of this block's heads, hi plane and lo plane, -> LDS (all requested before the first LDS write)
     {
-        const char* const wsrc = reinterpret_cast<const char*>(p.wqkv_hl);
-        constexpr int PCS = C / 8;                                       // 16-byte pieces per row
-        constexpr int TOT = 2 * G::WROWS * PCS, WIT = TOT / NT;
-        static_assert(WIT * NT == TOT, "whole staging iterations");
-        u32x4 wst[WIT];
-#pragma unroll
-        for (int k = 0; k < WIT; ++k) {
-            const int i = tid + k * NT, plane = i / (G::WROWS * PCS), r = (i / PCS) % G::WROWS, col = i % PCS;
+        RowStage<G::WROWS, C / 8> w;
+        load_w_rows<C>(w, p, tid, [&](int r) {
             const int proj = r / (HB * 32), hr = r - proj * (HB * 32);
-            const int src = (KV ? (proj == 0 ? 128 : (proj == 1 ? 256 : 0)) : 0) + h0 * 32 + hr;      // rows of [q | k | v] in the packed weights
-            wst[k] = DS_LD(u32x4, reinterpret_cast<const u32x4*>(wsrc + ((size_t)plane * 384 + src) * C * 2 + col * 16), DS_BX_W);
-        }
-#pragma unroll
-        for (int k = 0; k < WIT; ++k) {
-            const int i = tid + k * NT, plane = i / (G::WROWS * PCS), r = (i / PCS) % G::WROWS, col = i % PCS;
-            *reinterpret_cast<u32x4*>(sm + (plane ? G::OFF_WL : G::OFF_WH) + r * RS + col * 16) = wst[k];
-        }
+            return (KV ? (proj == 0 ? 128 : (proj == 1 ? 256 : 0)) : 0) + h0 * 32 + hr;      // rows of [q | k | v] in the packed weights
+        });
+        w.store(tid, sm + G::OFF_WH, sm + G::OFF_WL, RS);
     }
     float ga, gam;
-    if (p.gn_part) gn_from_partials(p.gn_part, p.gn_parts, p.gn_count, p.gn_eps, b, ga, gam);
-    else { ga = DS_LD(float, p.gn_ab + 2 * b, DS_BX_GNAB); gam = DS_LD(float, p.gn_ab + 2 * b + 1, DS_BX_GNAB); }
+    read_gn(p, b, ga, gam);
     const float ga2 = ga * LOG2E;
-    if constexpr (Q) {
-        // additive part of q in the log2 domain, in accumulator order: entry (h, fh, r) = row d = acc_row32(r, fh) of head h0 + h
-        float* const shq = reinterpret_cast<float*>(sm + G::OFF_SHQ);
-        for (int i = tid; i < HB * 32; i += NT) {
-            const int d = (h0 + (i >> 5)) * 32 + acc_row32(i & 15, (i >> 4) & 1);
-            shq[i] = LOG2E * (DS_LD(float, p.t1 + d, DS_BX_T1) - gam * DS_LD(float, p.t2 + d, DS_BX_T2) +
-                              (p.label_q ? DS_LD(float, p.label_q + (size_t)b * p.lq_stride + d, DS_BX_AUX3) : 0.f));
-        }
-    }
+    if constexpr (Q) fill_shq(p, reinterpret_cast<float*>(sm + G::OFF_SHQ), h0, HB, b, gam, tid);
     float shk2[HB], m[HB], ls[HB];
     f32x16 ctx[HB];
     if constexpr (KV) {
@@ -198,7 +289,6 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_pass1_kernel(const ds_attn_x3_p
     }
     __syncthreads();
     const float* const shq = reinterpret_cast<const float*>(sm + G::OFF_SHQ);
-    const char* const xf = xs + n * XS + kg * 16;                        // operand fragment (K step ks of the chunk): + ks * 32, lo: + 64
     const char* const wf = sm + G::OFF_WH + n * RS + kg * 16;            // weight fragment: + row0 * RS + (c * 32 + ks * 16) * 2, lo: + OFF_WL
     char* const qp = p.qplanes ? reinterpret_cast<char*>(p.qplanes) + (size_t)b * ntiles * QTILE + lane * 16 : nullptr;
 
@@ -208,28 +298,8 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_pass1_kernel(const ds_attn_x3_p
         f32x16 acc[G::NPROJ * HB];
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            // stage chunk c from its slot, then refill the slot with the chunk two ahead in the wave's sequence
-            // (the refill is UNCONDITIONAL — past the wave's last tile it re-reads that tile: under `if (t2 < t1)` the loads sit in a conditional
-            // region, and the wait for the other slot must then also hold on the path that issued nothing: vmcnt(3..0) instead of vmcnt(4),
-            // i.e. every chunk waited for the loads it had just requested)
-            const int c2 = c + 2 < NCH ? c + 2 : c + 2 - NCH, t2 = c + 2 < NCH ? t : min(t + 1, t1 - 1);
-            // (scheduling fences: left alone, the scheduler sinks the refill loads to the end of the tile — shorter live ranges — and the
-            // next stage then waits for loads that have only just been requested)
-            __builtin_amdgcn_sched_barrier(0);
-            if (((P0 + c) & 1) == 0) {
-                xq.template stage<0>();
-                xq.template issue<0>(t2, c2);
-            } else {
-                xq.template stage<1>();
-                xq.template issue<1>(t2, c2);
-            }
-            __builtin_amdgcn_sched_barrier(0);
             bf16x8 xh[2], xl[2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                xh[ks] = *reinterpret_cast<const bf16x8*>(xf + ks * 32);
-                xl[ks] = *reinterpret_cast<const bf16x8*>(xf + ks * 32 + 64);
-            }
+            xq.template chunk<P0, 1>(c, t, t1, xh, xl, [](const f32x4*) {});       // (a wave's tiles are consecutive)
 #pragma unroll
             for (int a = 0; a < G::NPROJ * HB; ++a) {
 #pragma unroll
@@ -310,16 +380,7 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_pass1_kernel(const ds_attn_x3_p
             }
         }
     };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    if constexpr (NCH & 1) {
-        for (int t = t0; t < t1; t += 2) {
-            tile(I0{}, t);
-            if (t + 1 < t1) tile(I1{}, t + 1);
-        }
-    } else {
-        for (int t = t0; t < t1; ++t) tile(I0{}, t);
-    }
+    XStream<C>::template for_tiles<1>(t0, t1, tile);
     // ---- this wave's segment of the partials: [32 max (natural log domain)][32 sum][ctx[d][e]] per head
     if constexpr (KV) {
         if (seg >= p.nseg) return;
@@ -351,8 +412,7 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_pass1_kernel(const ds_attn_x3_p
 
 // form B with out_planes: the block's output also (or only) as hi / lo bf16 planes [B][N][2C] — the input format of the Down / Upsample that
 // follows (DS_CONV_F_SPLIT_IN): no ds_split_planes pass over it
-__device__ __forceinline__ void x3_store_planes(const ds_attn_x3_params& p, int b, int px, int C, int c, const f32x4& v) {
-    bf16* const o2 = reinterpret_cast<bf16*>(p.out_planes) + ((size_t)b * p.N + px) * (2 * C) + c;
+__device__ __forceinline__ void x3_store_planes(bf16* o2, int C, const f32x4& v) {       // o2: the pixel's hi plane at the first of the four channels
     uint2 hi, lo;
     ds_split2(v[0], v[1], hi.x, lo.x);
     ds_split2(v[2], v[3], hi.y, lo.y);
@@ -408,33 +468,150 @@ __global__ __launch_bounds__(256) void attn_x3_fold_kernel(const float* ctx, con
 }
 
 // ------------------------------------------------------------------------------------------------ pass 2
-struct Z2 {
-    static constexpr int M_RS = 2 * 128 + 16;                         // an odd number of 16-byte slots
-    static constexpr int OFF_MH = 0, OFF_ML = 96 * M_RS, OFF_T = 2 * 96 * M_RS, OFF_BIAS = OFF_T + NW * XTILE, OFF_RED = OFF_BIAS + 96 * 4;
-    static constexpr int LDS = OFF_RED + 64 + 2 * 96 * 4;            // (+ scale / shift rows of the output GroupNorm, MODE 2)
-};
+constexpr int M_RS = 2 * 128 + 16;                                   // LDS row of M_b: an odd number of 16-byte slots
 
+// Prologue: the bias row of channels c0 .. c0 + nch - 1 and, in MODE 2, the scale and shift rows of the output GroupNorm (sgam[0 .. nch - 1],
+// sgam[nch .. 2 nch - 1]) from the `parts` partials per sample that MODE 1 wrote
+template <int MODE>
+__device__ __forceinline__ void fill_out_rows(const ds_attn_x3_params& p, float* sbias, float* sgam, int c0, int nch, int parts, int C, int b, int tid) {
+    for (int i = tid; i < nch; i += NT) sbias[i] = DS_LD(float, p.bias_out + c0 + i, DS_BX_BIAS);
+    if constexpr (MODE == 2) {
+        float oa, oam;
+        gn_from_partials(p.stats_part, parts, (double)C * p.N, p.on_eps, b, oa, oam, DS_BX_STATS);
+        // out = x + (a y - a mean) gamma_c + beta_c = x + y (a gamma_c) + (beta_c - a mean gamma_c): the shift gets a row beside the bias,
+        // the scale its own row (the accumulators start from the plain bias: y itself is what gets scaled)
+        for (int i = tid; i < nch; i += NT) {
+            const float gmm = DS_LD(float, p.on_gamma + c0 + i, DS_BX_AUX2);
+            sgam[i] = oa * gmm;
+            sgam[nch + i] = DS_LD(float, p.on_beta + c0 + i, DS_BX_SRC1) - oam * gmm;
+        }
+    }
+}
+
+// The output block of both pass-2 kernels: Z of 32 channels of one tile -> statistics, or stores.
 // MODE 0: y and its GroupNorm partials (form A).  MODE 1: the partials alone.  MODE 2: out = x + GroupNorm(y) (statistics from MODE 1's
 // partials), y itself never leaves the registers.
 template <int MODE>
+struct ZOut {
+    const char* m_l;                 // this lane's A fragment of M_b in LDS (block cb, step hs): + cb * 32 * M_RS + hs * 32; lo plane: + ml_off
+    int ml_off;
+    const float *sbias, *sgam;       // rows of fill_out_rows (nch channels each)
+    int nch;
+    char* tt;                        // the wave's 32 px x 32 ch fp32 transpose tile (144-byte rows)
+    float* yout;                     // y / out of sample b (MODE 2 without `out`: never stored through)
+    bf16* planes;                    // MODE 2: out_planes, or null
+    bool st_f32;                     // the fp32 result is stored (always but in MODE 2 without `out`)
+    int N;
+    int b, C, c0, n, kg, spx, scol;
+    float s1 = 0.f, s2 = 0.f;        // this lane's share of the block's GroupNorm partials
+
+    // The constructor: sample b_ of a tensor of C_ channels, this block's channels from c0_; mh = M_b's hi plane in LDS, the lo plane ml_off_
+    // bytes behind it; sbias_ / sgam_ = rows of fill_out_rows, nch_ channels each; tt_ = the wave's transpose tile.
+    // Build it where the kernel STARTS, with the kernel's other argument reads: built behind the prologue's barrier, the reads of N, out and
+    // out_planes became scalar round trips of their own, one of them in front of the tile loop.
+    __device__ __forceinline__ ZOut(const ds_attn_x3_params& p, int b_, int C_, int c0_, int lane, const char* mh, int ml_off_, const float* sbias_,
+                                    const float* sgam_, int nch_, char* tt_)
+        : m_l(mh + (lane & 31) * M_RS + (lane >> 5) * 16), ml_off(ml_off_), sbias(sbias_), sgam(sgam_), nch(nch_), tt(tt_),
+          yout((MODE == 2 ? (p.out ? p.out : reinterpret_cast<float*>(p.out_planes)) : p.y) + (size_t)b_ * p.N * C_),
+          planes(reinterpret_cast<bf16*>(p.out_planes)), st_f32(MODE != 2 || p.out), N(p.N),
+          b(b_), C(C_), c0(c0_), n(lane & 31), kg(lane >> 5), spx(lane >> 3), scol(lane & 7) {}
+
+    // channels c0 + cb * 32 .. + 31 of tile t from the tile's B fragments (qh / ql[head * 2 + s]); res(i) = the residual x of pixel
+    // t * 32 + i * 8 + spx, channels c0 + cb * 32 + scol * 4 .. + 3 (MODE 2 only)
+    template <class Res>
+    __device__ __forceinline__ void block(const bf16x8* qh, const bf16x8* ql, int cb, int t, Res res) {
+        f32x16 Z;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(sbias + cb * 32 + 16 * kg + 4 * k);      // accumulators start from the bias
+#pragma unroll
+            for (int e = 0; e < 4; ++e) Z[4 * k + e] = bv[e];
+        }
+#pragma unroll
+        for (int hs = 0; hs < 8; ++hs) {
+            const bf16x8 mh = *reinterpret_cast<const bf16x8*>(m_l + cb * 32 * M_RS + hs * 32);
+            const bf16x8 ml = *reinterpret_cast<const bf16x8*>(m_l + ml_off + cb * 32 * M_RS + hs * 32);
+            Z = mma3(mh, ml, qh[hs], ql[hs], Z);
+        }
+        if constexpr (MODE == 1) {
+            // statistics straight from the accumulators: lane = pixel n of the tile (both halves), 16 channels each
+            if (t * 32 + n < N) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    s1 += Z[r];
+                    s2 = fmaf(Z[r], Z[r], s2);
+                }
+            }
+            // (fence: with no store between them the channel blocks of a tile are independent, the scheduler hoists all their fragment
+            // reads (48 at three blocks) to the top of the tile and spills — 644 bytes of scratch per lane, 188 us instead of 90)
+            __builtin_amdgcn_sched_barrier(0);
+            return;
+        }
+        // lane (pixel n, half kg) holds channels c0 + cb*32 + 16 kg + r: 64 contiguous bytes.  Through the wave's LDS tile the stores
+        // become whole 128-byte lines (8 lanes per pixel) — 16-byte pieces from 64 different lines per instruction are bound by the
+        // L2 request rate, not by bytes
+        f32x4 xr[4];
+        if constexpr (MODE == 2) {
+            // the residual, exact fp32, on the contiguous side (requested before the transpose)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) xr[i] = res(i);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = Z[4 * k + e];
+            *reinterpret_cast<f32x4*>(tt + n * XS + kg * 64 + k * 16) = v;
+        }
+        const int ch = c0 + cb * 32 + scol * 4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int pl = i * 8 + spx, px = t * 32 + pl;
+            f32x4 v = *reinterpret_cast<const f32x4*>(tt + pl * XS + scol * 16);
+            if constexpr (MODE == 2) {
+                const f32x4 sc4 = *reinterpret_cast<const f32x4*>(sgam + cb * 32 + scol * 4), sh4 = *reinterpret_cast<const f32x4*>(sgam + nch + cb * 32 + scol * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = xr[i][e] + fmaf(v[e], sc4[e], sh4[e]);
+            }
+            if (px < N) {
+                if (st_f32) DS_ST(f32x4, reinterpret_cast<f32x4*>(yout + (size_t)px * C + ch), DS_BX_OUT, v);
+                if constexpr (MODE == 2) {
+                    if (planes) x3_store_planes(planes + ((size_t)b * N + px) * (2 * C) + ch, C, v);
+                }
+                if constexpr (MODE == 0) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        s1 += v[e];
+                        s2 = fmaf(v[e], v[e], s2);
+                    }
+                }
+            }
+        }
+    }
+};
+
+struct Z2 {
+    static constexpr int OFF_MH = 0, OFF_ML = 96 * M_RS, OFF_T = 2 * 96 * M_RS, OFF_BIAS = OFF_T + NW * XTILE, OFF_RED = OFF_BIAS + 96 * 4, OFF_GAM = OFF_RED + 64;
+    static constexpr int LDS = OFF_GAM + 2 * 96 * 4;                 // (scale / shift rows of the output GroupNorm, MODE 2)
+};
+
+template <int MODE>      // MODE as in ZOut
 __global__ __launch_bounds__(NT, 1) void attn_x3_z_kernel(const ds_attn_x3_params p, const int tiles_per_block) {
     using G = Z2;
     extern __shared__ __attribute__((aligned(16))) char sm[];
     float* const sbias = reinterpret_cast<float*>(sm + G::OFF_BIAS);
+    float* const sgam = reinterpret_cast<float*>(sm + G::OFF_GAM);
     float* const red = reinterpret_cast<float*>(sm + G::OFF_RED);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = lane & 31, kg = lane >> 5;
-    // the C / 96 channel groups of one (tile range, sample) read the same q planes: consecutive work items of one XCD (see pass 1)
-    const int gx = gridDim.x, gy = gridDim.y, gz = gridDim.z, nwg = gx * gy * gz;
-    int wid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    if ((nwg & 7) == 0) wid = (wid & 7) * (nwg >> 3) + (wid >> 3);
-    const int cg = wid % gz, tb = (wid / gz) % gx, b = wid / (gz * gx);
+    int cg, tb, b;                       // the C / 96 channel groups of one (tile range, sample) read the same q planes
+    xcd_block_decode(cg, tb, b);
+    const int gx = gridDim.x, gz = gridDim.z;
     const int C = p.C, c0 = cg * 96;
     const int ntiles = (p.N + 31) >> 5;
     const int t0 = tb * tiles_per_block, t1 = min(ntiles, t0 + tiles_per_block);
     const char* const qp = reinterpret_cast<const char*>(p.qplanes) + (size_t)b * ntiles * QTILE + lane * 16;
-    float* const yout = (MODE == 2 ? (p.out ? p.out : reinterpret_cast<float*>(p.out_planes)) : p.y) + (size_t)b * p.N * C;   // (MODE 2 without `out`: never stored through)
     const float* const xres = p.x + (size_t)b * p.N * C;
+    ZOut<MODE> zo(p, b, C, c0, lane, sm + G::OFF_MH, G::OFF_ML - G::OFF_MH, sbias, sgam, 96, sm + G::OFF_T + wave * XTILE);
 
     // B fragments of a tile: fragment f = plane * 8 + head * 2 + s, 1 KB contiguous per instruction
     bf16x8 qf[16];
@@ -445,120 +622,26 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_z_kernel(const ds_attn_x3_param
     if (t0 + wave < t1) load_q(t0 + wave);
     {
         // this sample's folded to_out matrix, rows c0 .. c0 + 95 of both planes -> LDS
-        const char* mb = reinterpret_cast<const char*>(p.mfold) + (size_t)b * 2 * C * 256;
-        constexpr int MIT = 2 * 96 * 16 / NT;
-        static_assert(MIT * NT == 2 * 96 * 16, "whole staging iterations");
-        u32x4 mst[MIT];
-#pragma unroll
-        for (int k = 0; k < MIT; ++k) {
-            const int i = tid + k * NT, plane = i / (96 * 16), row = (i >> 4) % 96, col = i & 15;
-            mst[k] = DS_LD(u32x4, reinterpret_cast<const u32x4*>(mb + ((size_t)plane * C + c0 + row) * 256 + col * 16), DS_BX_RES);
-        }
-#pragma unroll
-        for (int k = 0; k < MIT; ++k) {
-            const int i = tid + k * NT, plane = i / (96 * 16), row = (i >> 4) % 96, col = i & 15;
-            *reinterpret_cast<u32x4*>(sm + (plane ? G::OFF_ML : G::OFF_MH) + row * G::M_RS + col * 16) = mst[k];
-        }
-        for (int i = tid; i < 96; i += NT) sbias[i] = DS_LD(float, p.bias_out + c0 + i, DS_BX_BIAS);
-        if constexpr (MODE == 2) {
-            float oa, oam;
-            gn_from_partials(p.stats_part, gx * gz, (double)C * p.N, p.on_eps, b, oa, oam, DS_BX_STATS);
-            // out = x + (a y - a mean) gamma_c + beta_c = x + y (a gamma_c) + (beta_c - a mean gamma_c): the bias row becomes the shift,
-            // the scale its own row (the accumulators start from the plain bias: y itself is what gets scaled)
-            float* const sgam = reinterpret_cast<float*>(sm + G::OFF_RED + 64);
-            for (int i = tid; i < 96; i += NT) {
-                const float gmm = DS_LD(float, p.on_gamma + c0 + i, DS_BX_AUX2);
-                sgam[i] = oa * gmm;
-                sgam[96 + i] = DS_LD(float, p.on_beta + c0 + i, DS_BX_SRC1) - oam * gmm;
-            }
-        }
+        RowStage<96, 16> m;
+        load_mb_rows(m, p, tid, b, C, c0);
+        m.store(tid, sm + G::OFF_MH, sm + G::OFF_ML, M_RS);
+        fill_out_rows<MODE>(p, sbias, sgam, c0, 96, gx * gz, C, b, tid);
     }
     __syncthreads();
-    const float* const sgam = reinterpret_cast<const float*>(sm + G::OFF_RED + 64);
-    const char* const m_l = sm + G::OFF_MH + n * G::M_RS + kg * 16;       // A fragment (block cb, step hs): + cb*32*M_RS + hs*32; lo: + OFF_ML
-    char* const tt = sm + G::OFF_T + wave * XTILE;                        // 32 px x 32 ch fp32 transpose tile (144-byte rows)
-    const int spx = lane >> 3, scol = lane & 7;
-    float s1 = 0.f, s2 = 0.f;
     for (int t = t0 + wave; t < t1; t += NW) {
         bf16x8 qc[16];
 #pragma unroll
         for (int f = 0; f < 16; ++f) qc[f] = qf[f];
-        load_q(t + NW < t1 ? t + NW : t);                                 // next tile's fragments under this tile's products (unconditional: see pass 1)
+        load_q(t + NW < t1 ? t + NW : t);                                 // next tile's fragments under this tile's products (unconditional: see XStream::chunk)
 #pragma unroll
-        for (int cb = 0; cb < 3; ++cb) {
-            f32x16 Z;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(sbias + cb * 32 + 16 * kg + 4 * k);      // accumulators start from the bias
-#pragma unroll
-                for (int e = 0; e < 4; ++e) Z[4 * k + e] = bv[e];
-            }
-#pragma unroll
-            for (int hs = 0; hs < 8; ++hs) {
-                const bf16x8 mh = *reinterpret_cast<const bf16x8*>(m_l + cb * 32 * G::M_RS + hs * 32);
-                const bf16x8 ml = *reinterpret_cast<const bf16x8*>(m_l + G::OFF_ML + cb * 32 * G::M_RS + hs * 32);
-                Z = mma3(mh, ml, qc[hs], qc[8 + hs], Z);
-            }
-            if constexpr (MODE == 1) {
-                // statistics straight from the accumulators: lane = pixel n of the tile (both halves), 16 channels each
-                if (t * 32 + n < p.N) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        s1 += Z[r];
-                        s2 = fmaf(Z[r], Z[r], s2);
-                    }
-                }
-                // (fence: with no store between them the three channel blocks are independent, the scheduler hoists all 48 fragment reads
-                // to the top of the tile and spills — 644 bytes of scratch per lane, 188 us instead of 90)
-                __builtin_amdgcn_sched_barrier(0);
-                continue;
-            }
-            // lane (pixel n, half kg) holds channels c0 + cb*32 + 16 kg + r: 64 contiguous bytes.  Through the wave's LDS tile the stores
-            // become whole 128-byte lines (8 lanes per pixel) — 16-byte pieces from 64 different lines per instruction are bound by the
-            // L2 request rate, not by bytes
-            f32x4 xr[4];
-            if constexpr (MODE == 2) {
-                // the residual, exact fp32, on the contiguous side (requested before the transpose)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int px = t * 32 + i * 8 + spx;
-                    xr[i] = DS_LD(f32x4, xres + (size_t)(px < p.N ? px : 0) * C + c0 + cb * 32 + scol * 4, DS_BX_SRC0);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = Z[4 * k + e];
-                *reinterpret_cast<f32x4*>(tt + n * XS + kg * 64 + k * 16) = v;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int pl = i * 8 + spx, px = t * 32 + pl;
-                f32x4 v = *reinterpret_cast<const f32x4*>(tt + pl * XS + scol * 16);
-                if constexpr (MODE == 2) {
-                    const f32x4 sc4 = *reinterpret_cast<const f32x4*>(sgam + cb * 32 + scol * 4), sh4 = *reinterpret_cast<const f32x4*>(sgam + 96 + cb * 32 + scol * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = xr[i][e] + fmaf(v[e], sc4[e], sh4[e]);
-                }
-                if (px < p.N) {
-                    if (MODE != 2 || p.out) DS_ST(f32x4, reinterpret_cast<f32x4*>(yout + (size_t)px * C + c0 + cb * 32 + scol * 4), DS_BX_OUT, v);
-                    if constexpr (MODE == 2) {
-                        if (p.out_planes) x3_store_planes(p, b, px, C, c0 + cb * 32 + scol * 4, v);
-                    }
-                    if constexpr (MODE == 0) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            s1 += v[e];
-                            s2 = fmaf(v[e], v[e], s2);
-                        }
-                    }
-                }
-            }
-        }
+        for (int cb = 0; cb < 3; ++cb)
+            zo.block(qc, qc + 8, cb, t, [&](int i) {
+                const int px = t * 32 + i * 8 + zo.spx;
+                return DS_LD(f32x4, xres + (size_t)(px < p.N ? px : 0) * C + c0 + cb * 32 + zo.scol * 4, DS_BX_SRC0);
+            });
     }
     if constexpr (MODE != 2) {
-        if (p.stats_part) block_stats_write(s1, s2, red, p.stats_part + ((size_t)b * gx * gz + tb * gz + cg) * 2);
+        if (p.stats_part) block_stats_write(zo.s1, zo.s2, red, p.stats_part + ((size_t)b * gx * gz + tb * gz + cg) * 2);
     }
 }
 
@@ -567,29 +650,31 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_z_kernel(const ds_attn_x3_param
 // pixel instead of 2 x 512 B of q planes), projects q for the four heads, and multiplies the softmaxed q~ straight into the output channels.
 template <int NKS>
 struct QZ {
-    static constexpr int C = 16 * NKS, NCH = C / 32, CB = C / 32, RS = 2 * C + 16, M_RS = 2 * 128 + 16;
+    static constexpr int C = 16 * NKS, NCH = C / 32, CB = C / 32, RS = 2 * C + 16;
     static constexpr int OFF_WH = 0, OFF_WL = 128 * RS, OFF_MH = 2 * 128 * RS, OFF_ML = OFF_MH + C * M_RS, OFF_X = OFF_ML + C * M_RS;
     static constexpr int OFF_SHQ = OFF_X + NW * XTILE, OFF_BIAS = OFF_SHQ + 128 * 4, OFF_RED = OFF_BIAS + C * 4, OFF_GAM = OFF_RED + 64;
     static constexpr int LDS = OFF_GAM + 2 * C * 4;
     static_assert(LDS <= 160 * 1024, "fused pass 2 operands must fit the CU's LDS");
 };
 
-template <int NKS, int MODE>      // MODE as in attn_x3_z_kernel
+template <int NKS, int MODE>      // MODE as in ZOut
 __global__ __launch_bounds__(NT, 1) void attn_x3_qz_kernel(const ds_attn_x3_params p, const int tiles_per_block) {
     using G = QZ<NKS>;
     constexpr int C = G::C, NCH = G::NCH, RS = G::RS;
     extern __shared__ __attribute__((aligned(16))) char sm[];
     float* const shq = reinterpret_cast<float*>(sm + G::OFF_SHQ);
     float* const sbias = reinterpret_cast<float*>(sm + G::OFF_BIAS);
+    float* const sgam = reinterpret_cast<float*>(sm + G::OFF_GAM);
     float* const red = reinterpret_cast<float*>(sm + G::OFF_RED);
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 31, kg = lane >> 5;
     const int ntiles = (p.N + 31) >> 5;
     const int t0 = blockIdx.x * tiles_per_block, t1 = min(ntiles, t0 + tiles_per_block);
-    float* const yout = (MODE == 2 ? (p.out ? p.out : reinterpret_cast<float*>(p.out_planes)) : p.y) + (size_t)b * p.N * C;   // (MODE 2 without `out`: never stored through)
 
     XStream<C> xq;
     char* const xs = sm + G::OFF_X + wave * XTILE;
+    // the wave's x tile is consumed when Z is formed: it is the transpose tile then
+    ZOut<MODE> zo(p, b, C, 0, lane, sm + G::OFF_MH, G::OFF_ML - G::OFF_MH, sbias, sgam, C, xs);
     xq.init(p.x + (size_t)b * p.N * C, p.N, lane, xs);
     if (t0 + wave < t1) {
         xq.template issue<0>(t0 + wave, 0);
@@ -597,61 +682,22 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_qz_kernel(const ds_attn_x3_para
     }
     {
         // Wq (rows 0..127 of both planes of the packed qkv weights) and this sample's folded to_out matrix (both planes) -> LDS
-        const char* const wsrc = reinterpret_cast<const char*>(p.wqkv_hl);
-        const char* const mb = reinterpret_cast<const char*>(p.mfold) + (size_t)b * 2 * C * 256;
-        constexpr int PCS = C / 8, WIT = 2 * 128 * PCS / NT, MIT = 2 * C * 16 / NT;
-        static_assert(WIT * NT == 2 * 128 * PCS && MIT * NT == 2 * C * 16, "whole staging iterations");
-        u32x4 wst[WIT], mst[MIT];
-#pragma unroll
-        for (int k = 0; k < WIT; ++k) {
-            const int i = tid + k * NT, plane = i / (128 * PCS), r = (i / PCS) % 128, col = i % PCS;
-            wst[k] = DS_LD(u32x4, reinterpret_cast<const u32x4*>(wsrc + ((size_t)plane * 384 + r) * C * 2 + col * 16), DS_BX_W);
-        }
-#pragma unroll
-        for (int k = 0; k < MIT; ++k) {
-            const int i = tid + k * NT, plane = i / (C * 16), row = (i >> 4) % C, col = i & 15;
-            mst[k] = DS_LD(u32x4, reinterpret_cast<const u32x4*>(mb + ((size_t)plane * C + row) * 256 + col * 16), DS_BX_RES);
-        }
-#pragma unroll
-        for (int k = 0; k < WIT; ++k) {
-            const int i = tid + k * NT, plane = i / (128 * PCS), r = (i / PCS) % 128, col = i % PCS;
-            *reinterpret_cast<u32x4*>(sm + (plane ? G::OFF_WL : G::OFF_WH) + r * RS + col * 16) = wst[k];
-        }
-#pragma unroll
-        for (int k = 0; k < MIT; ++k) {
-            const int i = tid + k * NT, plane = i / (C * 16), row = (i >> 4) % C, col = i & 15;
-            *reinterpret_cast<u32x4*>(sm + (plane ? G::OFF_ML : G::OFF_MH) + row * G::M_RS + col * 16) = mst[k];
-        }
+        RowStage<128, C / 8> w;
+        RowStage<C, 16> m;
+        load_w_rows<C>(w, p, tid, [](int r) { return r; });
+        load_mb_rows(m, p, tid, b, C, 0);
+        w.store(tid, sm + G::OFF_WH, sm + G::OFF_WL, RS);
+        m.store(tid, sm + G::OFF_MH, sm + G::OFF_ML, M_RS);
         float ga, gam;
-        if (p.gn_part) gn_from_partials(p.gn_part, p.gn_parts, p.gn_count, p.gn_eps, b, ga, gam);
-        else { ga = DS_LD(float, p.gn_ab + 2 * b, DS_BX_GNAB); gam = DS_LD(float, p.gn_ab + 2 * b + 1, DS_BX_GNAB); }
-        for (int i = tid; i < 128; i += NT) {
-            const int d = (i >> 5) * 32 + acc_row32(i & 15, (i >> 4) & 1);
-            shq[i] = LOG2E * (DS_LD(float, p.t1 + d, DS_BX_T1) - gam * DS_LD(float, p.t2 + d, DS_BX_T2) +
-                              (p.label_q ? DS_LD(float, p.label_q + (size_t)b * p.lq_stride + d, DS_BX_AUX3) : 0.f));
-        }
-        for (int i = tid; i < C; i += NT) sbias[i] = DS_LD(float, p.bias_out + i, DS_BX_BIAS);
+        read_gn(p, b, ga, gam);
+        fill_shq(p, shq, 0, 4, b, gam, tid);
         if (tid == 0) red[15] = ga * LOG2E;
-        if constexpr (MODE == 2) {
-            float oa, oam;
-            gn_from_partials(p.stats_part, gridDim.x, (double)C * p.N, p.on_eps, b, oa, oam, DS_BX_STATS);
-            float* const sg = reinterpret_cast<float*>(sm + G::OFF_GAM);      // out = x + y (a gamma_c) + (beta_c - a mean gamma_c)
-            for (int i = tid; i < C; i += NT) {
-                const float gmm = DS_LD(float, p.on_gamma + i, DS_BX_AUX2);
-                sg[i] = oa * gmm;
-                sg[C + i] = DS_LD(float, p.on_beta + i, DS_BX_SRC1) - oam * gmm;
-            }
-        }
+        fill_out_rows<MODE>(p, sbias, sgam, 0, C, gridDim.x, C, b, tid);
     }
     __syncthreads();
     const float ga2 = red[15];
     __syncthreads();                       // (red is reused by the statistics reduction at the end)
-    const char* const xf = xs + n * XS + kg * 16;
     const char* const wf = sm + G::OFF_WH + n * RS + kg * 16;
-    const char* const m_l = sm + G::OFF_MH + n * G::M_RS + kg * 16;
-    const int spx = lane >> 3, scol = lane & 7;
-    const float* const sgam = reinterpret_cast<const float*>(sm + G::OFF_GAM);
-    float s1 = 0.f, s2 = 0.f;
 
     auto tile = [&](auto p0c, const int t) {
         constexpr int P0 = decltype(p0c)::value;
@@ -661,32 +707,13 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_qz_kernel(const ds_attn_x3_para
         f32x4 xkeep[MODE == 2 ? NCH : 1][4];
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            const int c2 = c + 2 < NCH ? c + 2 : c + 2 - NCH, t2 = c + 2 < NCH ? t : (t + NW < t1 ? t + NW : t);      // unconditional refill (see pass 1)
-            // (scheduling fences: left alone, the scheduler sinks the refill loads to the end of the tile — shorter live ranges — and the
-            // next stage then waits for loads that have only just been requested)
-            __builtin_amdgcn_sched_barrier(0);
-            if (((P0 + c) & 1) == 0) {
-                xq.template stage<0>();
-                if constexpr (MODE == 2) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) xkeep[c][i] = xq.raw[0][i];
-                }
-                xq.template issue<0>(t2, c2);
-            } else {
-                xq.template stage<1>();
-                if constexpr (MODE == 2) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) xkeep[c][i] = xq.raw[1][i];
-                }
-                xq.template issue<1>(t2, c2);
-            }
-            __builtin_amdgcn_sched_barrier(0);
             bf16x8 xh[2], xl[2];
+            xq.template chunk<P0, NW>(c, t, t1, xh, xl, [&](const f32x4* raw) {       // (a wave's tiles are NW apart)
+                if constexpr (MODE == 2) {
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                xh[ks] = *reinterpret_cast<const bf16x8*>(xf + ks * 32);
-                xl[ks] = *reinterpret_cast<const bf16x8*>(xf + ks * 32 + 64);
-            }
+                    for (int i = 0; i < 4; ++i) xkeep[c][i] = raw[i];
+                }
+            });
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
 #pragma unroll
@@ -705,84 +732,15 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_qz_kernel(const ds_attn_x3_para
         bf16x8 qh[8], ql[8];
 #pragma unroll
         for (int h = 0; h < 4; ++h) q_softmax_split(aq[h], shq + (h * 2 + kg) * 16, ga2, p.scale, qh[2 * h], ql[2 * h], qh[2 * h + 1], ql[2 * h + 1]);
-        // ---- Z[c][px] = sum_{h,d} M_b[c][h*32 + d] q~_h[d][px] + bias[c]; the wave's x tile is consumed: it is the transpose tile now
+        // ---- Z[c][px] = sum_{h,d} M_b[c][h*32 + d] q~_h[d][px] + bias[c].  The residual, exact fp32 (the staged tile holds hi + lo = x to
+        // 2^-17 only): the pieces kept above
+        static_assert(G::CB == NCH, "one 32-channel output block per input chunk");
 #pragma unroll
-        for (int cb = 0; cb < G::CB; ++cb) {
-            f32x16 Z;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(sbias + cb * 32 + 16 * kg + 4 * k);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) Z[4 * k + e] = bv[e];
-            }
-#pragma unroll
-            for (int hs = 0; hs < 8; ++hs) {
-                const bf16x8 mh = *reinterpret_cast<const bf16x8*>(m_l + cb * 32 * G::M_RS + hs * 32);
-                const bf16x8 ml = *reinterpret_cast<const bf16x8*>(m_l + (G::OFF_ML - G::OFF_MH) + cb * 32 * G::M_RS + hs * 32);
-                Z = mma3(mh, ml, qh[hs], ql[hs], Z);
-            }
-            if constexpr (MODE == 1) {
-                if (t * 32 + n < p.N) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        s1 += Z[r];
-                        s2 = fmaf(Z[r], Z[r], s2);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                continue;
-            }
-            f32x4 xr[4];
-            if constexpr (MODE == 2) {
-                // the residual, exact fp32 (the staged tile holds hi + lo = x to 2^-17 only): the pieces kept above
-                static_assert(G::CB == NCH, "one 32-channel output block per input chunk");
-#pragma unroll
-                for (int i = 0; i < 4; ++i) xr[i] = xkeep[cb][i];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = Z[4 * k + e];
-                *reinterpret_cast<f32x4*>(xs + n * XS + kg * 64 + k * 16) = v;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int pl = i * 8 + spx, px = t * 32 + pl;
-                f32x4 v = *reinterpret_cast<const f32x4*>(xs + pl * XS + scol * 16);
-                if constexpr (MODE == 2) {
-                    const f32x4 sc4 = *reinterpret_cast<const f32x4*>(sgam + cb * 32 + scol * 4), sh4 = *reinterpret_cast<const f32x4*>(sgam + C + cb * 32 + scol * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = xr[i][e] + fmaf(v[e], sc4[e], sh4[e]);
-                }
-                if (px < p.N) {
-                    if (MODE != 2 || p.out) DS_ST(f32x4, reinterpret_cast<f32x4*>(yout + (size_t)px * C + cb * 32 + scol * 4), DS_BX_OUT, v);
-                    if constexpr (MODE == 2) {
-                        if (p.out_planes) x3_store_planes(p, b, px, C, cb * 32 + scol * 4, v);
-                    }
-                    if constexpr (MODE == 0) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            s1 += v[e];
-                            s2 = fmaf(v[e], v[e], s2);
-                        }
-                    }
-                }
-            }
-        }
+        for (int cb = 0; cb < G::CB; ++cb) zo.block(qh, ql, cb, t, [&](int i) { return xkeep[MODE == 2 ? cb : 0][i]; });
     };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    if constexpr (NCH & 1) {
-        for (int t = t0 + wave; t < t1; t += 2 * NW) {
-            tile(I0{}, t);
-            if (t + NW < t1) tile(I1{}, t + NW);
-        }
-    } else {
-        for (int t = t0 + wave; t < t1; t += NW) tile(I0{}, t);
-    }
+    XStream<C>::template for_tiles<NW>(t0 + wave, t1, tile);
     if constexpr (MODE != 2) {
-        if (p.stats_part) block_stats_write(s1, s2, red, p.stats_part + ((size_t)b * gridDim.x + blockIdx.x) * 2);
+        if (p.stats_part) block_stats_write(zo.s1, zo.s2, red, p.stats_part + ((size_t)b * gridDim.x + blockIdx.x) * 2);
     }
 }
 
@@ -861,6 +819,23 @@ int launch_pass1(const ds_attn_x3_params* p, hipStream_t st) {
     return DS_OK;
 }
 
+// pass 2 in one of its modes (ZOut): at C = 96 fused with the q projection (one channel group), else from the q planes
+template <int MODE>
+int launch_pass2(const ds_attn_x3_params* p, int nb, int per, hipStream_t st) {
+    if (p->C == 96) {
+        auto kern = attn_x3_qz_kernel<6, MODE>;
+        DS_SET_MAX_LDS(kern, QZ<6>::LDS, "attn_x3_qz");
+        hipLaunchKernelGGL(kern, dim3(nb, p->B), dim3(NT), QZ<6>::LDS, st, *p, per);
+        DS_CHECK_LAUNCH("attn_x3_qz");
+    } else {
+        auto kern = attn_x3_z_kernel<MODE>;
+        DS_SET_MAX_LDS(kern, Z2::LDS, "attn_x3_z");
+        hipLaunchKernelGGL(kern, dim3(nb, p->B, p->C / 96), dim3(NT), Z2::LDS, st, *p, per);
+        DS_CHECK_LAUNCH("attn_x3_z");
+    }
+    return DS_OK;
+}
+
 }  // namespace
 
 #if DS_BOUNDS
@@ -933,26 +908,11 @@ extern "C" int ds_attn_x3_output(const ds_attn_x3_params* p, void* stream) {
 #endif
     hipLaunchKernelGGL(attn_x3_fold_kernel, dim3(p->C / 32, p->B), dim3(256), 0, st, p->ctx, p->wout, reinterpret_cast<bf16*>(p->mfold), p->C);
     DS_CHECK_LAUNCH("attn_x3_fold");
-#define DS_X3_QZ(MODE_)                                                                                         \
-    do {                                                                                                        \
-        DS_SET_MAX_LDS((attn_x3_qz_kernel<6, MODE_>), QZ<6>::LDS, "attn_x3_qz");                                \
-        hipLaunchKernelGGL((attn_x3_qz_kernel<6, MODE_>), dim3(nb, p->B), dim3(NT), QZ<6>::LDS, st, *p, per);   \
-        DS_CHECK_LAUNCH("attn_x3_qz");                                                                          \
-    } while (0)
-#define DS_X3_Z(MODE_)                                                                                              \
-    do {                                                                                                            \
-        DS_SET_MAX_LDS(attn_x3_z_kernel<MODE_>, Z2::LDS, "attn_x3_z");                                              \
-        hipLaunchKernelGGL(attn_x3_z_kernel<MODE_>, dim3(nb, p->B, p->C / 96), dim3(NT), Z2::LDS, st, *p, per);     \
-        DS_CHECK_LAUNCH("attn_x3_z");                                                                               \
-    } while (0)
-    if (p->C == 96) {
-        if (formb) { DS_X3_QZ(1); DS_X3_QZ(2); }
-        else DS_X3_QZ(0);
+    if (formb) {
+        rc = launch_pass2<1>(p, nb, per, st);
+        if (!rc) rc = launch_pass2<2>(p, nb, per, st);
     } else {
-        if (formb) { DS_X3_Z(1); DS_X3_Z(2); }
-        else DS_X3_Z(0);
+        rc = launch_pass2<0>(p, nb, per, st);
     }
-#undef DS_X3_QZ
-#undef DS_X3_Z
-    return DS_OK;
+    return rc;
 }

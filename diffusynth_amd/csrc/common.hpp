@@ -242,6 +242,10 @@ __device__ __forceinline__ void ds_split8(const float* v, u32x4& hi, u32x4& lo) 
     lo = u32x4{l[0], l[1], l[2], l[3]};
 }
 
+// ---- shared by the attention kernels (attn_fused.hip, attn_out2.hpp, attn_x3.hip) ------------------------------------------------------
+__device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32 (flushes denormal results)
+__device__ __forceinline__ int acc_row32(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }   // row of register r of lane half fh in a 32x32 accumulator
+
 // ---- activations (erf GELU like nn.GELU(); x*sigmoid(x) like nn.SiLU / VQGAN swish) ----------------
 // erf by Abramowitz & Stegun 7.1.26 (|abs err| <= 1.5e-7, i.e. fp32 rounding level): one v_rcp, one v_exp
 // and five fma instead of libm erff's ~40 instructions — the GELU epilogue of the 3x3 convolutions

@@ -12,6 +12,15 @@
 #           attn   attn_microbench.py over the four attention levels (-a e.g. "--batch 128 --iters 20")
 #           small  the small-batch workloads: BASELINE configs[1] (batch 16) and batch 1 (bench.py --workload config2 / config1)
 # Rounds are interleaved (A B A B), so drift of the box shows up as disagreement between rounds.
+# The first command that exits non-zero (a fault, a time limit, a result line that does not parse) ends the script with ITS status (the
+# first failing stage of the pipeline: 124 / 134 / 139 of the measured program, not the 1 of the parser that then got no line):
+# nothing more is started on the device after a failure.
+set -o pipefail
+fail() {      # $1 = variant, rest = the pipeline's PIPESTATUS
+  local v=$1 st; shift
+  for st in "$@"; do [ "$st" -ne 0 ] && { echo "ab.sh: variant '$v' exited with status $st: stopping" >&2; exit "$st"; }; done
+  return 0
+}
 MODE=bench; R=2; EXTRA=""
 while getopts "m:r:a:" o; do case $o in m) MODE=$OPTARG;; r) R=$OPTARG;; a) EXTRA=$OPTARG;; *) exit 2;; esac; done
 shift $((OPTIND - 1))
@@ -33,19 +42,19 @@ for r in $(seq 1 $R); do
   case $MODE in
     bench)
       for v in "$@"; do printf "%-52s " "$v"
-        run_variant "$v" timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-secondary --steps 10 --warmup 2 $EXTRA 2>/dev/null | tail -1 | python3 -c "$JSON_LINE"; done;;
+        run_variant "$v" timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-secondary --steps 10 --warmup 2 $EXTRA 2>/dev/null | tail -1 | python3 -c "$JSON_LINE"; fail "$v" "${PIPESTATUS[@]}"; done;;
     small)
       for wl in config2 config1; do for v in "$@"; do printf "%-8s %-44s " $wl "$v"
-        run_variant "$v" timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-secondary --workload $wl --steps 20 $EXTRA 2>/dev/null | tail -1 | python3 -c "$JSON_LINE"; done; done;;
+        run_variant "$v" timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-secondary --workload $wl --steps 20 $EXTRA 2>/dev/null | tail -1 | python3 -c "$JSON_LINE"; fail "$v" "${PIPESTATUS[@]}"; done; done;;
     conv)
       for L in $CONV_LAYERS; do IFS=: read cin cout h w act res <<< "$L"; for v in "$@"; do printf "%-44s " "$v"
-        run_variant "$v" timeout -k 10 120 python tools/conv_microbench.py --cin $cin --cout $cout --h $h --w $w --batch 128 --tile 11 --act $act --res $res --iters 10 $EXTRA 2>&1 | tail -1; done; done;;
+        run_variant "$v" timeout -k 10 120 python tools/conv_microbench.py --cin $cin --cout $cout --h $h --w $w --batch 128 --tile 11 --act $act --res $res --iters 10 $EXTRA 2>&1 | tail -1; fail "$v" "${PIPESTATUS[@]}"; done; done;;
     dw)
       for L in $DW_LAYERS; do IFS=: read c h w <<< "$L"; for v in "$@"; do printf "%-44s " "$v"
-        run_variant "$v" timeout -k 10 120 python tools/dw_microbench.py --c $c --h $h --w $w --batch 128 --iters 20 $EXTRA 2>&1 | tail -1; done; done;;
+        run_variant "$v" timeout -k 10 120 python tools/dw_microbench.py --c $c --h $h --w $w --batch 128 --iters 20 $EXTRA 2>&1 | tail -1; fail "$v" "${PIPESTATUS[@]}"; done; done;;
     attn)
       for L in $ATTN_LAYERS; do IFS=: read c n <<< "$L"; for v in "$@"; do printf "%-44s " "$v"
-        run_variant "$v" timeout -k 10 120 python tools/attn_microbench.py --c $c --n $n --batch 128 --iters 20 $EXTRA 2>&1 | tail -1; done; done;;
+        run_variant "$v" timeout -k 10 120 python tools/attn_microbench.py --c $c --n $n --batch 128 --iters 20 $EXTRA 2>&1 | tail -1; fail "$v" "${PIPESTATUS[@]}"; done; done;;
     *) echo "unknown mode $MODE"; exit 2;;
   esac
 done

@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
 """Compare the kernels of two `hipcc -S` outputs of one translation unit, opcode by opcode:
 
-    python tools/isa_diff.py before.s after.s
+    python tools/isa_diff.py [--arith] before.s after.s
 
 One row per kernel: instruction count, VGPRs, SGPRs, scratch, LDS and code bytes of AFTER (`old>new` where BEFORE differs) and a verdict —
-`identical` (the same instruction lines once branch labels are renumbered), `same opcode histogram`, or the opcodes whose counts differ."""
+`identical` (the same instruction lines once branch labels are renumbered), `same opcode histogram`, or the opcodes whose counts differ.
+--arith adds a line per kernel for refactors that may move address code only: whether the counts of every matrix, LDS, memory, barrier,
+conversion and floating-point opcode (ARITH) equal BEFORE's, scratch is 0, LDS is equal and AFTER has at most 256 VGPRs; exit 1 if not."""
 import collections
 import re
 import sys
 
 META = (("vgpr", r"; NumVgprs: (\d+)"), ("sgpr", r"; TotalNumSgprs: (\d+)"), ("scratch", r"; ScratchSize: (\d+)"),
         ("lds", r"; LDSByteSize: (\d+)"), ("code", r"; codeLenInByte = (\d+)"))
+# what a refactor of a kernel's structure must leave alone (integer, address, compare / select, move, scalar, s_nop and s_waitcnt may differ)
+ARITH = re.compile(r"^(v_mfma|ds_|global_|buffer_|flat_|scratch_|s_barrier|v_exp_|v_cvt)|^v_.*_(f16|f32|f64|bf16)")
 
 
 def kernels(path):
@@ -25,11 +29,14 @@ def kernels(path):
 
 
 if __name__ == "__main__":
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    arith = "--arith" in sys.argv
+    files = [x for x in sys.argv[1:] if x != "--arith"]
+    a, b = kernels(files[0]), kernels(files[1])
+    broken = []
     print("| kernel | instr | vgpr | sgpr | scratch | lds | code | verdict |\n|---|---|---|---|---|---|---|---|")
     for name in sorted(set(a) | set(b)):
         if name not in a or name not in b:
-            print("| %s | only in %s |" % (name, sys.argv[1] if name in a else sys.argv[2]))
+            print("| %s | only in %s |" % (name, files[0] if name in a else files[1]))
             continue
         (ia, ma), (ib, mb) = a[name], b[name]
         ha, hb = (collections.Counter(ln.split()[0] for ln in i) for i in (ia, ib))
@@ -41,3 +48,13 @@ if __name__ == "__main__":
             verdict = " ".join("%s%+d" % (op, hb[op] - ha[op]) for op in sorted(set(ha) | set(hb)) if ha[op] != hb[op])
         cols = [len(ib) if len(ia) == len(ib) else "%d>%d" % (len(ia), len(ib))] + [mb[k] if ma[k] == mb[k] else "%d>%d" % (ma[k], mb[k]) for k, _ in META]
         print("| %s | %s | %s |" % (name, " | ".join(str(c) for c in cols), verdict))
+        if arith:
+            moved = [op for op in sorted(set(ha) | set(hb)) if ha[op] != hb[op] and ARITH.search(op)]
+            ok = not moved and mb["scratch"] == 0 and ma["lds"] == mb["lds"] and mb["vgpr"] <= 256
+            broken += [] if ok else [name]
+            print("|  | arith: %d of %d instructions, counts %s; scratch %d; lds %d = %d; vgpr %d -> %d: %s |" % (
+                sum(n for op, n in hb.items() if ARITH.search(op)), len(ib), "differ in " + " ".join(moved) if moved else "equal",
+                mb["scratch"], ma["lds"], mb["lds"], ma["vgpr"], mb["vgpr"], "ok" if ok else "BROKEN"))
+    if arith:
+        print("kernels that break a condition: %d %s" % (len(broken), " ".join(broken)))
+        sys.exit(1 if broken else 0)
