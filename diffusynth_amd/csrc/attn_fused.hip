@@ -17,61 +17,24 @@
 //
 // HBM traffic per pixel: 2 reads of x (second one L2-resident) + 1 read of x + 1 write of y,
 // instead of x + 2.67x(384 ch) + ... of the unfused chain.
+//
+// This file: the first-generation kernels (attn_fused_ctx, attn_fused_out: block = 4 waves = the 4 heads, x staged in LDS, every weight
+// fragment of a wave in its registers), the weight packing, and the launch decisions and launches of BOTH generations; the
+// second-generation kernels (wave = pixel tile, weights in LDS) are attn_out2.hpp.  Both are put together from the parts of
+// attn_bf16_parts.hpp (x stage, online-softmax tile step, partial write-out, q softmax) and common.hpp (RowStage, read_gn, shq_entry).
 #include "common.hpp"
 #include "conv_epilogue.hpp"   // permlane32_swap
+#include "attn_bf16_parts.hpp"
+#include "attn_out2.hpp"       // the second-generation kernels: one translation unit, one bounds table
 
-#ifndef DS_ATTN_ABL
-#define DS_ATTN_ABL 0   // diagnostic builds only: bit0 no y stores, bit1 no statistics, bit2 no Z phase, bit3 no q softmax, bit4 no x prefetch
-#endif
 int ds_linattn_launch_combine(const ds_attn_params* p, hipStream_t st);  // linattn.hip
 
 namespace {
 
-__device__ __forceinline__ bf16x8 pack8(const float* v) {
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (bf16)v[j];
-    return o;
-}
-
-constexpr int PARTF = 32 + 32 + 1024;
-constexpr float LOG2E = 1.44269504088896340736f;
-
-// Both passes share one structure: a block is 4 waves = the 4 heads; it walks a contiguous range of 32*T-pixel
-// groups of one sample.  The group's x rows (contiguous in NHWC) are fetched with fully coalesced 16-byte loads one
-// group ahead, staged in LDS (rows padded by 16 B: an odd number of 16-byte slots, conflict-free ds_read_b128) and
-// shared by the four heads.  Every weight fragment a wave needs lives in its registers for the whole kernel.
-template <int NKS, int T>
-struct XStage {
-    static constexpr int C = NKS * 16, TP = 32 * T, RS = 2 * C + 16;   // row stride in bytes
-    static constexpr int BYTES = TP * RS;
-    static constexpr int PIECES = TP * 2 * NKS;                        // 16-byte pieces of one group
-    static constexpr int IT = (PIECES + 255) / 256;
-    u32x4 r[IT];
-    // unconditional loads (clamped address + select): a load under a branch would serialise the prefetch
-    __device__ __forceinline__ void load(const bf16* x, int N, int group) {
-        const long base = (long)group * TP * C;
-        const long lim = (long)N * C;
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int piece = threadIdx.x + it * 256;
-            const long e = base + (long)piece * 8;
-            const bool ok = piece < PIECES && e < lim;
-            const u32x4 v = DS_LD(u32x4, x + (ok ? e : 0), DS_BX_SRC0);
-            r[it] = ok ? v : u32x4{0u, 0u, 0u, 0u};
-        }
-    }
-    __device__ __forceinline__ void store(char* buf) const {
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int piece = threadIdx.x + it * 256;
-            if (PIECES % 256 == 0 || piece < PIECES) {
-                const int row = piece / (2 * NKS), col = piece - row * (2 * NKS);
-                *reinterpret_cast<u32x4*>(buf + row * RS + col * 16) = r[it];
-            }
-        }
-    }
-};
+// The x stage of the first generation: 32 T pixels per group.  Its load keeps the piece bound where it would fold (a multiple of 256 pieces):
+// with `e < lim` alone attn_fused_ctx<12, 1> ran 21.70 -> 21.94 us at batch 16 and attn_fused_out<24, 1> 23.92 -> 24.10 us at 32x8, batch
+// 128, each outside the parent's spread; with the bound both are the parent's again (profiles/attn_bf16_refactor_ab.txt)
+template <int NKS, int T> using FusedXStage = XStage<NKS, 32 * T, true>;
 
 // ------------------------------------------------------------------------------------------------ pass 1
 // k, v tiles of this head: acc layout = (lane: d resp. e, registers: 16 pixel rows).  Online softmax over the pixels
@@ -79,8 +42,9 @@ struct XStage {
 // MFMA operands: the rescale by exp(m_old - m_new) is then a per-LANE factor.
 template <int NKS, int T>
 __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_ctx_kernel(const ds_attn_fused_params p) {
-    using XS = XStage<NKS, T>;
-    constexpr int C = XS::C, TP = XS::TP, RS = XS::RS;
+    constexpr int TP = 32 * T;
+    using XS = FusedXStage<NKS, T>;
+    constexpr int C = XS::C, RS = XS::RS;
     constexpr int KCH = NKS < 12 ? NKS : 12;                    // fragment reads in flight per chunk
     extern __shared__ __attribute__((aligned(16))) char sm[];   // x[2][XS::BYTES]
     const int seg = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63, head = threadIdx.x >> 6;
@@ -109,13 +73,11 @@ __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_ctx_kernel(
             }
         }
         float ga, gam;
-        if (p.gn_part) gn_from_partials(p.gn_part, p.gn_parts, p.gn_count, p.gn_eps, b, ga, gam);
-        else { ga = p.gn_ab[2 * b]; gam = p.gn_ab[2 * b + 1]; }
+        read_gn(p, b, ga, gam);
         const float shk = DS_LD(float, p.t1 + nk, DS_BX_T1) - gam * DS_LD(float, p.t2 + nk, DS_BX_T2);
         const float shv = DS_LD(float, p.t1 + nv, DS_BX_T1) - gam * DS_LD(float, p.t2 + nv, DS_BX_T2);
         const float ga2 = ga * LOG2E, shk2 = shk * LOG2E;
-        xs.store(sm);
-        xs.load(x, p.N, g0 + 1 < g1 ? g0 + 1 : g0);
+        xs.next(sm, x, p.N, g0 + 1 < g1 ? g0 + 1 : g0);
         __syncthreads();
         for (int g = g0; g < g1; ++g) {
             const int cur = (g - g0) & 1;
@@ -143,55 +105,21 @@ __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_ctx_kernel(
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                // softmax in the log2 domain: ga2 / shk2 carry log2(e), so every exponential is a bare v_exp_f32
+                // online softmax in the log2 domain: ga2 / shk2 carry log2(e); v is normalised per element before the bf16 pack
                 const int px0 = g * TP + t * 32;
                 const bool full = px0 + 32 <= p.N;                    // wave-uniform: only the last group can be ragged
-                // (ga2 = rstd * log2 e > 0: the maximum of the affine image is the affine image of the raw maximum, and the softmax
-                // argument ga2 * ak + shk2 - max folds into one fma per element)
-                float mr = -INFINITY;
-                if (full) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) mr = fmaxf(mr, ak[r]);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        if (px0 + acc_row32(r, fh) >= p.N) ak[r] = -INFINITY;     // exp2(-inf) = 0
-                        mr = fmaxf(mr, ak[r]);
-                    }
-                }
-                mr = fmaxf(mr, __shfl_xor(mr, 32, 64));
-                const float mt = fmaf(ga2, mr, shk2);
-                const float mn = fmaxf(m, mt);                       // finite: every group holds >= 1 real pixel
-                const float sc = exp2_hw(m - mn);                 // m = -inf on the first tile -> 0
-                m = mn;
-                const float cexp = shk2 - mn;
-                float P[16], V[16], psum = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    P[r] = exp2_hw(fmaf(ga2, ak[r], cexp));
-                    V[r] = ga * av[r] + shv;
-                    psum += P[r];
-                }
-                ls = ls * sc + psum;
-                if (__any(sc != 1.0f)) {                             // the running maximum rarely moves after the first tiles
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) ctx[r] *= sc;
-                }
-                ctx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack8(V), pack8(P), ctx, 0, 0, 0);          // ctx^T[e][d]
-                ctx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack8(V + 8), pack8(P + 8), ctx, 0, 0, 0);
+                float mr;
+                if (full) mr = tile_row_max<false, false>(ak, px0, fh, p.N);
+                else mr = tile_row_max<true, false>(ak, px0, fh, p.N);
+                softmax_tile_step<false>(ak, av, mr, ga2, [&](float mx) { return fmaf(ga2, mx, shk2); }, [&](float mn) { return shk2 - mn; },
+                                         [&](float v) { return ga * v + shv; }, m, ls, ctx);
             }
-            xs.store(sm + (cur ^ 1) * XS::BYTES);          // group g+1 (loaded a full iteration ago)
-            xs.load(x, p.N, g + 2 < g1 ? g + 2 : g);       // group g+2 stays in flight across the next iteration
+            xs.next(sm + (cur ^ 1) * XS::BYTES, x, p.N, g + 2 < g1 ? g + 2 : g);
             __syncthreads();
         }
         ls += __shfl_xor(ls, 32, 64);
     }
-    if (fh == 0) {
-        DS_ST(float, out + frow, DS_BX_AUX0, m * (1.0f / LOG2E));   // back to the natural-log domain of the combine kernel; lane = d
-        DS_ST(float, out + 32 + frow, DS_BX_AUX0, ls);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) DS_ST(float, out + 64 + frow * 32 + acc_row32(r, fh), DS_BX_AUX0, ctx[r]);   // ctx[d][e]: d on the lane, e in registers
+    write_partial(out, frow, fh, m, ls, [&](int r) { return ctx[r]; });
 }
 
 // ------------------------------------------------------------------------------------------------ pass 2
@@ -199,20 +127,11 @@ __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_ctx_kernel(
 // accumulator tile as the B operand; the four heads' Y tiles (bf16, already B-operand shaped) are exchanged through LDS
 // and each wave then produces the 32-channel blocks {wave, wave+4, ..} of Z = Wout . [Y_0..Y_3] + bias.  Z's accumulators
 // hold one pixel per lane: v_permlane32_swap pairs the lane halves into 8 consecutive channels = one 16-byte store.
-// blocks per sample: the whole grid is resident at once (2 blocks per CU; 1 for the 384-channel variant) — a second,
-// partial round of blocks would double the kernel's duration
-static inline int out_blocks(int ngroups, int B, int C) {
-    int nb = (C == 384 ? 256 : 512) / B;
-    if (nb > ngroups) nb = ngroups;
-    if (nb < 1) nb = 1;
-    const int per = (ngroups + nb - 1) / nb;
-    return (ngroups + per - 1) / per;
-}
-
 template <int NKS, int T>
 __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_out_kernel(const ds_attn_fused_params p) {
-    using XS = XStage<NKS, T>;
-    constexpr int C = XS::C, CB = C / 32, TP = XS::TP, RS = XS::RS;
+    constexpr int TP = 32 * T;
+    using XS = FusedXStage<NKS, T>;
+    constexpr int C = XS::C, CB = C / 32, RS = XS::RS;
     constexpr int NCB = (CB + 3) / 4;
     constexpr int KCH = NKS < 12 ? NKS : 12;                    // fragment reads in flight per chunk
     constexpr int YBYTES = 4 * T * 2 * 1024;
@@ -253,17 +172,12 @@ __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_out_kernel(
             }
         }
         float ga, gam;
-        if (p.gn_part) gn_from_partials(p.gn_part, p.gn_parts, p.gn_count, p.gn_eps, b, ga, gam);
-        else { ga = p.gn_ab[2 * b]; gam = p.gn_ab[2 * b + 1]; }
+        read_gn(p, b, ga, gam);
         float shq[16];                                   // additive part of q (fold shift + label_q) for this lane's 16 rows d
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int d = head * 32 + acc_row32(r, fh);
-            shq[r] = LOG2E * (DS_LD(float, p.t1 + d, DS_BX_T1) - gam * DS_LD(float, p.t2 + d, DS_BX_T2) +
-                              (p.label_q ? DS_LD(float, p.label_q + (size_t)b * p.lq_stride + d, DS_BX_AUX3) : 0.f));
-        }
+        for (int r = 0; r < 16; ++r) shq[r] = shq_entry(p, head * 32 + acc_row32(r, fh), b, gam);
         const float ga2 = ga * LOG2E;                    // softmax over d in the log2 domain: bare v_exp_f32
-        xs.store(sm);
+        xs.store(sm);                                    // (XStage::next() spelled out: the bias row is requested between its two halves, as ever)
         for (int i = threadIdx.x; i < C; i += 256) sbias[i] = DS_LD(float, p.bias_out + i, DS_BX_BIAS);
         xs.load(x, p.N, g0 + 1 < g1 ? g0 + 1 : g0);
         __syncthreads();
@@ -286,39 +200,21 @@ __global__ __launch_bounds__(256, NKS >= 24 ? 1 : 2) void attn_fused_out_kernel(
                     for (int ks = 0; ks < KCH; ++ks) aq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wq[k0 + ks], xf[ks], aq, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                float q[16], mxq = -INFINITY;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    q[r] = ga2 * aq[r] + shq[r];
-                    mxq = fmaxf(mxq, q[r]);
-                }
-                if constexpr (!(DS_ATTN_ABL & 8)) {
-                mxq = fmaxf(mxq, __shfl_xor(mxq, 32, 64));
-                float sq = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    q[r] = exp2_hw(q[r] - mxq);
-                    sq += q[r];
-                }
-                sq += __shfl_xor(sq, 32, 64);
-                const float inv = p.scale / sq;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) q[r] *= inv;
-                }
+                bf16x8 qB[2];
+                q_softmax<!(DS_ATTN_ABL & 8)>(aq, [&](int k) { return f32x4{shq[4 * k], shq[4 * k + 1], shq[4 * k + 2], shq[4 * k + 3]}; }, ga2, p.scale, qB[0], qB[1]);
                 // Y_h[e][px] = sum_d ctx[d][e] q~[d][px]: A = ctx^T in the permuted k order of the accumulator operand
                 f32x16 Y;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) Y[r] = 0.f;
-                Y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cA[0], pack8(q), Y, 0, 0, 0);
-                Y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cA[1], pack8(q + 8), Y, 0, 0, 0);
+                Y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cA[0], qB[0], Y, 0, 0, 0);
+                Y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cA[1], qB[1], Y, 0, 0, 0);
                 float yv[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) yv[r] = Y[r];
                 yw[(t * 2 + 0) * 64] = pack8(yv);
                 yw[(t * 2 + 1) * 64] = pack8(yv + 8);
             }
-            xs.store(sm + (cur ^ 1) * XS::BYTES);          // group g+1 (loaded a full iteration ago)
-            if constexpr (!(DS_ATTN_ABL & 16)) xs.load(x, p.N, g + 2 < g1 ? g + 2 : g);   // group g+2 stays in flight across the Z phase and the next Q phase
+            xs.template next<!(DS_ATTN_ABL & 16)>(sm + (cur ^ 1) * XS::BYTES, x, p.N, g + 2 < g1 ? g + 2 : g);   // group g+2 stays in flight across the Z phase and the next Q phase
             __syncthreads();
             // ---- Z[c][px] = sum_{h,e} Wout[c][h*32+e] Y_h[e][px] + bias[c] for this wave's channel blocks
             const bf16x8* const yr = reinterpret_cast<const bf16x8*>(ybase + cur * YBYTES) + lane;
@@ -384,9 +280,48 @@ __global__ void pack_attn_kernel(const float* wqkv, const float* gamma, const fl
     }
 }
 
-// The batch the batch-dependent choices of this file and attn_out2.hpp look at (generation, blocks per sample of the output pass):
-// ds_attn_fused_params.batch_hint where the caller gives one, else B.
+// ------------------------------------------------------------------------------------------------ launch decisions (host)
+// The batch the batch-dependent choices look at (generation, blocks per sample of the output pass): ds_attn_fused_params.batch_hint where
+// the caller gives one, else B.
 int fused_batch(const ds_attn_fused_params* p) { return p->batch_hint > 0 ? p->batch_hint : p->B; }
+
+// pixels per group of the first generation: 64 where the image is large enough to keep every CU busy with fewer, longer iterations
+int group_t(int C, int N) { return (C == 96 && N >= 4096) ? 2 : 1; }
+
+// blocks per sample: the whole grid is resident at once (2 blocks per CU; 1 for the 384-channel variant) — a second,
+// partial round of blocks would double the kernel's duration
+int out_blocks(int ngroups, int B, int C) {
+    int nb = (C == 384 ? 256 : 512) / B;
+    if (nb > ngroups) nb = ngroups;
+    if (nb < 1) nb = 1;
+    const int per = (ngroups + nb - 1) / nb;
+    return (ngroups + per - 1) / per;
+}
+
+// second generation: every CU busy with few, long-lived blocks (a block pays 53 / 104 KB of operand staging)
+int attn_out2_blocks(int N, int B, int C) {
+    const int ntiles = (N + 31) / 32;
+    const int nw = C == 96 ? 4 : 8, per_cu = C == 96 ? 3 : 1;
+    int nb = (256 * per_cu + B - 1) / B;                      // blocks per sample that fill the chip once
+    const int max_nb = (ntiles + nw - 1) / nw;                // at least one tile per wave
+    if (nb > max_nb) nb = max_nb;
+    if (nb < 1) nb = 1;
+    const int per = (ntiles + nb - 1) / nb;
+    return (ntiles + per - 1) / per;
+}
+
+// Which generation runs (ds_attn_fused_params.gen; 0 = by batch): the second-generation kernels stage 50 - 100 KB of weights per block and
+// walk pixel tiles with them — measured per level at U-Net batch 16 / 32 / 64 / 128 (tools/ab.sh -m attn): context pass 53 / 70 / 95 / 176 us
+// against 32 / 52 / 92 / 222 us of the first generation at C = 96, output pass 42 / 62 / 129 / 233 against 35 / 67 / 151 / 272
+bool ctx2_exists(int C, int N) { return C == 96 || C == 192 || (C == 384 && N >= 1024); }
+bool use_ctx2(const ds_attn_fused_params* p) {
+    if (p->gen == 1 || !ctx2_exists(p->C, p->N)) return false;
+    return p->gen == 2 || fused_batch(p) >= 96;
+}
+bool use_out2(const ds_attn_fused_params* p) {
+    if (p->gen == 1 || !p->mfold || !(p->C == 96 || p->C == 192)) return false;
+    return p->gen == 2 || fused_batch(p) >= (p->C == 96 ? 32 : 96);
+}
 
 int check(const ds_attn_fused_params* p) {
     DS_REQUIRE(p && p->x && p->wqkv && p->t1 && p->t2 && (p->gn_ab || p->gn_part) && p->part && p->ctx, "attn_fused: null pointer");
@@ -396,19 +331,6 @@ int check(const ds_attn_fused_params* p) {
     if (!ds_aligned16(p->x) || !ds_aligned16(p->wqkv)) DS_FAIL(DS_EALIGN, "attn_fused: pointers must be 16-byte aligned");
     return DS_OK;
 }
-
-}  // namespace
-
-extern "C" int ds_pack_attn_fused(const float* wqkv, const float* gamma, const float* wout, void* wq_bf16, void* wo_perm_bf16, int C,
-                                  void* stream) {
-    DS_REQUIRE(wqkv && gamma && wout && wq_bf16 && wo_perm_bf16 && C > 0, "pack_attn_fused: bad args");
-    hipLaunchKernelGGL(pack_attn_kernel, dim3((384 * C + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), wqkv, gamma,
-                       wout, (bf16*)wq_bf16, (bf16*)wo_perm_bf16, C);
-    DS_CHECK_LAUNCH("pack_attn_fused");
-    return DS_OK;
-}
-
-namespace {
 
 #if DS_BOUNDS
 void attn_publish_bounds(const ds_attn_fused_params* p, int kernel, int stats_parts, hipStream_t st) {
@@ -430,54 +352,59 @@ void attn_publish_bounds(const ds_attn_fused_params* p, int kernel, int stats_pa
 }
 #endif
 
+// The one launch of this file: LDS limit of the kernel, the operand extents of the bounds build, the launch, its check.
+// (KERN is a template argument: DS_SET_MAX_LDS remembers per expansion, i.e. per kernel, that the limit is set)
+template <auto KERN, class... Extra>
+int launch(const ds_attn_fused_params* p, dim3 grid, int threads, int lds, const char* name, int bx_kernel, int stats_parts, hipStream_t st, Extra... extra) {
+    DS_SET_MAX_LDS(KERN, lds, name);
+#if DS_BOUNDS
+    attn_publish_bounds(p, bx_kernel, stats_parts, st);
+#else
+    (void)bx_kernel; (void)stats_parts;
+#endif
+    hipLaunchKernelGGL(KERN, grid, dim3(threads), lds, st, *p, extra...);
+    DS_CHECK_LAUNCH(name);
+    return DS_OK;
+}
+
 template <int NKS, int T>
 int launch_ctx(const ds_attn_fused_params* p, hipStream_t st) {
-    auto kern = attn_fused_ctx_kernel<NKS, T>;
-    constexpr int lds = 2 * XStage<NKS, T>::BYTES;
-    DS_SET_MAX_LDS(kern, lds, "attn_fused_ctx");
-#if DS_BOUNDS
-    attn_publish_bounds(p, DS_K_ATTN_CTX, 0, st);
-#endif
-    hipLaunchKernelGGL(kern, dim3(p->nseg, p->B), dim3(256), lds, st, *p);
-    DS_CHECK_LAUNCH("attn_fused_ctx");
-    return DS_OK;
+    return launch<attn_fused_ctx_kernel<NKS, T>>(p, dim3(p->nseg, p->B), 256, 2 * FusedXStage<NKS, T>::BYTES, "attn_fused_ctx", DS_K_ATTN_CTX, 0, st);
 }
 
 template <int NKS, int T>
 int launch_out(const ds_attn_fused_params* p, hipStream_t st) {
-    auto kern = attn_fused_out_kernel<NKS, T>;
-    constexpr int lds = 2 * XStage<NKS, T>::BYTES + 2 * 4 * T * 2 * 1024;
-    DS_SET_MAX_LDS(kern, lds, "attn_fused_out");
-    const int ngroups = (p->N + 32 * T - 1) / (32 * T);
-#if DS_BOUNDS
-    attn_publish_bounds(p, DS_K_ATTN_OUT, out_blocks(ngroups, fused_batch(p), p->C), st);
-#endif
-    hipLaunchKernelGGL(kern, dim3(out_blocks(ngroups, fused_batch(p), p->C), p->B), dim3(256), lds, st, *p);
-    DS_CHECK_LAUNCH("attn_fused_out");
+    const int nb = out_blocks((p->N + 32 * T - 1) / (32 * T), fused_batch(p), p->C);
+    return launch<attn_fused_out_kernel<NKS, T>>(p, dim3(nb, p->B), 256, 2 * FusedXStage<NKS, T>::BYTES + 2 * 4 * T * 2 * 1024, "attn_fused_out",
+                                                 DS_K_ATTN_OUT, nb, st);
+}
+
+// (C = 384: two heads per block, half of the k / v weights — 100 KB)
+template <int NKS, int NW, int HPW, int HG>
+int launch_ctx2(const ds_attn_fused_params* p, hipStream_t st) {
+    return launch<attn_ctx2_kernel<NKS, NW, HPW, HG>>(p, dim3((p->nseg + NW - 1) / NW, p->B, HG), NW * 64, C2<NKS>::LDS / HG, "attn_ctx2", DS_K_ATTN_CTX, 0, st);
+}
+
+template <int NKS, int NW>
+int launch_out2(const ds_attn_fused_params* p, hipStream_t st) {
+    const int nb = attn_out2_blocks(p->N, fused_batch(p), p->C), ntiles = (p->N + 31) / 32, per = (ntiles + nb - 1) / nb;
+    const bf16* const mfold = reinterpret_cast<const bf16*>(p->mfold);
+    hipLaunchKernelGGL(attn_fold_out_kernel, dim3(p->C / 32, p->B), dim3(256), 0, st, p->ctx, reinterpret_cast<const bf16*>(p->wout_perm),
+                       reinterpret_cast<bf16*>(p->mfold), p->C);
+    DS_CHECK_LAUNCH("attn_fold_out");
+    return launch<attn_out2_kernel<NKS, NW>>(p, dim3(nb, p->B), NW * 64, O2<NKS>::LDS, "attn_out2", DS_K_ATTN_OUT, nb, st, mfold, per);
+}
+
+}  // namespace
+
+extern "C" int ds_pack_attn_fused(const float* wqkv, const float* gamma, const float* wout, void* wq_bf16, void* wo_perm_bf16, int C,
+                                  void* stream) {
+    DS_REQUIRE(wqkv && gamma && wout && wq_bf16 && wo_perm_bf16 && C > 0, "pack_attn_fused: bad args");
+    hipLaunchKernelGGL(pack_attn_kernel, dim3((384 * C + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), wqkv, gamma,
+                       wout, (bf16*)wq_bf16, (bf16*)wo_perm_bf16, C);
+    DS_CHECK_LAUNCH("pack_attn_fused");
     return DS_OK;
 }
-
-}  // namespace
-#include "attn_out2.hpp"
-namespace {
-
-// Which generation runs (ds_attn_fused_params.gen; 0 = by batch): the second-generation kernels stage 50 - 100 KB of weights per block and
-// walk pixel tiles with them — measured per level at U-Net batch 16 / 32 / 64 / 128 (tools/ab.sh -m attn): context pass 53 / 70 / 95 / 176 us
-// against 32 / 52 / 92 / 222 us of the first generation at C = 96, output pass 42 / 62 / 129 / 233 against 35 / 67 / 151 / 272
-static inline bool ctx2_exists(int C, int N) { return C == 96 || C == 192 || (C == 384 && N >= 1024); }
-static inline bool use_ctx2(const ds_attn_fused_params* p) {
-    if (p->gen == 1 || !ctx2_exists(p->C, p->N)) return false;
-    return p->gen == 2 || fused_batch(p) >= 96;
-}
-static inline bool use_out2(const ds_attn_fused_params* p) {
-    if (p->gen == 1 || !p->mfold || !(p->C == 96 || p->C == 192)) return false;
-    return p->gen == 2 || fused_batch(p) >= (p->C == 96 ? 32 : 96);
-}
-
-// pixels per group: 64 where the image is large enough to keep every CU busy with fewer, longer iterations
-static inline int group_t(int C, int N) { return (C == 96 && N >= 4096) ? 2 : 1; }
-
-}  // namespace
 
 #if DS_BOUNDS
 extern "C" int ds_bounds_fetch_attn_fused(ds_bounds_rec* out, int reset) { return ds_bounds_fetch_tu(out, reset); }
@@ -488,12 +415,8 @@ extern "C" int ds_attn_fused_context(const ds_attn_fused_params* p, void* stream
     if (rc) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int T = group_t(p->C, p->N);
-    if (use_ctx2(p)) {
-#if DS_BOUNDS
-        attn_publish_bounds(p, DS_K_ATTN_CTX, 0, st);
-#endif
-        rc = attn_ctx2_launch(p, st);
-    } else if (p->C == 96) rc = T == 2 ? launch_ctx<6, 2>(p, st) : launch_ctx<6, 1>(p, st);
+    if (use_ctx2(p)) rc = p->C == 96 ? launch_ctx2<6, 4, 4, 1>(p, st) : p->C == 192 ? launch_ctx2<12, 8, 4, 1>(p, st) : launch_ctx2<24, 8, 2, 2>(p, st);
+    else if (p->C == 96) rc = T == 2 ? launch_ctx<6, 2>(p, st) : launch_ctx<6, 1>(p, st);
     else if (p->C == 192) rc = launch_ctx<12, 1>(p, st);
     else rc = launch_ctx<24, 1>(p, st);
     if (rc) return rc;
@@ -510,10 +433,7 @@ extern "C" int ds_attn_fused_output(const ds_attn_fused_params* p, void* stream)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (use_out2(p)) {
         DS_REQUIRE(ds_aligned16(p->mfold) && ds_aligned16(p->y), "attn_fused_output: mfold / y must be 16-byte aligned");
-#if DS_BOUNDS
-        attn_publish_bounds(p, DS_K_ATTN_OUT, attn_out2_blocks(p->N, fused_batch(p), p->C), st);
-#endif
-        return attn_out2_launch(p, st);
+        return p->C == 96 ? launch_out2<6, 4>(p, st) : launch_out2<12, 8>(p, st);
     }
     const int T = group_t(p->C, p->N);
     if (p->C == 96) return T == 2 ? launch_out<6, 2>(p, st) : launch_out<6, 1>(p, st);

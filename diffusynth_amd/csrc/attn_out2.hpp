@@ -18,18 +18,13 @@
 //   * Wq (128 x C) and M_b (C x 128) live in LDS (53 KB at C = 96: three 4-wave blocks per CU; 104 KB at C = 192: one 8-wave block),
 //     read as A fragments; x fragments come straight from global memory (a lane reads 16 bytes of its pixel row per K step: the rows'
 //     other bytes are the next K steps' — served by L1) and are prefetched one tile ahead into the registers the q MFMAs just freed.
-// (included by attn_fused.hip: one translation unit, one bounds table)
+// (the kernels alone, from the parts of attn_bf16_parts.hpp; included at the top of attn_fused.hip, which holds their launches: one
+// translation unit, one bounds table)
 #pragma once
 
 #include <type_traits>
+#include "attn_bf16_parts.hpp"
 namespace {
-
-__device__ __forceinline__ bf16x8 pack8f(const float* v) {
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (bf16)v[j];
-    return o;
-}
 
 template <int NKS>
 struct O2 {
@@ -83,53 +78,23 @@ __global__ __launch_bounds__(NW * 64, NKS == 6 ? 3 : 2) void attn_out2_kernel(co
 
     // x fragments of a tile: lane (pixel n, k group kg) reads channels ks*16 + kg*8 .. + 7 of its pixel for every K step
     bf16x8 xf[NKS];
-    auto load_x = [&](int t) {
-        // (pixels past the end of a ragged last tile read pixel 0 instead: their columns are computed and never stored)
-        const int px = t * 32 + n;
-        const bf16* row = x + (size_t)(px < p.N ? px : 0) * C + kg * 8;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) xf[ks] = DS_LD(bf16x8, row + ks * 16, DS_BX_SRC0);
-    };
-    if (t0 + wave < t1) load_x(t0 + wave);
+    if (t0 + wave < t1) load_x_frags(xf, x, p.N, t0 + wave, n, kg);
 
     // ---- block prologue: Wq rows 0..127 of the packed qkv weights and this sample's folded to_out matrix -> LDS
     {
-        // (all loads of the block's operands requested before the first LDS write: as a `for (i = tid; ...; i += NT)` loop every iteration
-        // was load -> s_waitcnt vmcnt(0) -> ds_write, twelve serial memory round trips per block)
-        const char* wq = reinterpret_cast<const char*>(p.wqkv);
-        const char* mb = reinterpret_cast<const char*>(mfold) + (size_t)b * C * 256;
-        constexpr int WIT = 128 * 2 * NKS / NT, MIT = C * 16 / NT;
-        static_assert(WIT * NT == 128 * 2 * NKS && MIT * NT == C * 16, "whole staging iterations");
-        u32x4 wst[WIT], mst[MIT];
-#pragma unroll
-        for (int k = 0; k < WIT; ++k) {
-            const int i = tid + k * NT, row = i / (2 * NKS), col = i - row * (2 * NKS);
-            wst[k] = DS_LD(u32x4, reinterpret_cast<const u32x4*>(wq + ((size_t)row * C * 2 + col * 16)), DS_BX_W);
-        }
-#pragma unroll
-        for (int k = 0; k < MIT; ++k) {
-            const int i = tid + k * NT, row = i >> 4, col = i & 15;
-            mst[k] = DS_LD(u32x4, reinterpret_cast<const u32x4*>(mb + ((size_t)row * 256 + col * 16)), DS_BX_RES);
-        }
-#pragma unroll
-        for (int k = 0; k < WIT; ++k) {
-            const int i = tid + k * NT, row = i / (2 * NKS), col = i - row * (2 * NKS);
-            *reinterpret_cast<u32x4*>(sm + G::OFF_WQ + row * G::WQ_RS + col * 16) = wst[k];
-        }
-#pragma unroll
-        for (int k = 0; k < MIT; ++k) {
-            const int i = tid + k * NT, row = i >> 4, col = i & 15;
-            *reinterpret_cast<u32x4*>(sm + G::OFF_M + row * G::M_RS + col * 16) = mst[k];
-        }
+        // (all loads of the block's operands requested before the first LDS write: RowStage)
+        const char* const wq = reinterpret_cast<const char*>(p.wqkv);
+        const char* const mb = reinterpret_cast<const char*>(mfold) + (size_t)b * C * 256;
+        RowStage<1, 128, 2 * NKS, NT> w;
+        RowStage<1, C, 16, NT> mst;
+        static_assert(decltype(w)::WHOLE && decltype(mst)::WHOLE, "whole staging iterations");
+        w.template load<DS_BX_W>(tid, [&](int, int r) { return wq + (size_t)r * C * 2; });
+        mst.template load<DS_BX_RES>(tid, [&](int, int r) { return mb + (size_t)r * 256; });
+        w.store(tid, sm + G::OFF_WQ, G::WQ_RS);
+        mst.store(tid, sm + G::OFF_M, G::M_RS);
         float ga, gam;
-        if (p.gn_part) gn_from_partials(p.gn_part, p.gn_parts, p.gn_count, p.gn_eps, b, ga, gam);
-        else { ga = p.gn_ab[2 * b]; gam = p.gn_ab[2 * b + 1]; }
-        // additive part of q in the log2 domain, in accumulator order: entry (h, fh, r) = row d = h*32 + acc_row32(r, fh)
-        for (int i = tid; i < 128; i += NT) {
-            const int d = (i >> 5) * 32 + acc_row32(i & 15, (i >> 4) & 1);
-            shq[i] = LOG2E * (DS_LD(float, p.t1 + d, DS_BX_T1) - gam * DS_LD(float, p.t2 + d, DS_BX_T2) +
-                              (p.label_q ? DS_LD(float, p.label_q + (size_t)b * p.lq_stride + d, DS_BX_AUX3) : 0.f));
-        }
+        read_gn(p, b, ga, gam);
+        fill_shq<NT>(p, shq, 0, 4, b, gam, tid);
         for (int i = tid; i < C; i += NT) sbias[i] = DS_LD(float, p.bias_out + i, DS_BX_BIAS);
         if (tid == 0) red[15] = ga * LOG2E;
     }
@@ -158,30 +123,8 @@ __global__ __launch_bounds__(NW * 64, NKS == 6 ? 3 : 2) void attn_out2_kernel(co
                 for (int ks = 1; ks < NKS; ++ks) aq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], aq, 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (h == 3 && t + NW < t1) load_x(t + NW);               // the x fragments are consumed: fetch the next tile's into the same registers
-            float q[16], mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x4 sh = *reinterpret_cast<const f32x4*>(shq + (h * 2 + kg) * 16 + 4 * k);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    q[4 * k + e] = fmaf(ga2, aq[4 * k + e], sh[e]);
-                    mx = fmaxf(mx, q[4 * k + e]);
-                }
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            float sq = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                q[r] = exp2_hw(q[r] - mx);
-                sq += q[r];
-            }
-            sq += __shfl_xor(sq, 32, 64);
-            const float inv = p.scale / sq;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) q[r] *= inv;
-            qB[h][0] = pack8f(q);
-            qB[h][1] = pack8f(q + 8);
+            if (h == 3 && t + NW < t1) load_x_frags(xf, x, p.N, t + NW, n, kg);               // the x fragments are consumed: fetch the next tile's into the same registers
+            q_softmax(aq, [&](int k) { return *reinterpret_cast<const f32x4*>(shq + (h * 2 + kg) * 16 + 4 * k); }, ga2, p.scale, qB[h][0], qB[h][1]);
         }
         // ---- Z[c][px] = sum_{h,d} M_b[c][h*32 + d] q~_h[d][px] + bias[c]: lane = pixel, registers = 16 consecutive channels
         const int px = t * 32 + n;
@@ -212,7 +155,7 @@ __global__ __launch_bounds__(NW * 64, NKS == 6 ? 3 : 2) void attn_out2_kernel(co
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = Z[r];
             if (okp) {
-                const bf16x8 y0 = pack8f(v), y1 = pack8f(v + 8);
+                const bf16x8 y0 = pack8(v), y1 = pack8(v + 8);
                 DS_ST(bf16x8, reinterpret_cast<bf16x8*>(yrow + cb * 32), DS_BX_OUT, y0);
                 DS_ST(bf16x8, reinterpret_cast<bf16x8*>(yrow + cb * 32 + 8), DS_BX_OUT, y1);
                 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -230,10 +173,6 @@ __global__ __launch_bounds__(NW * 64, NKS == 6 ? 3 : 2) void attn_out2_kernel(co
     }
     if (p.stats_part) block_stats_write(s1, s2, red, p.stats_part + ((size_t)b * gridDim.x + blockIdx.x) * 2);
 }
-
-}  // namespace
-
-namespace {
 
 // ------------------------------------------------------------------------------------------------ context pass, second generation
 // The same structure for pass 1 (k / v projection, softmax over the pixels, ctx += P^T V): wave = 32-pixel tile x all four heads (C = 96) or two of them (C = 192).
@@ -264,39 +203,21 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_ctx2_kernel(const ds_attn_fus
     const int t0 = min(ntiles, seg * per), t1 = min(ntiles, t0 + per);     // an empty segment writes the neutral partial (max = -inf, sum = 0)
 
     bf16x8 xf[NKS];
-    auto load_x = [&](int t) {
-        // (pixels past the end of a ragged last tile read pixel 0 instead: finite values whose softmax weight is set to exactly 0)
-        const int px = t * 32 + n;
-        const bf16* row = x + (size_t)(px < p.N ? px : 0) * C + kg * 8;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) xf[ks] = DS_LD(bf16x8, row + ks * 16, DS_BX_SRC0);
-    };
-    if (t0 < t1) load_x(t0);
+    if (t0 < t1) load_x_frags(xf, x, p.N, t0, n, kg);
     {
         // rows 128 .. 255 of the packed qkv weights: k heads, 256 .. 383: v heads; LDS: this block's HB k heads, then its HB v heads
-        // (all requested before the first LDS write, in two halves: see attn_out2_kernel)
-        const char* wkv = reinterpret_cast<const char*>(p.wqkv);
-        constexpr int WIT = 2 * HB * 32 * 2 * NKS / NT;
-        static_assert(WIT * NT == 2 * HB * 32 * 2 * NKS && WIT % 2 == 0, "whole staging iterations");
+        // (all requested before the first LDS write, in two halves — k rows, v rows: RowStage)
+        const char* const wkv = reinterpret_cast<const char*>(p.wqkv);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-            u32x4 wst[WIT / 2];
-#pragma unroll
-            for (int k = 0; k < WIT / 2; ++k) {
-                const int i = tid + (half * (WIT / 2) + k) * NT, row = i / (2 * NKS), col = i - row * (2 * NKS);
-                const int src = row < HB * 32 ? 128 + blockIdx.z * HB * 32 + row : 256 + blockIdx.z * HB * 32 + (row - HB * 32);
-                wst[k] = DS_LD(u32x4, reinterpret_cast<const u32x4*>(wkv + ((size_t)src * C * 2 + col * 16)), DS_BX_W);
-            }
-#pragma unroll
-            for (int k = 0; k < WIT / 2; ++k) {
-                const int i = tid + (half * (WIT / 2) + k) * NT, row = i / (2 * NKS), col = i - row * (2 * NKS);
-                *reinterpret_cast<u32x4*>(sm + row * G::RS + col * 16) = wst[k];
-            }
+            RowStage<1, HB * 32, 2 * NKS, NT> w;
+            static_assert(decltype(w)::WHOLE, "whole staging iterations");
+            w.template load<DS_BX_W>(tid, [&](int, int r) { return wkv + (size_t)(128 + half * 128 + blockIdx.z * HB * 32 + r) * C * 2; });
+            w.store(tid, sm + half * HB * 32 * G::RS, G::RS);
         }
     }
     float ga, gam;
-    if (p.gn_part) gn_from_partials(p.gn_part, p.gn_parts, p.gn_count, p.gn_eps, b, ga, gam);
-    else { ga = p.gn_ab[2 * b]; gam = p.gn_ab[2 * b + 1]; }
+    read_gn(p, b, ga, gam);
     const float ga2 = ga * LOG2E;
     float shk2[HPW], m[HPW], ls[HPW];
     f32x16 ctx[HPW];
@@ -346,45 +267,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_ctx2_kernel(const ds_attn_fus
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (h == HPW - 1 && t + 1 < t1) load_x(t + 1);           // the x fragments are consumed: the next tile's go into the same registers
-            // online softmax over the pixels in the log2 domain (ga2 > 0: the maximum is taken on the raw accumulators)
-            if constexpr (decltype(ragged)::value) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (px0 + acc_row32(r, kg) >= p.N) ak[r] = -INFINITY;       // exp2(-inf) = 0
-            }
-            float mr = ak[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mr = fmaxf(mr, ak[r]);
-            mr = fmaxf(mr, __shfl_xor(mr, 32, 64));
-            const float mn = fmaxf(m[h], fmaf(ga2, mr, shk2[h]));     // finite: a tile holds >= 1 real pixel
-            const float sc = exp2_hw(m[h] - mn);                      // m = -inf on the wave's first tile -> 0
-            m[h] = mn;
-            const float cexp = shk2[h] - mn;
-            // This kernel is bound by its VALU instruction count (profiles/r03_attn_pmc.txt), so per element only what must be: the exponential's
-            // argument (1 fma), the exponential, one add for the denominator, the two bf16 conversions.  v enters the context RAW — its
-            // normalisation is affine and is applied to the finished context (ctx = ga * ctx_raw + shv[e] * sum_px P, see the write-out).
-            float P[16], V[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                P[r] = exp2_hw(fmaf(ga2, ak[r], cexp));
-                V[r] = av[r];
-            }
-            const bf16x8 p0 = pack8f(P), p1 = pack8f(P + 8);
-            float psum = 0.f, ps1 = 0.f;                              // (two chains; v_dot2c_f32_bf16 on the packed pairs measured slower:
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {                             //  21 cycles per instruction beside a busy matrix pipe against 2 x 8.4)
-                psum += P[r];
-                ps1 += P[8 + r];
-            }
-            psum += ps1;
-            ls[h] = fmaf(ls[h], sc, psum);
-            if (__any(sc != 1.0f)) {                                  // the running maximum rarely moves after the first tiles
-#pragma unroll
-                for (int r = 0; r < 16; ++r) ctx[h][r] *= sc;
-            }
-            ctx[h] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack8f(V), p0, ctx[h], 0, 0, 0);          // ctx^T[e][d]
-            ctx[h] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack8f(V + 8), p1, ctx[h], 0, 0, 0);
+            if (h == HPW - 1 && t + 1 < t1) load_x_frags(xf, x, p.N, t + 1, n, kg);           // the x fragments are consumed: the next tile's go into the same registers
+            // Online softmax over the pixels.  This kernel is bound by its VALU instruction count (profiles/r03_attn_pmc.txt), so per element
+            // only what must be: the exponential's argument (1 fma), the exponential, one add for the denominator (two chains), the two bf16
+            // conversions.  v enters the context RAW — its normalisation is affine and is applied to the finished context
+            // (ctx = ga * ctx_raw + shv[e] * sum_px P, see the write-out).
+            const float mr = tile_row_max<decltype(ragged)::value, true>(ak, px0, kg, p.N);
+            softmax_tile_step<true>(ak, av, mr, ga2, [&](float mx) { return fmaf(ga2, mx, shk2[h]); }, [&](float mn) { return shk2[h] - mn; },
+                                    [](float v) { return v; }, m[h], ls[h], ctx[h]);
         }
     };
     {
@@ -397,69 +287,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_ctx2_kernel(const ds_attn_fus
     if (seg >= nseg) return;
 #pragma unroll
     for (int h = 0; h < HPW; ++h) {
-        float* out = p.part + (((size_t)b * 4 + h0 + h) * nseg + seg) * (32 + 32 + 1024);
+        float* out = p.part + (((size_t)b * 4 + h0 + h) * nseg + seg) * PARTF;
         const float lsum = ls[h] + __shfl_xor(ls[h], 32, 64);
-        if (kg == 0) {
-            DS_ST(float, out + n, DS_BX_AUX0, m[h] * (1.0f / LOG2E));
-            DS_ST(float, out + 32 + n, DS_BX_AUX0, lsum);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int e = acc_row32(r, kg), nv = 256 + (h0 + h) * 32 + e;                 // v's normalisation, applied once: + shv[e] * sum_px P[px][d]
+        write_partial(out, n, kg, m[h], lsum, [&](int r) {
+            const int nv = 256 + (h0 + h) * 32 + acc_row32(r, kg);                       // v's normalisation, applied once: + shv[e] * sum_px P[px][d]
             const float shv = DS_LD(float, p.t1 + nv, DS_BX_T1) - gam * DS_LD(float, p.t2 + nv, DS_BX_T2);
-            DS_ST(float, out + 64 + n * 32 + e, DS_BX_AUX0, fmaf(ga, ctx[h][r], shv * lsum));
-        }
+            return fmaf(ga, ctx[h][r], shv * lsum);
+        });
     }
 }
 
 }  // namespace
-
-static int attn_ctx2_launch(const ds_attn_fused_params* p, hipStream_t st) {
-    if (p->C == 96) {
-        auto kern = attn_ctx2_kernel<6, 4, 4, 1>;
-        DS_SET_MAX_LDS(kern, C2<6>::LDS, "attn_ctx2");
-        hipLaunchKernelGGL(kern, dim3((p->nseg + 3) / 4, p->B), dim3(256), C2<6>::LDS, st, *p);
-    } else if (p->C == 192) {
-        auto kern = attn_ctx2_kernel<12, 8, 4, 1>;
-        DS_SET_MAX_LDS(kern, C2<12>::LDS, "attn_ctx2");
-        hipLaunchKernelGGL(kern, dim3((p->nseg + 7) / 8, p->B), dim3(512), C2<12>::LDS, st, *p);
-    } else {
-        auto kern = attn_ctx2_kernel<24, 8, 2, 2>;             // two heads per block: half of the k / v weights (100 KB)
-        DS_SET_MAX_LDS(kern, C2<24>::LDS / 2, "attn_ctx2");
-        hipLaunchKernelGGL(kern, dim3((p->nseg + 7) / 8, p->B, 2), dim3(512), C2<24>::LDS / 2, st, *p);
-    }
-    DS_CHECK_LAUNCH("attn_ctx2");
-    return DS_OK;
-}
-
-// blocks per sample: every CU busy with few, long-lived blocks (a block pays 53 / 104 KB of operand staging)
-static int attn_out2_blocks(int N, int B, int C) {
-    const int ntiles = (N + 31) / 32;
-    const int nw = C == 96 ? 4 : 8, per_cu = C == 96 ? 3 : 1;
-    int nb = (256 * per_cu + B - 1) / B;                      // blocks per sample that fill the chip once
-    const int max_nb = (ntiles + nw - 1) / nw;                // at least one tile per wave
-    if (nb > max_nb) nb = max_nb;
-    if (nb < 1) nb = 1;
-    const int per = (ntiles + nb - 1) / nb;
-    return (ntiles + per - 1) / per;
-}
-
-static int attn_out2_launch(const ds_attn_fused_params* p, hipStream_t st) {
-    void* const mfold = p->mfold;
-    const int C = p->C, nb = attn_out2_blocks(p->N, fused_batch(p), C);
-    const int ntiles = (p->N + 31) / 32, per = (ntiles + nb - 1) / nb;
-    hipLaunchKernelGGL(attn_fold_out_kernel, dim3(C / 32, p->B), dim3(256), 0, st, p->ctx, reinterpret_cast<const bf16*>(p->wout_perm),
-                       reinterpret_cast<bf16*>(mfold), C);
-    DS_CHECK_LAUNCH("attn_fold_out");
-    if (C == 96) {
-        auto kern = attn_out2_kernel<6, 4>;
-        DS_SET_MAX_LDS(kern, O2<6>::LDS, "attn_out2");
-        hipLaunchKernelGGL(kern, dim3(nb, p->B), dim3(256), O2<6>::LDS, st, *p, reinterpret_cast<const bf16*>(mfold), per);
-    } else {
-        auto kern = attn_out2_kernel<12, 8>;
-        DS_SET_MAX_LDS(kern, O2<12>::LDS, "attn_out2");
-        hipLaunchKernelGGL(kern, dim3(nb, p->B), dim3(512), O2<12>::LDS, st, *p, reinterpret_cast<const bf16*>(mfold), per);
-    }
-    DS_CHECK_LAUNCH("attn_out2");
-    return DS_OK;
-}

@@ -21,8 +21,8 @@
 // The three big kernels are put together from ONE copy of each part (a fix to a part reaches every kernel that runs it):
 //   XStream::chunk           the chunk step — fence, stage, keep the raw pieces (qz, MODE 2), unconditional refill, fence, operand reads  (pass1, qz)
 //   XStream::for_tiles       the tile driver: the ring slot of a tile's chunk 0 as a compile-time constant                               (pass1, qz)
-//   RowStage                 rows of 16-byte pieces -> LDS, a load half and a store half; load_w_rows (row map), load_mb_rows (c0)      (pass1, z, qz)
-//   read_gn, fill_shq        (a, a . mean) of the input GroupNorm; the additive q table                                                 (pass1, qz)
+//   RowStage (common.hpp)    rows of 16-byte pieces -> LDS, a load half and a store half; load_w_rows (row map), load_mb_rows (c0)      (pass1, z, qz)
+//   read_gn, fill_shq (common.hpp)   (a, a . mean) of the input GroupNorm; the additive q table                                          (pass1, qz)
 //   fill_out_rows            the bias row and, MODE 2, the scale and shift rows of the output GroupNorm                                 (z, qz)
 //   ZOut::block              Z of 32 channels of one tile -> statistics (MODE 1), or transpose, scale / shift / residual, stores         (z, qz)
 //   xcd_block_decode         XCD-aware block order                                                                                      (pass1, z)
@@ -37,8 +37,6 @@ int ds_linattn_launch_combine(const ds_attn_params* p, hipStream_t st);  // lina
 
 namespace {
 
-constexpr float LOG2E = 1.44269504088896340736f;
-constexpr int PARTF = 32 + 32 + 1024;
 constexpr int XS = 144;                  // row of a wave's staging tile: 64 B hi | 64 B lo | 16 B pad (nine 16-byte slots: conflict-free ds_read_b128)
 constexpr int XTILE = 32 * XS;           // 4608 B per wave (also the 32 px x 32 ch fp32 transpose tile of pass 2: 128 + 16 B rows)
 constexpr int NW = 8, NT = NW * 64;
@@ -167,28 +165,10 @@ struct XStream {
     }
 };
 
-// ---- prologue pieces.  Each staging helper has a load half and a store half: a prologue requests EVERY global load of its tables before
-// its first LDS write (one round trip instead of one per table).
-// Two planes (hi, lo) of ROWS rows of PCS 16-byte pieces, global memory -> LDS rows of `pitch` bytes; src(plane, row) = the row in global memory
-template <int ROWS, int PCS>
-struct RowStage {
-    static constexpr int IT = 2 * ROWS * PCS / NT;
-    static_assert(IT * NT == 2 * ROWS * PCS, "whole staging iterations");
-    u32x4 v[IT];
-    template <int BX, class Src> __device__ __forceinline__ void load(int tid, Src src) {
-#pragma unroll
-        for (int k = 0; k < IT; ++k) {
-            const int i = tid + k * NT, plane = i / (ROWS * PCS), r = (i / PCS) % ROWS, col = i % PCS;
-            v[k] = DS_LD(u32x4, reinterpret_cast<const u32x4*>(src(plane, r) + col * 16), BX);
-        }
-    }
-    __device__ __forceinline__ void store(int tid, char* hi, char* lo, int pitch) const {
-#pragma unroll
-        for (int k = 0; k < IT; ++k) {
-            const int i = tid + k * NT, plane = i / (ROWS * PCS), r = (i / PCS) % ROWS, col = i % PCS;
-            *reinterpret_cast<u32x4*>((plane ? lo : hi) + r * pitch + col * 16) = v[k];
-        }
-    }
+// ---- prologue pieces.  Each staging helper has a load half and a store half (RowStage, common.hpp): a prologue requests EVERY global load
+// of its tables before its first LDS write.  Here: two planes (hi, lo), the block's NT threads
+template <int ROWS, int PCS> struct RowStage : ::RowStage<2, ROWS, PCS, NT> {
+    static_assert(::RowStage<2, ROWS, PCS, NT>::WHOLE, "whole staging iterations");
 };
 // weight rows of the packed [q | k | v] planes (row map: LDS row -> row of the 384); rows c0 .. c0 + ROWS - 1 of sample b's folded to_out matrix M_b
 template <int C, int ROWS, class RowMap>
@@ -200,22 +180,6 @@ template <int ROWS>
 __device__ __forceinline__ void load_mb_rows(RowStage<ROWS, 16>& s, const ds_attn_x3_params& p, int tid, int b, int C, int c0) {
     const char* const mb = reinterpret_cast<const char*>(p.mfold) + (size_t)b * 2 * C * 256;
     s.template load<DS_BX_RES>(tid, [&](int plane, int r) { return mb + ((size_t)plane * C + c0 + r) * 256; });
-}
-
-// (a, a . mean) of the input GroupNorm of sample b: from the raw partials or from finished pairs
-__device__ __forceinline__ void read_gn(const ds_attn_x3_params& p, int b, float& ga, float& gam) {
-    if (p.gn_part) gn_from_partials(p.gn_part, p.gn_parts, p.gn_count, p.gn_eps, b, ga, gam);
-    else { ga = DS_LD(float, p.gn_ab + 2 * b, DS_BX_GNAB); gam = DS_LD(float, p.gn_ab + 2 * b + 1, DS_BX_GNAB); }
-}
-
-// additive part of q (fold + label) in the log2 domain for heads h0 .. h0 + nh - 1, in accumulator order: entry (h, fh, r) = row d =
-// acc_row32(r, fh) of head h0 + h
-__device__ __forceinline__ void fill_shq(const ds_attn_x3_params& p, float* shq, int h0, int nh, int b, float gam, int tid) {
-    for (int i = tid; i < nh * 32; i += NT) {
-        const int d = (h0 + (i >> 5)) * 32 + acc_row32(i & 15, (i >> 4) & 1);
-        shq[i] = LOG2E * (DS_LD(float, p.t1 + d, DS_BX_T1) - gam * DS_LD(float, p.t2 + d, DS_BX_T2) +
-                          (p.label_q ? DS_LD(float, p.label_q + (size_t)b * p.lq_stride + d, DS_BX_AUX3) : 0.f));
-    }
 }
 
 // XCD-aware block order: hardware block L runs on XCD L % 8.  The gridDim.z groups of one (blockIdx.x, sample) read the same stream (x in
@@ -273,7 +237,7 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_pass1_kernel(const ds_attn_x3_p
     float ga, gam;
     read_gn(p, b, ga, gam);
     const float ga2 = ga * LOG2E;
-    if constexpr (Q) fill_shq(p, reinterpret_cast<float*>(sm + G::OFF_SHQ), h0, HB, b, gam, tid);
+    if constexpr (Q) fill_shq<NT>(p, reinterpret_cast<float*>(sm + G::OFF_SHQ), h0, HB, b, gam, tid);
     float shk2[HB], m[HB], ls[HB];
     f32x16 ctx[HB];
     if constexpr (KV) {
@@ -690,7 +654,7 @@ __global__ __launch_bounds__(NT, 1) void attn_x3_qz_kernel(const ds_attn_x3_para
         m.store(tid, sm + G::OFF_MH, sm + G::OFF_ML, M_RS);
         float ga, gam;
         read_gn(p, b, ga, gam);
-        fill_shq(p, shq, 0, 4, b, gam, tid);
+        fill_shq<NT>(p, shq, 0, 4, b, gam, tid);
         if (tid == 0) red[15] = ga * LOG2E;
         fill_out_rows<MODE>(p, sbias, sgam, 0, C, gridDim.x, C, b, tid);
     }

@@ -242,7 +242,7 @@ __device__ __forceinline__ void ds_split8(const float* v, u32x4& hi, u32x4& lo) 
     lo = u32x4{l[0], l[1], l[2], l[3]};
 }
 
-// ---- shared by the attention kernels (attn_fused.hip, attn_out2.hpp, attn_x3.hip) ------------------------------------------------------
+// ---- shared by the attention kernels (more at the end of this file) ---------------------------------------------------------------------
 __device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32 (flushes denormal results)
 __device__ __forceinline__ int acc_row32(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }   // row of register r of lane half fh in a 32x32 accumulator
 
@@ -420,4 +420,63 @@ __device__ __forceinline__ void gn_from_partials(const float* part, int parts, d
     const double rstd = 1.0 / sqrt(var + (double)eps);
     a = (float)rstd;
     am = (float)(rstd * mean);
+}
+
+// ---- shared by the attention kernels, both tiers (attn_fused.hip + attn_out2.hpp, vq_attn.hip, attn_x3.hip; PARTF also linattn.hip) -----------
+constexpr float LOG2E = 1.44269504088896340736f;
+constexpr int PARTF = 32 + 32 + 1024;    // floats of one (max[32], sum[32], ctx[32][32]) partial of the context pass
+
+// v[0..7] -> one packed bf16 MFMA operand (pairs: one v_cvt_pk_bf16_f32 per two values, see ds_split2)
+__device__ __forceinline__ bf16x8 pack8(const float* v) {
+    unsigned h[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) h[j] = __builtin_bit_cast(unsigned, __builtin_convertvector((ds_f32x2{v[2 * j], v[2 * j + 1]}), ds_bf16x2));
+    return __builtin_bit_cast(bf16x8, (u32x4{h[0], h[1], h[2], h[3]}));
+}
+
+// PLANES planes of ROWS rows of PCS 16-byte pieces, global memory -> LDS rows of `pitch` bytes, by NT threads; src(plane, row) = the row in
+// global memory.  A load half and a store half: a prologue requests EVERY global load of its tables before its first LDS write (one round
+// trip instead of one per table: as a `for (i = tid; ...; i += NT)` loop every iteration was load -> s_waitcnt vmcnt(0) -> ds_write).
+// Where the pieces are no multiple of NT the last iteration is ragged: clamped address on the load side, a guard on the store side
+// (a caller whose geometry must not be ragged asserts WHOLE).
+template <int PLANES, int ROWS, int PCS, int NT>
+struct RowStage {
+    static constexpr int TOTAL = PLANES * ROWS * PCS, IT = (TOTAL + NT - 1) / NT;
+    static constexpr bool WHOLE = IT * NT == TOTAL;
+    u32x4 v[IT];
+    template <int BX, class Src> __device__ __forceinline__ void load(int tid, Src src) {
+#pragma unroll
+        for (int k = 0; k < IT; ++k) {
+            const int i0 = tid + k * NT, i = WHOLE || i0 < TOTAL ? i0 : 0;
+            const int plane = PLANES > 1 ? i / (ROWS * PCS) : 0, r = PLANES > 1 ? (i / PCS) % ROWS : i / PCS, col = i % PCS;
+            v[k] = DS_LD(u32x4, reinterpret_cast<const u32x4*>(src(plane, r) + col * 16), BX);
+        }
+    }
+    __device__ __forceinline__ void store(int tid, char* hi, char* lo, int pitch) const {
+#pragma unroll
+        for (int k = 0; k < IT; ++k) {
+            const int i = tid + k * NT, plane = PLANES > 1 ? i / (ROWS * PCS) : 0, r = PLANES > 1 ? (i / PCS) % ROWS : i / PCS, col = i % PCS;
+            if (WHOLE || i < TOTAL) *reinterpret_cast<u32x4*>((plane ? lo : hi) + r * pitch + col * 16) = v[k];
+        }
+    }
+    __device__ __forceinline__ void store(int tid, char* dst, int pitch) const { store(tid, dst, dst, pitch); }
+};
+
+// (a, a . mean) of the input GroupNorm of sample b: from the raw partials or from finished pairs (P: any of the attention params structs)
+template <class P>
+__device__ __forceinline__ void read_gn(const P& p, int b, float& ga, float& gam) {
+    if (p.gn_part) gn_from_partials(p.gn_part, p.gn_parts, p.gn_count, p.gn_eps, b, ga, gam);
+    else { ga = DS_LD(float, p.gn_ab + 2 * b, DS_BX_GNAB); gam = DS_LD(float, p.gn_ab + 2 * b + 1, DS_BX_GNAB); }
+}
+
+// additive part of q (fold shift + label) of row d of [q | k | v], in the log2 domain; fill_shq: the table of heads h0 .. h0 + nh - 1 in
+// accumulator order, entry (h, fh, r) = row d = acc_row32(r, fh) of head h0 + h, by NT threads
+template <class P>
+__device__ __forceinline__ float shq_entry(const P& p, int d, int b, float gam) {
+    return LOG2E * (DS_LD(float, p.t1 + d, DS_BX_T1) - gam * DS_LD(float, p.t2 + d, DS_BX_T2) +
+                    (p.label_q ? DS_LD(float, p.label_q + (size_t)b * p.lq_stride + d, DS_BX_AUX3) : 0.f));
+}
+template <int NT, class P>
+__device__ __forceinline__ void fill_shq(const P& p, float* shq, int h0, int nh, int b, float gam, int tid) {
+    for (int i = tid; i < nh * 32; i += NT) shq[i] = shq_entry(p, (h0 + (i >> 5)) * 32 + acc_row32(i & 15, (i >> 4) & 1), b, gam);
 }

@@ -8,7 +8,6 @@
 
 namespace {
 
-constexpr int PART = 32 + 32 + 1024;
 constexpr int TP = 64;  // pixels per LDS tile in pass 1
 
 template <typename T>
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(256) void attn_ctx_partial(const ds_attn_params p) 
         lsum[tid] = a;
     }
     __syncthreads();
-    float* out = p.part + (((size_t)b * p.heads + h) * p.nseg + seg) * PART;
+    float* out = p.part + (((size_t)b * p.heads + h) * p.nseg + seg) * PARTF;
     if (tid < 32) {
         out[tid] = kmax[tid];
         out[32 + tid] = lsum[tid];
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(256) void attn_ctx_partial(const ds_attn_params p) 
 __global__ __launch_bounds__(256) void attn_ctx_combine(const ds_attn_params p) {
     __shared__ float sf[32][9], sl[32][9];                      // [segment of the batch][row of this block]
     const int h = blockIdx.x, b = blockIdx.y, dl = threadIdx.x >> 5, d = blockIdx.z * 8 + dl, e = threadIdx.x & 31;
-    const float* part = p.part + ((size_t)b * p.heads + h) * p.nseg * PART;
+    const float* part = p.part + ((size_t)b * p.heads + h) * p.nseg * PARTF;
     const bool tok = p.label_k != nullptr;
     float lk = 0.f, lv = 0.f;
     if (tok) {
@@ -145,7 +144,7 @@ __global__ __launch_bounds__(256) void attn_ctx_combine(const ds_attn_params p) 
     }
     // row maximum: lane e looks at segments e, e + 32, ..; the 32 lanes of a row are one half of a wave
     float M = tok ? lk : -INFINITY;
-    for (int s = e; s < p.nseg; s += 32) M = fmaxf(M, part[(size_t)s * PART + d]);
+    for (int s = e; s < p.nseg; s += 32) M = fmaxf(M, part[(size_t)s * PARTF + d]);
 #pragma unroll
     for (int sh = 16; sh >= 1; sh >>= 1) M = fmaxf(M, __shfl_xor(M, sh, 64));
     float Lr = tok ? expf(lk - M) : 0.f;
@@ -154,9 +153,9 @@ __global__ __launch_bounds__(256) void attn_ctx_combine(const ds_attn_params p) 
         const int nb = min(32, p.nseg - s0);
         float cv[32];
 #pragma unroll
-        for (int j = 0; j < 32; ++j) cv[j] = part[(size_t)min(s0 + j, p.nseg - 1) * PART + 64 + d * 32 + e];
+        for (int j = 0; j < 32; ++j) cv[j] = part[(size_t)min(s0 + j, p.nseg - 1) * PARTF + 64 + d * 32 + e];
         {
-            const float* ps = part + (size_t)min(s0 + e, p.nseg - 1) * PART;
+            const float* ps = part + (size_t)min(s0 + e, p.nseg - 1) * PARTF;
             sf[e][dl] = e < nb ? expf(ps[d] - M) : 0.f;
             sl[e][dl] = ps[32 + d];
         }
@@ -309,7 +308,7 @@ int ds_linattn_launch_combine(const ds_attn_params* p, hipStream_t st) {   // sh
     return DS_OK;
 }
 
-extern "C" size_t ds_linattn_part_floats(int B, int heads, int nseg) { return (size_t)B * heads * nseg * PART; }
+extern "C" size_t ds_linattn_part_floats(int B, int heads, int nseg) { return (size_t)B * heads * nseg * PARTF; }
 
 extern "C" int ds_linattn_context(const ds_attn_params* p, void* stream) {
     int rc = check(p);

@@ -9,58 +9,26 @@
 //   pass 1 (vq_attn_ctx):   block = 4 waves, each with its own 32-pixel tile of a 128-pixel group staged in LDS (coalesced 16-byte loads two
 //                           groups ahead, rows padded to an odd number of 16-byte slots); k, v tiles on v_mfma_f32_32x32x16_bf16 with the weight
 //                           fragments in registers, online softmax over the pixels in the log2 domain, ctx^T += V^T P with the accumulators as
-//                           operands (attn_fused.hip, first generation); one (max, sum, ctx) partial per wave, merged by attn_ctx_combine;
+//                           operands (the tile step of attn_bf16_parts.hpp; no input norm, v raw); one (max, sum, ctx) partial per wave,
+//                           merged by attn_ctx_combine;
 //   fold    (vq_attn_fold): W_b per sample in fp32, stored as bf16 [roundup(C, 32)][C];
-//   pass 2 (vq_attn_apply): W_b in LDS; wave = 32-pixel tile, its x fragments in registers, y^T = W_b x^T per 32-channel block, + bias, written over
+//   pass 2 (vq_attn_apply): W_b in LDS (RowStage: every row requested before the first LDS write); wave = 32-pixel tile, its x fragments in registers, y^T = W_b x^T per 32-channel block, + bias, written over
 //                           the wave's own x rows in LDS and stored as whole contiguous rows; the per-channel (sum, sum of squares) of the stored
 //                           values go to the statistics slots the following Normalize finishes (ds_gn_stats_finish) — no statistics pass.
 #include "common.hpp"
+#include "attn_bf16_parts.hpp"
 
 int ds_linattn_launch_combine(const ds_attn_params* p, hipStream_t st);   // linattn.hip
 
 namespace {
 
-constexpr int PARTF = 32 + 32 + 1024;
-constexpr float LOG2E = 1.44269504088896340736f;
 constexpr int GP = 128;                                          // pixels per group: one 32-pixel tile per wave
-
-__device__ __forceinline__ int acc_row(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }
-__device__ __forceinline__ bf16x8 pack8(const float* v) {
-    unsigned h[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) h[j] = __builtin_bit_cast(unsigned, __builtin_convertvector((ds_f32x2{v[2 * j], v[2 * j + 1]}), ds_bf16x2));
-    return __builtin_bit_cast(bf16x8, (u32x4{h[0], h[1], h[2], h[3]}));
-}
-
-// a group's x rows: 256 threads x NKS 16-byte pieces, unconditional loads (clamped address + select), see attn_fused.hip
-template <int NKS>
-struct VX {
-    static constexpr int C = NKS * 16, RS = 2 * C + 16, BYTES = GP * RS, PPR = 2 * NKS;     // row stride in bytes, pieces per row
-    u32x4 r[NKS];
-    __device__ __forceinline__ void load(const bf16* x, int N, int group) {
-        const long base = (long)group * GP * C, lim = (long)N * C;
-#pragma unroll
-        for (int it = 0; it < NKS; ++it) {
-            const long e = base + (long)(threadIdx.x + it * 256) * 8;
-            const bool ok = e < lim;
-            const u32x4 v = DS_LD(u32x4, x + (ok ? e : 0), DS_BX_SRC0);
-            r[it] = ok ? v : u32x4{0u, 0u, 0u, 0u};
-        }
-    }
-    __device__ __forceinline__ void store(char* buf) const {
-#pragma unroll
-        for (int it = 0; it < NKS; ++it) {
-            const int piece = threadIdx.x + it * 256;
-            const int row = piece / PPR, col = piece - row * PPR;
-            *reinterpret_cast<u32x4*>(buf + row * RS + col * 16) = r[it];
-        }
-    }
-};
+template <int NKS> using VXS = XStage<NKS, GP>;                  // (256 threads x NKS 16-byte pieces per group)
 
 // ------------------------------------------------------------------------------------------------ pass 1
 template <int NKS>
 __global__ __launch_bounds__(256, NKS > 5 ? 1 : 2) void vq_attn_ctx_kernel(const ds_vq_attn_params p) {
-    using XS = VX<NKS>;
+    using XS = VXS<NKS>;
     constexpr int C = XS::C, RS = XS::RS;
     extern __shared__ __attribute__((aligned(16))) char sm[];    // x[2][XS::BYTES]
     const int blk = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -87,8 +55,7 @@ __global__ __launch_bounds__(256, NKS > 5 ? 1 : 2) void vq_attn_ctx_kernel(const
                 Wv[ks] = DS_LD(bf16x8, wv + ks * 16, DS_BX_W);
             }
         }
-        xs.store(sm);
-        xs.load(x, p.N, g0 + 1 < g1 ? g0 + 1 : g0);
+        xs.next(sm, x, p.N, g0 + 1 < g1 ? g0 + 1 : g0);
         __syncthreads();
         for (int g = g0; g < g1; ++g) {
             const int cur = (g - g0) & 1;
@@ -111,48 +78,19 @@ __global__ __launch_bounds__(256, NKS > 5 ? 1 : 2) void vq_attn_ctx_kernel(const
                     av = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[ks], Wv[ks], av, 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                float mr = -INFINITY;
-                if (px0 + 32 <= p.N) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) mr = fmaxf(mr, ak[r]);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        if (px0 + acc_row(r, fh) >= p.N) ak[r] = -INFINITY;                        // exp2(-inf) = 0
-                        mr = fmaxf(mr, ak[r]);
-                    }
-                }
-                mr = fmaxf(mr, __shfl_xor(mr, 32, 64));
-                const float mn = fmaxf(m, mr * LOG2E);           // finite: the tile holds >= 1 real pixel
-                const float sc = __builtin_amdgcn_exp2f(m - mn); // m = -inf on the first tile -> 0
-                m = mn;
-                float P[16], V[16], psum = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    P[r] = __builtin_amdgcn_exp2f(fmaf(LOG2E, ak[r], -mn));
-                    V[r] = av[r];
-                    psum += P[r];
-                }
-                ls = ls * sc + psum;
-                if (__any(sc != 1.0f)) {                         // the running maximum rarely moves after the first tiles
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) ctx[r] *= sc;
-                }
-                ctx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack8(V), pack8(P), ctx, 0, 0, 0);            // ctx^T[e][d]
-                ctx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack8(V + 8), pack8(P + 8), ctx, 0, 0, 0);
+                // no input norm: the softmax argument is LOG2E * k, v enters raw
+                float mr;
+                if (px0 + 32 <= p.N) mr = tile_row_max<false, false>(ak, px0, fh, p.N);
+                else mr = tile_row_max<true, false>(ak, px0, fh, p.N);
+                softmax_tile_step<false>(ak, av, mr, LOG2E, [](float mx) { return mx * LOG2E; }, [](float mn) { return -mn; }, [](float v) { return v; },
+                                         m, ls, ctx);
             }
-            xs.store(sm + (cur ^ 1) * XS::BYTES);                // group g+1 (loaded a full iteration ago)
-            xs.load(x, p.N, g + 2 < g1 ? g + 2 : g);             // group g+2 stays in flight across the next iteration
+            xs.next(sm + (cur ^ 1) * XS::BYTES, x, p.N, g + 2 < g1 ? g + 2 : g);
             __syncthreads();
         }
         ls += __shfl_xor(ls, 32, 64);
     }
-    if (fh == 0) {
-        DS_ST(float, out + frow, DS_BX_AUX0, m * (1.0f / LOG2E));        // natural-log domain of the combine kernel; lane = d
-        DS_ST(float, out + 32 + frow, DS_BX_AUX0, ls);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) DS_ST(float, out + 64 + frow * 32 + acc_row(r, fh), DS_BX_AUX0, ctx[r]);   // ctx[d][e]: d on the lane, e in registers
+    write_partial(out, frow, fh, m, ls, [&](int r) { return ctx[r]; });
 }
 
 // ------------------------------------------------------------------------------------------------ fold
@@ -219,7 +157,7 @@ __global__ __launch_bounds__(256) void vq_attn_fold_kernel(const ds_vq_attn_para
 // ------------------------------------------------------------------------------------------------ pass 2
 template <int NKS>
 __global__ __launch_bounds__(256, NKS > 5 ? 1 : 2) void vq_attn_apply_kernel(const ds_vq_attn_params p) {
-    using XS = VX<NKS>;
+    using XS = VXS<NKS>;
     constexpr int C = XS::C, RS = XS::RS, NCB = (C + 31) / 32, CP = NCB * 32, NP8 = C / 8, PPI = 64 / NP8, SIT = (32 + PPI - 1) / PPI;
     extern __shared__ __attribute__((aligned(16))) char sm[];    // x[2][XS::BYTES] | W_b[CP][RS] | bias[CP] fp32
     char* const wl = sm + 2 * XS::BYTES;
@@ -241,15 +179,13 @@ __global__ __launch_bounds__(256, NKS > 5 ? 1 : 2) void vq_attn_apply_kernel(con
         XS xs;
         xs.load(x, p.N, g0);
         {
-            const bf16* wf = reinterpret_cast<const bf16*>(p.wfold) + (size_t)b * CP * C;
-            for (int i = tid; i < CP * NP8; i += 256) {
-                const int row = i / NP8, col = i - row * NP8;
-                *reinterpret_cast<u32x4*>(wl + row * RS + col * 16) = DS_LD(u32x4, wf + (size_t)row * C + col * 8, DS_BX_RES);
-            }
+            const char* const wf = reinterpret_cast<const char*>(p.wfold) + (size_t)b * CP * C * 2;
+            RowStage<1, CP, NP8, 256> w;
+            w.template load<DS_BX_RES>(tid, [&](int, int r) { return wf + (size_t)r * C * 2; });
+            w.store(tid, wl, RS);
             for (int i = tid; i < CP; i += 256) bl[i] = i < C ? DS_LD(float, p.bias + i, DS_BX_BIAS) : 0.f;
         }
-        xs.store(sm);
-        xs.load(x, p.N, g0 + 1 < g1 ? g0 + 1 : g0);
+        xs.next(sm, x, p.N, g0 + 1 < g1 ? g0 + 1 : g0);
         __syncthreads();
         for (int g = g0; g < g1; ++g) {
             const int cur = (g - g0) & 1;
@@ -301,8 +237,7 @@ __global__ __launch_bounds__(256, NKS > 5 ? 1 : 2) void vq_attn_apply_kernel(con
                     }
                 }
             }
-            xs.store(sm + (cur ^ 1) * XS::BYTES);
-            xs.load(x, p.N, g + 2 < g1 ? g + 2 : g);
+            xs.next(sm + (cur ^ 1) * XS::BYTES, x, p.N, g + 2 < g1 ? g + 2 : g);
             __syncthreads();
         }
     }
@@ -358,32 +293,31 @@ void vq_publish_bounds(const ds_vq_attn_params* p, int kernel, hipStream_t st) {
 }
 #endif
 
-template <int NKS>
-int launch_ctx(const ds_vq_attn_params* p, hipStream_t st) {
-    auto kern = vq_attn_ctx_kernel<NKS>;
-    constexpr int lds = 2 * VX<NKS>::BYTES;
-    DS_SET_MAX_LDS(kern, lds, "vq_attn_ctx");
+// The one launch of this file (ctx and apply run the same grid): LDS limit, the operand extents of the bounds build, the launch, its check
+template <auto KERN>
+int launch(const ds_vq_attn_params* p, int lds, const char* name, int bx_kernel, hipStream_t st) {
+    DS_SET_MAX_LDS(KERN, lds, name);
 #if DS_BOUNDS
-    vq_publish_bounds(p, DS_K_VQ_ATTN_CTX, st);
+    vq_publish_bounds(p, bx_kernel, st);
+#else
+    (void)bx_kernel;
 #endif
-    hipLaunchKernelGGL(kern, dim3(p->nseg / 4, p->B), dim3(256), lds, st, *p);
-    DS_CHECK_LAUNCH("vq_attn_ctx");
+    hipLaunchKernelGGL(KERN, dim3(p->nseg / 4, p->B), dim3(256), lds, st, *p);
+    DS_CHECK_LAUNCH(name);
     return DS_OK;
 }
 
 template <int NKS>
+int launch_ctx(const ds_vq_attn_params* p, hipStream_t st) {
+    return launch<vq_attn_ctx_kernel<NKS>>(p, 2 * VXS<NKS>::BYTES, "vq_attn_ctx", DS_K_VQ_ATTN_CTX, st);
+}
+
+template <int NKS>
 int launch_apply(const ds_vq_attn_params* p, hipStream_t st) {
-    auto kern = vq_attn_apply_kernel<NKS>;
     constexpr int C = NKS * 16, CP = (C + 31) / 32 * 32;
-    constexpr int lds = 2 * VX<NKS>::BYTES + CP * VX<NKS>::RS + CP * 4;
+    constexpr int lds = 2 * VXS<NKS>::BYTES + CP * VXS<NKS>::RS + CP * 4;
     static_assert(lds <= 160 * 1024, "LDS");
-    DS_SET_MAX_LDS(kern, lds, "vq_attn_apply");
-#if DS_BOUNDS
-    vq_publish_bounds(p, DS_K_VQ_ATTN_APPLY, st);
-#endif
-    hipLaunchKernelGGL(kern, dim3(p->nseg / 4, p->B), dim3(256), lds, st, *p);
-    DS_CHECK_LAUNCH("vq_attn_apply");
-    return DS_OK;
+    return launch<vq_attn_apply_kernel<NKS>>(p, lds, "vq_attn_apply", DS_K_VQ_ATTN_APPLY, st);
 }
 
 }  // namespace
