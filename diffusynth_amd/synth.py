@@ -32,7 +32,7 @@ def synth_tensor(key, shape):
         arr = 0.3 * n
     elif leaf == "num_batches_tracked":
         return torch.zeros(shape, dtype=torch.int64)
-    elif leaf == "bias":
+    elif leaf == "bias" or leaf.startswith("bias_"):                   # bias_: nn.LSTM's bias_ih_l* / bias_hh_l* (gains of 1 saturate its gates)
         arr = 0.1 * n
     elif len(shape) == 1:                                              # norm gains
         arr = 1.0 + 0.2 * n

@@ -667,6 +667,21 @@ int ds_peak_normalize(const float* x, const int32_t* tab, int n_signals, int max
 int ds_mix_notes(const float* notes, long long total_samples, const int32_t* ev, int n_events, const int32_t* blk_ptr, const int32_t* blk_ev,
                  int n_blk_ev, float* track, int track_len, void* stream);
 
+/* ---------------------------------------------------------------- timbre encoder (timbre_encoder_pretrain.py:39,71,81-84), fp32
+ * One nn.LSTM layer over a whole sequence, h0 = c0 = 0:  c' = sigmoid(f) c + sigmoid(i) tanh(g),  h' = sigmoid(o) tanh(c')  with
+ * [i f g o][b][t] = pre[b][t] + h[b][t-1] w_hh^T.  pre [B][T][4H] = x W_ih^T + b_ih + b_hh comes from the caller (one ds_linear over all B T rows;
+ * element (b, t, j) at pre[b * pre_batch_stride + t * pre_step_stride + j]), w_hh [4H][H] is nn.LSTM's weight_hh_l*.  Writes the hidden
+ * sequence hs [B][T][H] (NULL: not wanted) and its last step h_last [B][H].  ws: ds_lstm_ws_floats(B, H) floats (c and two buffers of h), need
+ * not be initialised.  H % 16 == 0, any B, T >= 1.  The call enqueues T launches on `stream` and returns: stream order is the only dependence
+ * between steps, so no launch holds more than one step and no block waits for another.  The summation order over k of an output (b, unit) does
+ * not depend on B: a sample's result is the same bits whatever shares its batch. */
+size_t ds_lstm_ws_floats(int B, int H);
+int ds_lstm_layer(const float* pre, long long pre_batch_stride, long long pre_step_stride, const float* w_hh, int B, int T, int H, float* hs,
+                  float* h_last, float* ws, void* stream);
+/* The four classifier heads on one stacked [B][y_stride] matrix of logits, in place: log-softmax over columns [0, n0), [n0, n0 + n1) and
+ * [n0 + n1, n0 + n1 + n2), each by itself, and sigmoid over the n3 columns that follow. */
+int ds_timbre_heads(float* y, int y_stride, int B, int n0, int n1, int n2, int n3, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
