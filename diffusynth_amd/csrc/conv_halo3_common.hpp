@@ -102,8 +102,10 @@ __device__ __forceinline__ void gelu_poly8(float (&w)[8]) {
 // to [2^-12, 8)): T at the midpoint of that bf16 bucket, no interpolation.  5 VALU + one ds_read_b32 per value (clamp, shift, address,
 // relu, subtract) instead of the polynomial's 16 or the 10 of an interpolated table — these kernels are bound by the epilogue's vector
 // instruction count beside the other block's MFMA loop (8.4 cycles per instruction there, tools/ubench/coissue.hip).  Error against the
-// exact function: <= 6.6e-4 absolute (at x = -2), 1.7e-4 rms over N(0, 2.5) inputs = 5 % of the bf16 rounding of the result that
-// follows (3.2e-3 rms), mean 3e-7 (midpoints: unbiased); below 2^-12 the result is x/2 to within 1.2e-4.  oracle check: tests/test_hip_kernels.py.
+// exact function: <= 6.63e-4 absolute (at x = -2), 1.7e-4 rms over N(0, 2.5) inputs = 5 % of the bf16 rounding of the result that
+// follows (3.2e-3 rms), mean 3e-7 (midpoints: unbiased); below 2^-12 the result is x/2 to within 1.23e-4.  oracle check:
+// tests/test_exact_ref_cpu.py (test_gelu_table_and_polynomial_keep_their_documented_bounds: the table rebuilt on the CPU) and
+// tests/test_hip_exact.py (test_gelu_per_implementation: every bf16 input through the kernels).
 __device__ __forceinline__ void gelu_tab8(float (&w)[8], const char* lut) {
     const char* const tb = lut - GELU_TAB_BASE * 4;             // (table entry of pattern t at lut + (t - BASE) * 4)
     float h[8];
