@@ -7,3 +7,5 @@ Importing the package is cheap and works without a GPU; anything that computes l
 ``libdiffusynth_hip.so`` and raises if it is missing (there is no CPU fallback).
 """
 __version__ = "0.1.0"
+
+from .clap_text import ClapTextTower  # noqa: E402,F401

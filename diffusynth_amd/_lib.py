@@ -53,6 +53,7 @@ SR = _parse_defines(_HEADER_TEXT, "DS_SR_")     # ds_step_rows table layout (fie
 DW_FAMILY = {v: k[6:].lower() for k, v in _parse_defines(_HEADER_TEXT, "DS_DW_").items()}     # ds_dwconv_launch_choice: family code -> name
 PV = _parse_defines(_HEADER_TEXT, "DS_PV_")     # arranger signal table (field indices and row width)
 MIX_BLOCK = _parse_defines(_HEADER_TEXT, "DS_MIX_")["DS_MIX_BLOCK"]
+TAIL = _parse_defines(_HEADER_TEXT, "DS_TAIL_")     # ds_text_tail: op codes
 ConvParams = _STRUCTS["ds_conv_params"]
 PackConvParams = _STRUCTS["ds_pack_conv_params"]
 DwconvParams = _STRUCTS["ds_dwconv_params"]
@@ -165,6 +166,9 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_lstm_ws_floats": (_SZ, [_I, _I]),
     "ds_lstm_layer": (C.c_int, [_P, C.c_longlong, C.c_longlong, _P, _I, _I, _I, _P, _P, _P, _P]),
     "ds_timbre_heads": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P]),
+    "ds_text_embed": (C.c_int, [_P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _F, _P, _P]),
+    "ds_text_attention": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "ds_text_tail": (C.c_int, [_P, _I, _I, _I, _F, _P, _P]),
     "ds_bounds_report": (C.c_int, [C.c_char_p, _I, _I]),
 }
 _UNCHECKED = {"ds_conv3x3_f32_n4_weight_floats", "ds_bounds_report", "ds_abi_version", "ds_conv_stats_parts", "ds_conv1x1_x3_stats_parts", "ds_conv_tile_bn", "ds_dwconv_stats_parts", "ds_attn_fused_stats_parts", "ds_attn_fused_generations", "ds_attn_fused_segments", "ds_attn_fused_segments_gen", "ds_attn_x3_stats_parts", "ds_attn_x3_segments", "ds_vq_attn_segments", "ds_conv3x3_c80_stats_slots", "ds_convt4x4_c80_stats_slots"}

@@ -382,7 +382,8 @@ class DiffSynth:
     SamplingBatcher (shared U-Net steps), decoded per width group, and arranged on the device; one device -> host copy of the music.
 
     The empty-prompt condition comes from text_encoder.get_text_features(**CLAP_tokenizer([""], ...)) when a text encoder is given (once per
-    get_music: it is a constant) or from the keyword-only `condition` (a (1, D) tensor); the text tower itself is not part of this package.
+    get_music: it is a constant) or from the keyword-only `condition` (a (1, D) tensor).  With text_encoder = a multi_modal_model over a
+    clap_text.ClapTextTower (or the tower itself) that call runs on the device end to end; only the tokenizer stays outside.
     """
 
     def __init__(self, instruments_configs, noise_prediction_model, VAE_quantizer, VAE_decoder, text_encoder, CLAP_tokenizer, device,

@@ -3,7 +3,7 @@ model/multimodal_model.py:14-47, which turns a CLAP text feature into the 512-d 
 (multimodal_model.py:114-116, app.py:59).  Same constructor arguments and state-dict names
 (``layers.N.{projection,fc,layer_norm}.{weight,bias}``); inference only (dropout is the identity in eval mode).
 Per layer: two ds_linear launches (the second applies GELU to its input) and one ds_add_layernorm.  The CLAP text
-tower itself needs remote weights and stays outside."""
+tower that produces the feature is clap_text.ClapTextTower."""
 import torch
 from torch import nn
 

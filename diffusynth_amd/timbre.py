@@ -10,11 +10,12 @@ The encoder reads the latent sample() leaves on the device: (B, 4, 128, W) viewe
     ds_linear + ds_timbre_heads   the four classifiers stacked into one matrix, their log-softmax / sigmoid in one launch
 
 The nn.LSTM is held as the parameter container only (it gives the reference's key names); its forward is never called.  The CLAP text tower
-needs remote weights and stays outside, as in text_head.py."""
+is clap_text.ClapTextTower: given as multi_modal_model's text_encoder it makes get_text_features run end to end on the device."""
 import torch
 from torch import nn
 
 from . import _lib as L
+from .clap_text import ClapTextTower
 from .text_head import ProjectionHead
 
 _HEADS = ("instrument", "instrument_family", "velocity", "qualities")
@@ -118,7 +119,9 @@ def get_timbre_encoder(model_Config, load_pretrain=False, model_name=None, devic
 
 class multi_modal_model(nn.Module):
     """Inference side of the contrastive model: sounds and texts in one multi_modal_emb_dim space - the space of the U-Net's ``condition``.
-    ``text_encoder`` (the CLAP tower) may be None: callers that hold the tower's 512-d feature use project_text_features()."""
+    ``text_encoder`` (the CLAP tower) may be None: callers that hold the tower's 512-d feature use project_text_features().  With a
+    clap_text.ClapTextTower, get_text_features(input_ids, attention_mask) runs from token ids to the condition on the device, and a reference
+    checkpoint's text_encoder.text_model.* / text_encoder.text_projection.* weights load into it."""
 
     def __init__(self, timbre_encoder, text_encoder, spectrogram_feature_dim, text_feature_dim, multi_modal_emb_dim, temperature, dropout,
                  num_projection_layers=1, freeze_spectrogram_encoder=True, freeze_text_encoder=True):
@@ -141,12 +144,17 @@ class multi_modal_model(nn.Module):
     def load_state_dict(self, state_dict, *a, **k):
         if self.text_encoder is None:                      # a reference checkpoint carries the CLAP tower, which lives outside this package
             state_dict = {key: v for key, v in state_dict.items() if not key.startswith("text_encoder.")}
+        elif isinstance(self.text_encoder, ClapTextTower):   # the checkpoint holds a whole ClapModel: the tower takes its text half
+            keep = ("text_encoder.text_model.", "text_encoder.text_projection.")
+            state_dict = ClapTextTower.own_keys({key: v for key, v in state_dict.items() if not key.startswith("text_encoder.") or key.startswith(keep)},
+                                                "text_encoder.")
         return super().load_state_dict(state_dict, *a, **k)
 
     def forward(self, spectrogram_batch, tokenized_text_batch):
         raise NotImplementedError("inference only")
 
     def get_text_features(self, input_ids, attention_mask):
+        """text_projection(text_encoder.get_text_features(...)): with a ClapTextTower every step is a HIP launch, ids may come from the CPU."""
         if self.text_encoder is None:
             raise RuntimeError("multi_modal_model was built without a text encoder: pass the CLAP text feature to project_text_features()")
         return self.text_projection(self.text_encoder.get_text_features(input_ids=input_ids, attention_mask=attention_mask))

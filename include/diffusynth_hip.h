@@ -682,6 +682,29 @@ int ds_lstm_layer(const float* pre, long long pre_batch_stride, long long pre_st
  * [n0 + n1, n0 + n1 + n2), each by itself, and sigmoid over the n3 columns that follow. */
 int ds_timbre_heads(float* y, int y_stride, int B, int n0, int n1, int n2, int n3, void* stream);
 
+/* ---------------------------------------------------------------- CLAP text tower (RoBERTa-base encoder, pooler, projection), fp32
+ * The dense layers and the post-LN residuals are ds_linear / ds_add_layernorm / ds_activation; these are the launches they do not cover
+ * (csrc/clap_text.hip).  No result below depends on what else is in the batch.
+ *
+ * x[b * S + s][:] = LayerNorm(word[id] + pos[pid] + type0) * gamma + beta over H (biased variance, eps inside the sqrt), id = input_ids[b][s]
+ * (device memory) and pid = pad_id + #{s' <= s : input_ids[b][s'] != pad_id} if id != pad_id, else pad_id: RoBERTa's position rule, a
+ * function of input_ids alone.  word [V][H], pos [P][H], type0 [H].  The ids live on the device, so the call cannot see them: a row whose id
+ * is outside [0, V) or whose position is outside [0, P) is filled with NaN, and no table is read out of bounds. */
+int ds_text_embed(const int64_t* input_ids, int B, int S, int pad_id, const float* word, int V, const float* pos, int P, const float* type0,
+                  const float* gamma, const float* beta, int H, float eps, float* x, void* stream);
+/* ctx[b * S + q][h * d : (h + 1) * d] = softmax_k(q . k * d^-0.5 + mask_k) v per (sample, head, query), bidirectional, from the stacked rows
+ * qkv [B * S][3H] = q | k | v with H = heads * d.  mask [B][S] of uint8 (mask_bytes 1) or int32 (mask_bytes 4), nonzero = attend, NULL = all
+ * ones: a masked key has probability exactly 0 and takes no part in the maximum; a query with every key masked gives zeros.
+ * 1 <= S <= 512, d a multiple of 4 up to 128.  The bits of a query's output do not depend on S or on the rest of the batch as long as the
+ * extra keys are masked: a prompt alone and the same prompt padded inside a batch give equal rows. */
+int ds_text_attention(const float* qkv, const void* mask, int mask_bytes, int B, int S, int heads, int d, float* ctx, void* stream);
+/* The tower's tail, [B][D] rows, in place allowed: DS_TAIL_TANH (the pooler) and DS_TAIL_RELU (the projection) elementwise, eps unused;
+ * DS_TAIL_L2NORM: out[b][:] = x[b][:] / max(||x[b]||_2, eps), so an all-zero row stays zero. */
+#define DS_TAIL_TANH 0
+#define DS_TAIL_RELU 1
+#define DS_TAIL_L2NORM 2
+int ds_text_tail(const float* x, int B, int D, int op, float eps, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
