@@ -6,7 +6,9 @@ inpainting, one batch-1 ``inpaint_sample`` per note of the MIDI arranger).  A ba
 run on, and every tick advances every active call by one step with ONE U-Net forward per bucket and ONE ``ds_step_rows``
 launch per bucket that applies each row's own guidance scale, coefficients, inpaint blend and step noise.  Requests of the
 "dpmpp_2m" sampler share buckets and U-Net batches with the others: their rows are stepped by one ``ds_dpm_step_rows`` launch per
-bucket, each request on history rows of its own that stay where they are for the request's lifetime.
+bucket, each request on history rows of its own that stay where they are for the request's lifetime.  Requests whose sampler has
+a guidance rescale (``activate_classifier_free_guidance(..., guidance_rescale=phi)``) get their combined eps from one
+``ds_cfg_rescale_rows`` launch per bucket in front of the step launches, written over their unconditional eps rows.
 
     b = SamplingBatcher(unet, max_rows=128)
     h = b.submit(dss, "inpaint_sample", shape, 0.7, guide, mask, condition=c, sampler="ddpm", use_dynamic_mask=True, seed=7)
@@ -80,6 +82,7 @@ class _Request:
         self.B, self.C, self.H, self.W = prog.shape
         self.cfg = dss.CFG != 1.0
         self.scale = float(dss.CFG)
+        self.phi = float(dss.guidance_rescale) if self.cfg else 0.0     # guidance rescale (applied under CFG only, as in the sampler)
         self.unet_rows = self.B * (2 if self.cfg else 1)
         self.sampler = args["sampler"]
         cond = args["condition"]
@@ -283,7 +286,9 @@ class SamplingBatcher:
         Cc = reqs[0].C
         R = sum(r.B for r in reqs)
         R1 = sum(r.B for r in reqs if not r.solver)       # table rows [0, R1): ds_step_rows; [R1, R): ds_dpm_step_rows
+        Rg = sum(r.B for r in reqs if r.phi > 0.0)        # rows of the ds_cfg_rescale_rows launch (guidance rescale)
         ni, nf, npp = L.SR["DS_SR_NI"], L.SR["DS_SR_NF"], L.SR["DS_SR_NP"]
+        gi, gf = L.CR["DS_CR_NI"], L.CR["DS_CR_NF"]
         # column tables of the DDPM requests (one per distinct layout)
         col_tabs, col_off, n_cols = {}, {}, 0
         for r in reqs:
@@ -301,7 +306,9 @@ class SamplingBatcher:
         o_p = o_f + up(4 * R * nf)
         o_h = o_p + up(8 * R * npp)
         o_c = o_h + up(8 * max(R - R1, 1))
-        nbytes = o_c + up(4 * max(n_cols, 1))
+        o_gi = o_c + up(4 * max(n_cols, 1))
+        o_gf = o_gi + up(4 * Rg * gi)
+        nbytes = o_gf + up(4 * Rg * gf)
         host, ev = self._staging(nbytes)
         hb = host.numpy()
         tim = hb[o_t:o_t + 8 * Bu].view(np.int64)
@@ -310,11 +317,14 @@ class SamplingBatcher:
         prow = hb[o_p:o_p + 8 * R * npp].view(np.uint64).reshape(R, npp)
         hrow = hb[o_h:o_h + 8 * (R - R1)].view(np.uint64)
         cols = hb[o_c:o_c + 4 * max(n_cols, 1)].view(np.int32)
+        girow = hb[o_gi:o_gi + 4 * Rg * gi].view(np.int32).reshape(Rg, gi)
+        gfrow = hb[o_gf:o_gf + 4 * Rg * gf].view(np.float32).reshape(Rg, gf)
         for key, off in col_tabs.items():
             cols[off:off + len(key)] = key
         S = L.SR
         keep = []
         nxt = [0, R1]                   # next table row of a ds_step_rows request, of a solver request
+        gnxt = 0                        # next row of the rescale tables
         CHW = Cc * H * W
         for r, (x0, e0, ec0, d0) in zip(reqs, b.lay):
             k, B, prog = r.k, r.B, r.prog
@@ -329,7 +339,15 @@ class SamplingBatcher:
             irow[sl] = 0
             irow[sl, S["DS_SR_X"]] = x0 + ar
             irow[sl, S["DS_SR_EPS"]] = e0 + ar
-            irow[sl, S["DS_SR_EPSC"]] = (ec0 + ar) if ec0 >= 0 else -1
+            if r.phi > 0.0:             # the rescale launch combines into the unconditional eps rows: the step sees a plain eps
+                gsl = slice(gnxt, gnxt + B)
+                gnxt += B
+                girow[gsl, L.CR["DS_CR_U"]] = girow[gsl, L.CR["DS_CR_OUT"]] = e0 + ar
+                girow[gsl, L.CR["DS_CR_C"]] = ec0 + ar
+                gfrow[gsl, L.CR["DS_CR_SCALE"]], gfrow[gsl, L.CR["DS_CR_PHI"]] = r.scale, r.phi
+                irow[sl, S["DS_SR_EPSC"]] = -1
+            else:
+                irow[sl, S["DS_SR_EPSC"]] = (ec0 + ar) if ec0 >= 0 else -1
             irow[sl, S["DS_SR_OUT"]] = x0 + ar
             irow[sl, S["DS_SR_DUP"]] = (d0 + ar) if d0 >= 0 else -1
             frow[sl] = 0
@@ -375,6 +393,10 @@ class SamplingBatcher:
         else:
             eps = self.unet(b.x, t_dev, b.cond)
         out = torch.empty_like(b.x)
+        if Rg:
+            g = L.CfgRescaleRowsParams(eps=eps.data_ptr(), irow=dev.data_ptr() + o_gi, frow=dev.data_ptr() + o_gf, gain=None,
+                                       R=Rg, CHW=CHW, Beps=eps.shape[0])
+            L.call("ds_cfg_rescale_rows", C.byref(g), L.current_stream())
         for name, first, n in (("ds_step_rows", 0, R1), ("ds_dpm_step_rows", R1, R - R1)):
             if n == 0:
                 continue

@@ -551,6 +551,126 @@ __global__ __launch_bounds__(256) void dpm_step_rows_kernel(const ds_step_rows_p
 }
 #pragma clang fp contract(fast)
 
+// ------------------------------------------------------------------------------------------------ guidance rescale
+// out = g e with e = guided_eps(eps_u, eps_c, s) and g = phi std(eps_c) / std(e) + (1 - phi) over one row of N elements.  One block of
+// CR_THREADS per row: piece v (elements [4v, 4v + 4)) belongs to thread v % CR_THREADS in the 16-byte and in the scalar form alike, a
+// thread adds its elements in ascending order into float64 sums, and the sums meet in wave_sum and then wave by wave — an order that
+// N alone decides.  Two passes about the mean: sums, then squares of the distances from the means (the common 1 / (N - 1) of the two
+// variances cancels in the ratio).  cfg_rescale_kernel and cfg_rescale_rows_kernel both run cfg_rescale_row, so a row of
+// ds_cfg_rescale_rows is the same bits as ds_cfg_rescale given the same inputs.
+constexpr int CR_THREADS = 1024, CR_WAVES = CR_THREADS / 64;
+
+// piece at element i0: n (1..4) elements are inside the row; vec only where every piece is whole
+__device__ __forceinline__ void cr_load(const float* p, int i0, int n, bool vec, float (&v)[4]) {
+    if (vec) {
+        load_v<4>(p + i0, true, v);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = k < n ? p[i0 + k] : 0.f;
+}
+// both totals to every thread
+__device__ __forceinline__ void cr_block_sum(double& a, double& b, double (&red)[2][CR_WAVES]) {
+    a = wave_sum(a);
+    b = wave_sum(b);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = a;
+        red[1][threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    a = b = 0.0;
+#pragma unroll
+    for (int w = 0; w < CR_WAVES; ++w) {
+        a += red[0][w];
+        b += red[1][w];
+    }
+}
+#pragma clang fp contract(off)
+__device__ __forceinline__ float cfg_rescale_row(const float* u, const float* c, float* out, int N, float scale, float phi,
+                                                 double (&red)[2][2][CR_WAVES]) {
+    const bool vec = N % 4 == 0 && ((((uint64_t)u | (uint64_t)c | (uint64_t)out) & 15) == 0);
+    const int nv = (N + 3) / 4;
+    float g = 1.0f;
+    if (phi != 0.f) {                                   // (block-uniform)
+        double sc = 0.0, se = 0.0;
+        for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
+            const int i0 = v * 4, n = min(4, N - i0);
+            float uv[4], cv[4];
+            cr_load(u, i0, n, vec, uv);
+            cr_load(c, i0, n, vec, cv);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) {
+                    sc += (double)cv[k];
+                    se += (double)guided_eps(uv[k], true, cv[k], scale);
+                }
+        }
+        cr_block_sum(sc, se, red[0]);
+        const double mc = sc / N, me = se / N;
+        double qc = 0.0, qe = 0.0;
+        for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
+            const int i0 = v * 4, n = min(4, N - i0);
+            float uv[4], cv[4];
+            cr_load(u, i0, n, vec, uv);
+            cr_load(c, i0, n, vec, cv);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) {
+                    const double dc = (double)cv[k] - mc, de = (double)guided_eps(uv[k], true, cv[k], scale) - me;
+                    qc += dc * dc;
+                    qe += de * de;
+                }
+        }
+        cr_block_sum(qc, qe, red[1]);
+        const double ratio = qe > 0.0 ? sqrt(qc / qe) : 1.0;          // std(e) == 0: nothing to scale
+        g = (float)((double)phi * ratio + (1.0 - (double)phi));
+    }
+    for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
+        const int i0 = v * 4, n = min(4, N - i0);
+        float uv[4], cv[4], o[4];
+        cr_load(u, i0, n, vec, uv);
+        cr_load(c, i0, n, vec, cv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = g * guided_eps(uv[k], true, cv[k], scale);
+        if (vec) store_v<4>(out + i0, o);
+        else
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) out[i0 + k] = o[k];
+    }
+    return g;
+}
+#pragma clang fp contract(fast)
+
+// grid: one block per sample
+__global__ __launch_bounds__(CR_THREADS) void cfg_rescale_kernel(const ds_cfg_rescale_params p) {
+    __shared__ double red[2][2][CR_WAVES];
+    const size_t off = (size_t)blockIdx.x * p.CHW;
+    const float g = cfg_rescale_row(p.eps_u + off, p.eps_c + off, p.out + off, p.CHW, p.cfg_scale, p.phi, red);
+    if (p.gain && threadIdx.x == 0) p.gain[blockIdx.x] = g;
+}
+
+// grid: one block per table row.  The table is the host's: a row that points outside the buffer is never read out of bounds (see
+// step_rows_kernel)
+__global__ __launch_bounds__(CR_THREADS) void cfg_rescale_rows_kernel(const ds_cfg_rescale_rows_params p) {
+    __shared__ double red[2][2][CR_WAVES];
+    const int r = blockIdx.x;
+    const int32_t* ir = p.irow + (size_t)r * DS_CR_NI;
+    const float* fr = p.frow + (size_t)r * DS_CR_NF;
+    const int ur = ir[DS_CR_U], cr = ir[DS_CR_C], orow = ir[DS_CR_OUT];
+    const float scale = fr[DS_CR_SCALE], phi = fr[DS_CR_PHI];
+    const bool bad = ur < 0 || ur >= p.Beps || cr < 0 || cr >= p.Beps || !(phi >= 0.f && phi <= 1.f);
+    float g = __builtin_nanf("");
+    if (orow >= 0 && orow < p.Beps) {                   // (block-uniform, like bad)
+        float* out = p.eps + (size_t)orow * p.CHW;
+        if (bad)
+            for (int i = threadIdx.x; i < p.CHW; i += CR_THREADS) out[i] = g;
+        else
+            g = cfg_rescale_row(p.eps + (size_t)ur * p.CHW, p.eps + (size_t)cr * p.CHW, out, p.CHW, scale, phi, red);
+    }
+    if (p.gain && threadIdx.x == 0) p.gain[r] = g;
+}
+
 __global__ void gather_cols_kernel(const float* src, int src_w, const int32_t* cols, int out_w, float* out, size_t total) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t row = i / out_w;
@@ -813,6 +933,24 @@ extern "C" int ds_dpm_step_rows(const ds_step_rows_params* p, const uint64_t* hr
     if (vec) hipLaunchKernelGGL(dpm_step_rows_kernel<4>, grid, dim3(256), 0, st, *p, hrow);
     else hipLaunchKernelGGL(dpm_step_rows_kernel<1>, grid, dim3(256), 0, st, *p, hrow);
     DS_CHECK_LAUNCH("dpm_step_rows");
+    return DS_OK;
+}
+
+extern "C" int ds_cfg_rescale(const ds_cfg_rescale_params* p, void* stream) {
+    DS_REQUIRE(p && p->eps_u && p->eps_c && p->out, "cfg_rescale: null pointer");
+    DS_REQUIRE(p->B > 0 && p->CHW > 0 && p->CHW <= (1 << 30), "cfg_rescale: bad sizes (B=%d CHW=%d)", p->B, p->CHW);
+    DS_REQUIRE(p->phi >= 0.f && p->phi <= 1.f, "cfg_rescale: phi %g is not in [0, 1]", (double)p->phi);
+    hipLaunchKernelGGL(cfg_rescale_kernel, dim3((unsigned)p->B), dim3(CR_THREADS), 0, reinterpret_cast<hipStream_t>(stream), *p);
+    DS_CHECK_LAUNCH("cfg_rescale");
+    return DS_OK;
+}
+
+extern "C" int ds_cfg_rescale_rows(const ds_cfg_rescale_rows_params* p, void* stream) {
+    DS_REQUIRE(p && p->eps && p->irow && p->frow, "cfg_rescale_rows: null pointer");
+    DS_REQUIRE(p->R > 0 && p->CHW > 0 && p->CHW <= (1 << 30) && p->Beps > 0, "cfg_rescale_rows: bad sizes (R=%d CHW=%d Beps=%d)", p->R, p->CHW,
+               p->Beps);
+    hipLaunchKernelGGL(cfg_rescale_rows_kernel, dim3((unsigned)p->R), dim3(CR_THREADS), 0, reinterpret_cast<hipStream_t>(stream), *p);
+    DS_CHECK_LAUNCH("cfg_rescale_rows");
     return DS_OK;
 }
 

@@ -20,6 +20,10 @@ DPM-Solver++(2M), a deterministic second-order multistep solver on the same sche
   * The loop carries one history tensor per call (the previous step's x0 prediction).  ``p_sample(..., sampler="dpmpp_2m")`` on its
     own has no history, so it takes a first-order step.
   * ``logsnr_timesteps(n)`` gives the step list (uniform in log signal-to-noise ratio) the solver is most accurate on.
+
+``activate_classifier_free_guidance(CFG, unconditional_condition, guidance_rescale=phi)`` adds guidance rescale to every sampler:
+per sample, the combined eps is scaled back towards the standard deviation of the conditional eps (ds_cfg_rescale).
+The default 0.0 is the reference's combine, bit for bit.
 """
 import ctypes as C
 
@@ -49,6 +53,7 @@ class DiffSynthSampler:
         self.respaced = False
         self.define_beta_schedule()
         self.CFG = 1.0
+        self.guidance_rescale = 0.0
         self.mute = mute
         self.noise_strategy = noise_strategy
         self.noise_device = noise_device
@@ -98,11 +103,18 @@ class DiffSynthSampler:
         idx[0], idx[-1] = 0, len(lam) - 1
         return sorted(set(idx))
 
-    def activate_classifier_free_guidance(self, CFG, unconditional_condition):
+    def activate_classifier_free_guidance(self, CFG, unconditional_condition, guidance_rescale=0.0):
+        """``guidance_rescale`` (phi in [0, 1], beyond the reference): the combined eps of every step is scaled, per sample, by
+        phi * std(eps_cond) / std(eps) + (1 - phi) (ds_cfg_rescale).  0.0 is the reference's combine; with CFG == 1.0
+        there is no combine, and the value is kept but not applied."""
         assert (not unconditional_condition is None) or CFG == 1.0, \
             "For CFG != 1.0, unconditional_condition must be available"
+        phi = float(guidance_rescale)
+        if not 0.0 <= phi <= 1.0:                 # (NaN fails both comparisons)
+            raise ValueError("guidance_rescale must be in [0, 1], got %r" % (guidance_rescale,))
         self.CFG = CFG
         self.unconditional_condition = unconditional_condition
+        self.guidance_rescale = phi
 
     # ------------------------------------------------------------------ noise
     def _randn(self, shape, batchsize=None):
@@ -300,6 +312,21 @@ class DiffSynthSampler:
         out = model(xx, tt, cc, paired_halves=True) if getattr(model, "cfg_paired_halves", False) else model(xx, tt, cc)
         return out.chunk(2)
 
+    def _guided(self, eps, eps_c):
+        """(eps, eps_cond) as the step kernel takes them: with guidance rescale the combine is done here (ds_cfg_rescale) and the
+        step kernel gets its result as a plain eps."""
+        eps = eps.contiguous()
+        if eps_c is None:
+            return eps, None
+        eps_c = eps_c.contiguous()
+        if self.guidance_rescale == 0.0:
+            return eps, eps_c
+        out = torch.empty_like(eps)
+        p = L.CfgRescaleParams(eps_u=eps.data_ptr(), eps_c=eps_c.data_ptr(), out=out.data_ptr(), gain=None, cfg_scale=float(self.CFG),
+                               phi=self.guidance_rescale, B=eps.shape[0], CHW=eps[0].numel())
+        L.call("ds_cfg_rescale", C.byref(p), L.current_stream())
+        return out, None
+
     @torch.no_grad()
     def ddim_sample(self, model, x, t, condition=None, ddim_eta=0.0, _coef=None, _blend=None):
         mapped_t = self._timestep_map_on(t.device, t.dtype)[t]
@@ -312,11 +339,11 @@ class DiffSynthSampler:
         if not x.is_cuda:
             raise RuntimeError("diffusynth_amd.DiffSynthSampler steps on the GPU only (ds_ddim_step); got a CPU tensor")
         x = x.contiguous().float()
-        eps = eps.contiguous()
+        eps, eps_c = self._guided(eps, eps_c)
         out = torch.empty_like(x)
         coef = coef.to(x.device)
         B = x.shape[0]
-        p = L.StepParams(x=x.data_ptr(), eps=eps.data_ptr(), eps_cond=(eps_c.contiguous().data_ptr() if eps_c is not None else None),
+        p = L.StepParams(x=x.data_ptr(), eps=eps.data_ptr(), eps_cond=(eps_c.data_ptr() if eps_c is not None else None),
                          noise=step_noise.contiguous().data_ptr(), out=out.data_ptr(), coef=coef.data_ptr(),
                          cfg_scale=float(self.CFG), blend_mode=0, guide=None, init_noise=None, mask=None, qcoef=None,
                          B=B, CHW=x[0].numel(), HW=x.shape[2] * x.shape[3])
@@ -343,10 +370,10 @@ class DiffSynthSampler:
         if not x.is_cuda:
             raise RuntimeError("diffusynth_amd.DiffSynthSampler steps on the GPU only (ds_dpm_step); got a CPU tensor")
         x = x.contiguous().float()
-        eps = eps.contiguous()
+        eps, eps_c = self._guided(eps, eps_c)
         out = torch.empty_like(x)
         coef = _coef.to(x.device)
-        p = L.DpmStepParams(x=x.data_ptr(), eps=eps.data_ptr(), eps_cond=(eps_c.contiguous().data_ptr() if eps_c is not None else None),
+        p = L.DpmStepParams(x=x.data_ptr(), eps=eps.data_ptr(), eps_cond=(eps_c.data_ptr() if eps_c is not None else None),
                             hist=(_hist.data_ptr() if _hist is not None else None), out=out.data_ptr(), coef=coef.data_ptr(),
                             cfg_scale=float(self.CFG), blend_mode=0, guide=None, init_noise=None, mask=None, qcoef=None,
                             B=x.shape[0], C=x.shape[1], H=x.shape[2], W=x.shape[3])

@@ -18,14 +18,16 @@ from .sampler import DiffSynthSampler
 
 @torch.no_grad()
 def sample_mixed_widths(model, requests, steps, *, timesteps=1000, height=128, channels=4, sampler="ddim", cfg_scale=1.0,
-                        unconditional_condition=None, device="cuda", noise_device=None, return_trajectory=False, use_timesteps=None):
+                        unconditional_condition=None, device="cuda", noise_device=None, return_trajectory=False, use_timesteps=None,
+                        guidance_rescale=0.0):
     """requests: list of dicts ``{"width": int, "condition": (label_dim,) tensor or None, "seed": int}``.
     Returns a list (request order) of final latents (4, height, width) — or of trajectories when asked.
 
     Each request's initial noise is drawn like a batch-1 reference call with its seed would draw it
     (``torch.manual_seed(seed)``; ``randn((1, C, H, train_width))``, on a private generator); requests of one width then share the
     loop.  ``use_timesteps`` (a list for ``DiffSynthSampler.respace``, e.g. ``logsnr_timesteps(steps)``) replaces the default
-    ``linspace(0, timesteps - 1, steps)``.
+    ``linspace(0, timesteps - 1, steps)``.  ``guidance_rescale`` is every sampler's
+    ``activate_classifier_free_guidance(..., guidance_rescale=)`` (stored, not applied, with ``cfg_scale == 1``).
 
     Only the deterministic samplers ("ddim", "dpmpp_2m") are served this way: with ``"ddpm"`` the per-step noise of a bucket would come from ONE
     generator stream, so a request's result would depend on which other requests share its width and on their order (the
@@ -50,8 +52,8 @@ def sample_mixed_widths(model, requests, steps, *, timesteps=1000, height=128, c
             s = DiffSynthSampler(timesteps, mute=True, device=device, height=height, max_batchsize=1, channels=channels,
                                  noise_device=noise_device)
             s.respace(list(np.linspace(0, timesteps - 1, steps, dtype=np.int32)) if use_timesteps is None else list(use_timesteps))
-            if cfg_scale != 1.0:
-                s.activate_classifier_free_guidance(cfg_scale, unconditional_condition)
+            if cfg_scale != 1.0 or guidance_rescale != 0.0:
+                s.activate_classifier_free_guidance(cfg_scale, unconditional_condition, guidance_rescale)
             c = None if nocond else requests[i]["condition"].to(device).float()[None]
             handles.append(b.submit(s, "sample", (1, channels, height, width), return_tensor=True, condition=c, sampler=sampler,
                                     seed=int(requests[i]["seed"])))

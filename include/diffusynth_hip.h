@@ -514,6 +514,46 @@ int ds_dpm_step(const ds_dpm_step_params* p, void* stream);
  * only where the row's coef[4] == 0, anywhere else the row is malformed.  A malformed row reads nothing, writes no history and
  * fills its output row (and its duplicate, when in range) with NaN.  A row is the same bits as ds_dpm_step on the same inputs. */
 int ds_dpm_step_rows(const ds_step_rows_params* p, const uint64_t* hrow, void* stream);
+/* Guidance rescale of the classifier-free-guidance combine (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are
+ * Flawed", section 3.4), per sample (row) of CHW fp32 elements:
+ *     e     = eps_u + cfg_scale * (eps_c - eps_u)              (the step kernels' combine: three separately rounded fp32 operations)
+ *     ratio = std(eps_c) / std(e)                              (over the row; 1 where std(e) == 0)
+ *     g     = phi * ratio + (1 - phi),   out = g * e
+ * The step kernels then take `out` as a plain eps (eps_cond NULL / DS_SR_EPSC -1).  phi in [0, 1]; phi == 0 reduces nothing and
+ * writes e itself (g == 1).  One block works on a row, in two passes about the mean (float64 sums of the fp32 elements: the row's
+ * mean, then the squares of the distances from it): element i belongs to thread (i / 4) % 1024, and the order of every sum
+ * depends on CHW only, not on the rows in the launch, on their number or on the addresses.  So a row is the same bits alone, in
+ * any batch and in either entry point.  No atomics, no workspace.  eps_u / eps_c / out are [B][CHW]; out may be eps_u (each
+ * element is read and written by the same thread).  gain (may be NULL) receives g [B].  A row is moved in 16-byte pieces when
+ * CHW % 4 == 0 and its three addresses are 16-byte aligned, element by element otherwise. */
+typedef struct {
+    const float* eps_u; const float* eps_c; float* out;
+    float* gain;
+    float cfg_scale, phi;
+    int32_t B, CHW;
+} ds_cfg_rescale_params;
+int ds_cfg_rescale(const ds_cfg_rescale_params* p, void* stream);
+/* ds_cfg_rescale over R rows that belong to different requests, inside one eps buffer of Beps rows (the U-Net output of a
+ * SamplingBatcher tick).  Row r reads the unconditional eps from eps[irow[r][DS_CR_U]] and the conditional one from
+ * eps[irow[r][DS_CR_C]], and writes eps[irow[r][DS_CR_OUT]] (its own unconditional row is allowed, a row that another table row
+ * reads is not), with its own scale frow[r][DS_CR_SCALE] and phi frow[r][DS_CR_PHI]; gain (may be NULL) receives g [R].  Rows of eps
+ * that the table does not name are not touched.  A row whose input rows fall outside [0, Beps), or whose phi is not in [0, 1],
+ * reads nothing: its output row is filled with NaN (and its gain is NaN); a row whose output row is out of range writes no eps.
+ * A row is the same bits as ds_cfg_rescale on the same inputs. */
+#define DS_CR_U 0
+#define DS_CR_C 1
+#define DS_CR_OUT 2
+#define DS_CR_NI 3
+#define DS_CR_SCALE 0                  /* frow */
+#define DS_CR_PHI 1
+#define DS_CR_NF 2
+typedef struct {
+    float* eps;
+    const int32_t* irow; const float* frow;
+    float* gain;
+    int32_t R, CHW, Beps;
+} ds_cfg_rescale_rows_params;
+int ds_cfg_rescale_rows(const ds_cfg_rescale_rows_params* p, void* stream);
 /* counter-based N(0,1) generator (Philox4x32-10 + Box-Muller) for the throughput mode */
 int ds_philox_normal(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 /* column gather of the "repeat" noise layout (DiffSynthSampler.py:97-167): out[b][c][h][j] = src[b][c][h][cols[j]] */
