@@ -112,6 +112,43 @@ class _Bucket:
         self.x = None                   # the U-Net input of the next tick (written by the previous tick's ds_step_rows)
 
 
+class _Tables:
+    """The one upload of a bucket tick, each part at a 16-byte boundary: the U-Net timesteps, the DS_SR_* tables of the R step rows
+    (rows [0, R1): ds_step_rows, [R1, R): ds_dpm_step_rows), the history addresses of the solver rows, the column tables of the DDPM
+    requests (one per distinct layout) and the DS_CR_* tables of the Rg rows of the ds_cfg_rescale_rows launch (guidance rescale)."""
+
+    def __init__(self, reqs, Bu):
+        self.R = R = sum(r.B for r in reqs)
+        self.R1 = R1 = sum(r.B for r in reqs if not r.solver)
+        self.Rg = Rg = sum(r.B for r in reqs if r.phi > 0.0)
+        self.col_tabs, self.n_cols = {}, 0          # layout -> offset of its columns in cols
+        for r in reqs:
+            if r.sampler == "ddpm" and tuple(r.cols) not in self.col_tabs:
+                self.col_tabs[tuple(r.cols)] = self.n_cols
+                self.n_cols += len(r.cols)
+        self.parts = {"tim": (np.int64, (Bu,), 0), "irow": (np.int32, (R, L.SR["DS_SR_NI"]), 0),        # name: (type, shape, floor)
+                      "frow": (np.float32, (R, L.SR["DS_SR_NF"]), 0), "prow": (np.uint64, (R, L.SR["DS_SR_NP"]), 0),
+                      "hrow": (np.uint64, (R - R1,), 1), "cols": (np.int32, (max(self.n_cols, 1),), 1),
+                      "girow": (np.int32, (Rg, L.CR["DS_CR_NI"]), 0), "gfrow": (np.float32, (Rg, L.CR["DS_CR_NF"]), 0)}
+        self.off, o = {}, 0                                             # part -> its byte offset in the upload
+        for name, (dt, shape, floor) in self.parts.items():             # (floor: the least number of elements the part reserves)
+            self.off[name] = o
+            o += (np.dtype(dt).itemsize * max(int(np.prod(shape)), floor) + 15) & ~15
+        self.nbytes = o
+
+    def bind(self, hb):
+        """Numpy views of the parts in the staged bytes ``hb`` (attributes tim, irow, ..., gfrow); writes the column tables."""
+        for name, (dt, shape, _) in self.parts.items():
+            o = self.off[name]
+            setattr(self, name, hb[o:o + np.dtype(dt).itemsize * int(np.prod(shape))].view(dt).reshape(shape))
+        for key, off in self.col_tabs.items():
+            self.cols[off:off + len(key)] = key
+
+    def at(self, dev, name, row=0):                 # device address of row ``row`` of a part in the uploaded bytes ``dev``
+        dt, shape, _ = self.parts[name]
+        return dev.data_ptr() + self.off[name] + row * np.dtype(dt).itemsize * int(np.prod(shape[1:]))
+
+
 class SamplingBatcher:
     """See the module docstring.  ``max_rows`` bounds the U-Net rows (CFG rows counted twice) of all requests in flight and
     ``max_buckets`` (default: the number of plans the U-Net's engine keeps, DS_MAX_PLANS) the buckets live at once; requests are
@@ -278,136 +315,99 @@ class SamplingBatcher:
             st[1].synchronize()
         return st
 
-    def _tick(self, b):
-        if b.dirty:
-            self._relayout(b)
-        reqs, Bu = b.reqs, b.Bu
-        H, W = b.key[0], b.key[1]
-        Cc = reqs[0].C
-        R = sum(r.B for r in reqs)
-        R1 = sum(r.B for r in reqs if not r.solver)       # table rows [0, R1): ds_step_rows; [R1, R): ds_dpm_step_rows
-        Rg = sum(r.B for r in reqs if r.phi > 0.0)        # rows of the ds_cfg_rescale_rows launch (guidance rescale)
-        ni, nf, npp = L.SR["DS_SR_NI"], L.SR["DS_SR_NF"], L.SR["DS_SR_NP"]
-        gi, gf = L.CR["DS_CR_NI"], L.CR["DS_CR_NF"]
-        # column tables of the DDPM requests (one per distinct layout)
-        col_tabs, col_off, n_cols = {}, {}, 0
-        for r in reqs:
-            if r.sampler == "ddpm":
-                key = tuple(r.cols)
-                if key not in col_tabs:
-                    col_tabs[key] = n_cols
-                    n_cols += len(key)
-                col_off[id(r)] = col_tabs[key]
-
-        def up(n):
-            return (n + 15) & ~15
-        o_t, o_i = 0, up(8 * Bu)
-        o_f = o_i + up(4 * R * ni)
-        o_p = o_f + up(4 * R * nf)
-        o_h = o_p + up(8 * R * npp)
-        o_c = o_h + up(8 * max(R - R1, 1))
-        o_gi = o_c + up(4 * max(n_cols, 1))
-        o_gf = o_gi + up(4 * Rg * gi)
-        nbytes = o_gf + up(4 * Rg * gf)
-        host, ev = self._staging(nbytes)
-        hb = host.numpy()
-        tim = hb[o_t:o_t + 8 * Bu].view(np.int64)
-        irow = hb[o_i:o_i + 4 * R * ni].view(np.int32).reshape(R, ni)
-        frow = hb[o_f:o_f + 4 * R * nf].view(np.float32).reshape(R, nf)
-        prow = hb[o_p:o_p + 8 * R * npp].view(np.uint64).reshape(R, npp)
-        hrow = hb[o_h:o_h + 8 * (R - R1)].view(np.uint64)
-        cols = hb[o_c:o_c + 4 * max(n_cols, 1)].view(np.int32)
-        girow = hb[o_gi:o_gi + 4 * Rg * gi].view(np.int32).reshape(Rg, gi)
-        gfrow = hb[o_gf:o_gf + 4 * Rg * gf].view(np.float32).reshape(Rg, gf)
-        for key, off in col_tabs.items():
-            cols[off:off + len(key)] = key
-        S = L.SR
-        keep = []
-        nxt = [0, R1]                   # next table row of a ds_step_rows request, of a solver request
-        gnxt = 0                        # next row of the rescale tables
+    def _fill_rows(self, b, tb):
+        """The table rows of every request of the bucket, in layout order.  Returns the tensors the launches must keep alive."""
+        S, CR, (H, W), Cc = L.SR, L.CR, b.key[:2], b.reqs[0].C
         CHW = Cc * H * W
-        for r, (x0, e0, ec0, d0) in zip(reqs, b.lay):
+        keep = []
+        nxt = [0, tb.R1]                # next table row of a ds_step_rows request, of a solver request
+        gnxt = 0                        # next row of the rescale tables
+        for r, (x0, e0, ec0, d0) in zip(b.reqs, b.lay):
             k, B, prog = r.k, r.B, r.prog
             row = nxt[r.solver]
             nxt[r.solver] += B
             sl = slice(row, row + B)
             ar = np.arange(B, dtype=np.int32)
             ar64 = ar.astype(np.uint64)
-            tim[x0:x0 + B] = r.mapped[k]
+            tb.tim[x0:x0 + B] = r.mapped[k]
             if r.cfg:
-                tim[ec0:ec0 + B] = r.mapped[k]
-            irow[sl] = 0
-            irow[sl, S["DS_SR_X"]] = x0 + ar
-            irow[sl, S["DS_SR_EPS"]] = e0 + ar
+                tb.tim[ec0:ec0 + B] = r.mapped[k]
+            irow, frow, prow = tb.irow[sl], tb.frow[sl], tb.prow[sl]
+            irow[:] = 0
+            irow[:, S["DS_SR_X"]] = x0 + ar
+            irow[:, S["DS_SR_EPS"]] = e0 + ar
             if r.phi > 0.0:             # the rescale launch combines into the unconditional eps rows: the step sees a plain eps
                 gsl = slice(gnxt, gnxt + B)
                 gnxt += B
-                girow[gsl, L.CR["DS_CR_U"]] = girow[gsl, L.CR["DS_CR_OUT"]] = e0 + ar
-                girow[gsl, L.CR["DS_CR_C"]] = ec0 + ar
-                gfrow[gsl, L.CR["DS_CR_SCALE"]], gfrow[gsl, L.CR["DS_CR_PHI"]] = r.scale, r.phi
-                irow[sl, S["DS_SR_EPSC"]] = -1
+                tb.girow[gsl, CR["DS_CR_U"]] = tb.girow[gsl, CR["DS_CR_OUT"]] = e0 + ar
+                tb.girow[gsl, CR["DS_CR_C"]] = ec0 + ar
+                tb.gfrow[gsl, CR["DS_CR_SCALE"]], tb.gfrow[gsl, CR["DS_CR_PHI"]] = r.scale, r.phi
+                irow[:, S["DS_SR_EPSC"]] = -1
             else:
-                irow[sl, S["DS_SR_EPSC"]] = (ec0 + ar) if ec0 >= 0 else -1
-            irow[sl, S["DS_SR_OUT"]] = x0 + ar
-            irow[sl, S["DS_SR_DUP"]] = (d0 + ar) if d0 >= 0 else -1
-            frow[sl] = 0
-            frow[sl, S["DS_SR_COEF"]:S["DS_SR_COEF"] + 5] = prog.coef_cpu[k].numpy()
-            frow[sl, S["DS_SR_CFG"]] = r.scale
-            prow[sl] = 0
+                irow[:, S["DS_SR_EPSC"]] = (ec0 + ar) if ec0 >= 0 else -1
+            irow[:, S["DS_SR_OUT"]] = x0 + ar
+            irow[:, S["DS_SR_DUP"]] = (d0 + ar) if d0 >= 0 else -1
+            frow[:] = 0
+            frow[:, S["DS_SR_COEF"]:S["DS_SR_COEF"] + 5] = prog.coef_cpu[k].numpy()
+            frow[:, S["DS_SR_CFG"]] = r.scale
+            prow[:] = 0
             if prog.inpaint:
                 mode, m = prog.blends[k]
-                irow[sl, S["DS_SR_BLEND"]] = mode
+                irow[:, S["DS_SR_BLEND"]] = mode
                 chw = 0 if m.shape[1] == 1 else 1
-                irow[sl, S["DS_SR_MASK_CHW"]] = chw
+                irow[:, S["DS_SR_MASK_CHW"]] = chw
                 if mode == 1:
-                    frow[sl, S["DS_SR_Q0"]:S["DS_SR_Q1"] + 1] = prog.q_cpu[k].numpy()
-                    prow[sl, S["DS_SR_INIT"]] = np.uint64(prog.init.data_ptr()) + np.uint64(4 * CHW) * ar64
-                prow[sl, S["DS_SR_GUIDE"]] = np.uint64(prog.guide.data_ptr()) + np.uint64(4 * CHW) * ar64
-                prow[sl, S["DS_SR_MASKP"]] = np.uint64(m.data_ptr()) + np.uint64(4 * (CHW if chw else H * W)) * ar64
+                    frow[:, S["DS_SR_Q0"]:S["DS_SR_Q1"] + 1] = prog.q_cpu[k].numpy()
+                    prow[:, S["DS_SR_INIT"]] = np.uint64(prog.init.data_ptr()) + np.uint64(4 * CHW) * ar64
+                prow[:, S["DS_SR_GUIDE"]] = np.uint64(prog.guide.data_ptr()) + np.uint64(4 * CHW) * ar64
+                prow[:, S["DS_SR_MASKP"]] = np.uint64(m.data_ptr()) + np.uint64(4 * (CHW if chw else H * W)) * ar64
             if r.solver:
-                hrow[row - R1:row - R1 + B] = np.uint64(r.hist.data_ptr()) + np.uint64(4 * CHW) * ar64
+                tb.hrow[row - tb.R1:row - tb.R1 + B] = np.uint64(r.hist.data_ptr()) + np.uint64(4 * CHW) * ar64
             if r.sampler == "ddpm":
                 dss = r.dss
                 draw_shape = (dss.max_batchsize, Cc, H, r.draw_w)
-                irow[sl, S["DS_SR_SAMPLE"]] = ar
-                irow[sl, S["DS_SR_DRAW_ROWS"]] = dss.max_batchsize
-                irow[sl, S["DS_SR_DRAW_W"]] = r.draw_w
-                irow[sl, S["DS_SR_COLS"]] = col_off[id(r)]
+                irow[:, S["DS_SR_SAMPLE"]] = ar
+                irow[:, S["DS_SR_DRAW_ROWS"]] = dss.max_batchsize
+                irow[:, S["DS_SR_DRAW_W"]] = r.draw_w
+                irow[:, S["DS_SR_COLS"]] = tb.col_tabs[tuple(r.cols)]
                 if dss.noise_device == "philox":        # the kernel computes the draw: only its counters are reserved
-                    irow[sl, S["DS_SR_NOISE"]] = _NOISE_PHILOX
-                    prow[sl, S["DS_SR_SEED"]] = dss._philox_seed
-                    prow[sl, S["DS_SR_OFFSET"]] = dss._philox_take(int(np.prod(draw_shape)))
+                    irow[:, S["DS_SR_NOISE"]] = _NOISE_PHILOX
+                    prow[:, S["DS_SR_SEED"]] = dss._philox_seed
+                    prow[:, S["DS_SR_OFFSET"]] = dss._philox_take(int(np.prod(draw_shape)))
                 else:                                   # the standalone call's draw, on the request's own generator
                     raw = dss._randn(draw_shape, B).contiguous()
                     keep.append(raw)
-                    irow[sl, S["DS_SR_NOISE"]] = _NOISE_DRAW
-                    prow[sl, S["DS_SR_DRAW"]] = raw.data_ptr()
-        dev = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        dev.copy_(host[:nbytes], non_blocking=True)
+                    irow[:, S["DS_SR_NOISE"]] = _NOISE_DRAW
+                    prow[:, S["DS_SR_DRAW"]] = raw.data_ptr()
+        return keep
+
+    def _tick(self, b):
+        if b.dirty:
+            self._relayout(b)
+        reqs, Bu, H, W, Cc = b.reqs, b.Bu, b.key[0], b.key[1], b.reqs[0].C
+        tb = _Tables(reqs, Bu)
+        host, ev = self._staging(tb.nbytes)
+        tb.bind(host.numpy())
+        keep = self._fill_rows(b, tb)
+        dev = torch.empty(tb.nbytes, dtype=torch.uint8, device=self.dev)
+        dev.copy_(host[:tb.nbytes], non_blocking=True)
         ev.record()
-        t_dev = dev[o_t:o_t + 8 * Bu].view(torch.int64)
+        t_dev = dev[tb.off["tim"]:tb.off["tim"] + 8 * Bu].view(torch.int64)
         paired = b.paired and getattr(self.unet, "cfg_paired_halves", False)
         self.unet_batches.add((Bu, H, W, b.key[2], paired))
-        if paired:
-            eps = self.unet(b.x, t_dev, b.cond, paired_halves=True)
-        else:
-            eps = self.unet(b.x, t_dev, b.cond)
+        eps = self.unet(b.x, t_dev, b.cond, paired_halves=True) if paired else self.unet(b.x, t_dev, b.cond)
         out = torch.empty_like(b.x)
-        if Rg:
-            g = L.CfgRescaleRowsParams(eps=eps.data_ptr(), irow=dev.data_ptr() + o_gi, frow=dev.data_ptr() + o_gf, gain=None,
-                                       R=Rg, CHW=CHW, Beps=eps.shape[0])
+        if tb.Rg:
+            g = L.CfgRescaleRowsParams(eps=eps.data_ptr(), irow=tb.at(dev, "girow"), frow=tb.at(dev, "gfrow"), gain=None,
+                                       R=tb.Rg, CHW=Cc * H * W, Beps=eps.shape[0])
             L.call("ds_cfg_rescale_rows", C.byref(g), L.current_stream())
-        for name, first, n in (("ds_step_rows", 0, R1), ("ds_dpm_step_rows", R1, R - R1)):
+        for name, first, n, hrow in (("ds_step_rows", 0, tb.R1, ()), ("ds_dpm_step_rows", tb.R1, tb.R - tb.R1, (tb.at(dev, "hrow"),))):
             if n == 0:
                 continue
-            p = L.StepRowsParams(x=b.x.data_ptr(), eps=eps.data_ptr(), out=out.data_ptr(), irow=dev.data_ptr() + o_i + 4 * ni * first,
-                                 frow=dev.data_ptr() + o_f + 4 * nf * first, prow=dev.data_ptr() + o_p + 8 * npp * first,
-                                 cols=(dev.data_ptr() + o_c) if n_cols else None,
-                                 R=n, C=Cc, H=H, W=W, Bx=Bu, Beps=eps.shape[0], Bout=Bu, n_cols=n_cols)
-            if name == "ds_step_rows":
-                L.call(name, C.byref(p), L.current_stream())
-            else:
-                L.call(name, C.byref(p), dev.data_ptr() + o_h, L.current_stream())
+            p = L.StepRowsParams(x=b.x.data_ptr(), eps=eps.data_ptr(), out=out.data_ptr(), irow=tb.at(dev, "irow", first),
+                                 frow=tb.at(dev, "frow", first), prow=tb.at(dev, "prow", first), cols=tb.at(dev, "cols") if tb.n_cols else None,
+                                 R=n, C=Cc, H=H, W=W, Bx=Bu, Beps=eps.shape[0], Bout=Bu, n_cols=tb.n_cols)
+            L.call(name, C.byref(p), *hrow, L.current_stream())
         del keep
         b.x = out
         done = []

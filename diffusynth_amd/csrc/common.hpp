@@ -33,6 +33,11 @@ void ds_set_error(const char* fmt, ...);
     } while (0)
 
 static inline bool ds_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+// blocks of 256 threads for a grid-stride loop over n items
+static inline int blocks_for(size_t n, int cap = 8192) {
+    const size_t b = (n + 255) / 256;
+    return (int)(b < (size_t)cap ? (b ? b : 1) : cap);
+}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE attribute: a launcher remembers, per kernel
 // instantiation, the devices it has already set it on (bit d of the mask; idempotent, so a race is benign).

@@ -327,6 +327,32 @@ class DiffSynthSampler:
         L.call("ds_cfg_rescale", C.byref(p), L.current_stream())
         return out, None
 
+    def _launch_step(self, name, params, x, eps, eps_c, coef, _blend, noise=None, **fields):
+        """The tail both step methods share: guidance, the output, the params struct (``noise`` and ``fields``: what only kernel
+        ``name`` takes) with its blend operands, and the launch."""
+        if not x.is_cuda:
+            raise RuntimeError(f"diffusynth_amd.DiffSynthSampler steps on the GPU only ({name}); got a CPU tensor")
+        x = x.contiguous().float()
+        eps, eps_c = self._guided(eps, eps_c)
+        out = torch.empty_like(x)
+        coef = coef.to(x.device)
+        if noise is not None:
+            fields["noise"] = noise.contiguous().data_ptr()
+        p = params(x=x.data_ptr(), eps=eps.data_ptr(), eps_cond=(eps_c.data_ptr() if eps_c is not None else None), out=out.data_ptr(),
+                   coef=coef.data_ptr(), cfg_scale=float(self.CFG), blend_mode=0, guide=None, init_noise=None, mask=None, qcoef=None,
+                   B=x.shape[0], **fields)
+        keep = [eps_c, noise, coef]
+        if _blend is not None:
+            mode, guide, init_noise, mask, qcoef = _blend
+            p.blend_mode, p.guide, p.mask = mode, guide.data_ptr(), mask.data_ptr()
+            p.mask_chw = 0 if mask.shape[1] == 1 else 1
+            if mode == 1:
+                p.init_noise, p.qcoef = init_noise.data_ptr(), qcoef.data_ptr()
+            keep += [guide, init_noise, mask, qcoef]
+        L.call(name, C.byref(p), L.current_stream())
+        del keep
+        return out
+
     @torch.no_grad()
     def ddim_sample(self, model, x, t, condition=None, ddim_eta=0.0, _coef=None, _blend=None):
         mapped_t = self._timestep_map_on(t.device, t.dtype)[t]
@@ -336,28 +362,8 @@ class DiffSynthSampler:
         else:
             step_noise, _ = self.get_deterministic_noise_tensor(x.shape[0], x.shape[3])
         coef = self._step_coefficients(t.cpu(), ddim_eta) if _coef is None else _coef
-        if not x.is_cuda:
-            raise RuntimeError("diffusynth_amd.DiffSynthSampler steps on the GPU only (ds_ddim_step); got a CPU tensor")
-        x = x.contiguous().float()
-        eps, eps_c = self._guided(eps, eps_c)
-        out = torch.empty_like(x)
-        coef = coef.to(x.device)
-        B = x.shape[0]
-        p = L.StepParams(x=x.data_ptr(), eps=eps.data_ptr(), eps_cond=(eps_c.data_ptr() if eps_c is not None else None),
-                         noise=step_noise.contiguous().data_ptr(), out=out.data_ptr(), coef=coef.data_ptr(),
-                         cfg_scale=float(self.CFG), blend_mode=0, guide=None, init_noise=None, mask=None, qcoef=None,
-                         B=B, CHW=x[0].numel(), HW=x.shape[2] * x.shape[3])
-        keep = [eps_c, step_noise, coef]
-        if _blend is not None:
-            mode, guide, init_noise, mask, qcoef = _blend
-            p.blend_mode, p.guide, p.mask = mode, guide.data_ptr(), mask.data_ptr()
-            p.mask_chw = 0 if mask.shape[1] == 1 else 1
-            if mode == 1:
-                p.init_noise, p.qcoef = init_noise.data_ptr(), qcoef.data_ptr()
-            keep += [guide, init_noise, mask, qcoef]
-        L.call("ds_ddim_step", C.byref(p), L.current_stream())
-        del keep
-        return out
+        return self._launch_step("ds_ddim_step", L.StepParams, x, eps, eps_c, coef, _blend, noise=step_noise,
+                                 CHW=x[0].numel(), HW=x.shape[2] * x.shape[3])
 
     @torch.no_grad()
     def dpm_sample(self, model, x, t, condition=None, _coef=None, _hist=None, _blend=None):
@@ -367,27 +373,8 @@ class DiffSynthSampler:
         eps, eps_c = self._predict(model, x, mapped_t, condition)
         if _coef is None:                       # every sample is the first step of its own call
             _coef = torch.cat([self._solver_coefficients([i])[0] for i in t.cpu().tolist()])
-        if not x.is_cuda:
-            raise RuntimeError("diffusynth_amd.DiffSynthSampler steps on the GPU only (ds_dpm_step); got a CPU tensor")
-        x = x.contiguous().float()
-        eps, eps_c = self._guided(eps, eps_c)
-        out = torch.empty_like(x)
-        coef = _coef.to(x.device)
-        p = L.DpmStepParams(x=x.data_ptr(), eps=eps.data_ptr(), eps_cond=(eps_c.data_ptr() if eps_c is not None else None),
-                            hist=(_hist.data_ptr() if _hist is not None else None), out=out.data_ptr(), coef=coef.data_ptr(),
-                            cfg_scale=float(self.CFG), blend_mode=0, guide=None, init_noise=None, mask=None, qcoef=None,
-                            B=x.shape[0], C=x.shape[1], H=x.shape[2], W=x.shape[3])
-        keep = [eps_c, coef]
-        if _blend is not None:
-            mode, guide, init_noise, mask, qcoef = _blend
-            p.blend_mode, p.guide, p.mask = mode, guide.data_ptr(), mask.data_ptr()
-            p.mask_chw = 0 if mask.shape[1] == 1 else 1
-            if mode == 1:
-                p.init_noise, p.qcoef = init_noise.data_ptr(), qcoef.data_ptr()
-            keep += [guide, init_noise, mask, qcoef]
-        L.call("ds_dpm_step", C.byref(p), L.current_stream())
-        del keep
-        return out
+        return self._launch_step("ds_dpm_step", L.DpmStepParams, x, eps, eps_c, _coef, _blend,
+                                 hist=(_hist.data_ptr() if _hist is not None else None), C=x.shape[1], H=x.shape[2], W=x.shape[3])
 
     def p_sample(self, model, x, t, condition=None, sampler="ddim"):
         if sampler == "ddim":

@@ -423,7 +423,9 @@ int ds_nhwc_to_nchw(const void* x, int dtype, int B, int C, int C_stride, int H,
  * DiffSynthSampler.ddim_sample (DiffSynthSampler.py:311-343): classifier-free-guidance combine,
  * predicted x0, sigma, direction and the update — and, for inpainting, the q_sample + mask blend of
  * p_sample_loop (DiffSynthSampler.py:499-510, 271-294).  fp32 NCHW, reference operation order,
- * no fused multiply-add: bit-exact with the CPU reference given identical inputs. */
+ * no fused multiply-add: bit-exact with the CPU reference given identical inputs.  16-byte accesses when
+ * HW % 4 == 0 and x / eps / eps_cond / noise / out are 16-byte aligned (guide / init_noise / mask: per sample,
+ * when their addresses allow it), element by element otherwise: the same bits either way. */
 typedef struct {
     const float* x; const float* eps; const float* eps_cond; /* eps_cond != NULL => eps is the uncond half */
     const float* noise; float* out;
@@ -442,7 +444,7 @@ int ds_ddim_step(const ds_step_params* p, void* stream);
  * U-Net batch).  Row r reads its state from x[irow[r][DS_SR_X]], its eps (the unconditional half under CFG) from eps[irow[r][DS_SR_EPS]]
  * and, when irow[r][DS_SR_EPSC] >= 0, the conditional eps from that row of eps; it writes the new state to out[irow[r][DS_SR_OUT]] and,
  * when irow[r][DS_SR_DUP] >= 0, a second copy to that row (the classifier-free-guidance duplicate of the next U-Net input).  Rows are
- * C*H*W fp32 each.  The arithmetic is ds_ddim_step's (same device function, no FMA contraction), with the row's own CFG scale,
+ * C*H*W fp32 each.  The arithmetic is ds_ddim_step's (same row loop, no FMA contraction), with the row's own CFG scale,
  * coefficients (frow: coef[5] as ds_step_params.coef, qcoef[2], cfg scale), blend mode and mask layout.
  * Step noise (irow[r][DS_SR_NOISE]): 0 none (sigma == 0), 1 read from a raw draw, 2 computed in the kernel.  For element (c, h, j) of
  * the row, the source index into its request's draw of shape (draw_rows, C, H, draw_w) is

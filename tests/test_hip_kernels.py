@@ -514,19 +514,32 @@ def test_layout_roundtrip():
 
 
 # ----------------------------------------------------------------------------------------- sampler step
-@pytest.mark.parametrize("cfg", [1.0, 6.0])
-@pytest.mark.parametrize("blend", [0, 1, 2])
-def test_ddim_step_bit_exact(cfg, blend):
+def _one_float_in(t):
+    """t's values on the device at an address one float past a fresh allocation: 4 bytes off every 16-byte boundary."""
+    buf = torch.empty(t.numel() + 4, device="cuda")
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4
+    return v
+
+
+def _check_ddim_step(cfg, blend, hw, off=(), mask_chw=False):
+    """ds_ddim_step against the oracle, bit for bit: samples of hw = (H, W) planes, the operands named in `off` taken one float into a
+    larger buffer, the mask per channel where mask_chw."""
     from oracle import sampler_ref as S
-    B, Cc, Hh, Ww = 3, 4, 8, 12
-    x, e_u, e_c, nz = (synth_input("k_s_" + n, (B, Cc, Hh, Ww)) for n in ("x", "eu", "ec", "nz"))
-    guide, init = synth_input("k_s_g", (B, Cc, Hh, Ww)), synth_input("k_s_i", (B, Cc, Hh, Ww))
-    mask = (synth_input("k_s_m", (B, 1, Hh, Ww)) > 0).float()
+    B, Cc, (Hh, Ww) = 3, 4, hw
     s = S.RefSampler(1000)
     s.respace(list(np.linspace(0, 999, 20, dtype=np.int32)))
+    # every sample of a call on one timestep, and each on its own (a kernel that read sample 0's coefficients for all would pass the first)
+    ts = [torch.full((B,), ti, dtype=torch.long) for ti in (0, 1, 10, 19)] + [torch.tensor([0, 10, 19])]
+    x, e_u, e_c, nz = (synth_input("k_s_" + n, (B, Cc, Hh, Ww)) for n in ("x", "eu", "ec", "nz"))
+    guide, init = synth_input("k_s_g", (B, Cc, Hh, Ww)), synth_input("k_s_i", (B, Cc, Hh, Ww))
+    mask = (synth_input("k_s_m", (B, Cc if mask_chw else 1, Hh, Ww)) > 0).float()
+    d = {k: (_one_float_in(v) if k in off else v.cuda().contiguous())
+         for k, v in dict(x=x, eu=e_u, ec=e_c, nz=nz, g=guide, i=init, m=mask).items()}
+    out = _one_float_in(x) if "out" in off else torch.empty_like(d["x"])
     for eta in (0.0, 1.0):
-        for ti in (0, 1, 10, 19):
-            t = torch.full((B,), ti, dtype=torch.long)
+        for t in ts:
             eps = S.cfg_combine(e_u, e_c, cfg) if cfg != 1.0 else e_u
             want = S.ddim_update(x, eps, nz, s.alphas_cumprod, s.alphas_cumprod_prev, t, eta)
             tq = torch.clamp(t - 1, min=0)
@@ -537,19 +550,65 @@ def test_ddim_step_bit_exact(cfg, blend):
             a_t = torch.from_numpy(s.alphas_cumprod)[t].float()
             a_p = torch.from_numpy(s.alphas_cumprod_prev)[t].float()
             sig = eta * torch.sqrt((1 - a_p) / (1 - a_t)) * torch.sqrt(1 - a_t / a_p)
-            coef = torch.stack([torch.sqrt(1. - a_t), torch.sqrt(a_t), torch.sqrt(a_p), torch.sqrt(1 - a_p - sig ** 2), sig], 1)
+            coef = torch.stack([torch.sqrt(1. - a_t), torch.sqrt(a_t), torch.sqrt(a_p), torch.sqrt(1 - a_p - sig ** 2), sig], 1).cuda().contiguous()
             qc = torch.stack([torch.from_numpy(s.sched["sqrt_alphas_cumprod"])[tq].float(),
-                              torch.from_numpy(s.sched["sqrt_one_minus_alphas_cumprod"])[tq].float()], 1)
-            d = {k: v.cuda().contiguous() for k, v in dict(x=x, eu=e_u, ec=e_c, nz=nz, g=guide, i=init, m=mask, c=coef, q=qc).items()}
-            out = torch.empty_like(d["x"])
+                              torch.from_numpy(s.sched["sqrt_one_minus_alphas_cumprod"])[tq].float()], 1).cuda().contiguous()
+            out.fill_(float("nan"))
             p = L.StepParams(x=d["x"].data_ptr(), eps=d["eu"].data_ptr(), eps_cond=d["ec"].data_ptr() if cfg != 1.0 else None,
-                             noise=d["nz"].data_ptr(), out=out.data_ptr(), coef=d["c"].data_ptr(), cfg_scale=cfg,
+                             noise=d["nz"].data_ptr(), out=out.data_ptr(), coef=coef.data_ptr(), cfg_scale=cfg,
                              blend_mode=blend, guide=d["g"].data_ptr(), init_noise=d["i"].data_ptr(), mask=d["m"].data_ptr(),
-                             qcoef=d["q"].data_ptr(), B=B, CHW=Cc * Hh * Ww, HW=Hh * Ww)
+                             qcoef=qc.data_ptr(), B=B, CHW=Cc * Hh * Ww, HW=Hh * Ww, mask_chw=int(mask_chw))
             L.call("ds_ddim_step", C.byref(p), L.current_stream())
             torch.cuda.synchronize()
             bad = (out.cpu() != want)
-            assert not bad.any(), (cfg, blend, eta, ti, int(bad.sum()), (out.cpu() - want).abs().max().item())
+            assert not bad.any(), (eta, t.tolist(), int(bad.sum()), (out.cpu() - want).abs().max().item())
+
+
+@pytest.mark.parametrize("cfg", [1.0, 6.0])
+@pytest.mark.parametrize("blend", [0, 1, 2])
+def test_ddim_step_bit_exact(cfg, blend):
+    _check_ddim_step(cfg, blend, (8, 12))          # 16-byte pieces
+
+
+# (name, shape of a sample's plane, operands one float into a larger buffer, mask per channel, blend modes: those that read what the case is about)
+_DDIM_STEP_PATHS = [
+    ("hw15", (3, 5), (), False, (0, 1, 2)),                       # H*W = 15: scalar, a mask plane whose length is no multiple of 4
+    ("state_off", (8, 12), ("x", "nz", "out"), False, (0, 1, 2)),  # the shape allows 16-byte pieces, the pointers do not: the launcher falls back
+    ("blend_off", (8, 12), ("g", "m"), False, (1, 2)),            # only the blend operands are off: the per-row operand decision
+    ("mask_chw", (8, 12), (), True, (1, 2)),                      # a [B, C, H, W] mask (mask_chw = 1)
+]
+
+
+@pytest.mark.parametrize("cfg", [1.0, 6.0])
+@pytest.mark.parametrize("hw, off, mask_chw, blend", [pytest.param(hw, off, m, b, id=f"{n}-{b}") for n, hw, off, m, bs in _DDIM_STEP_PATHS for b in bs])
+def test_ddim_step_bit_exact_paths(cfg, hw, off, mask_chw, blend):
+    _check_ddim_step(cfg, blend, hw, off, mask_chw)
+
+
+@pytest.mark.parametrize("hw", [(8, 12), (3, 5)])
+def test_ddim_step_sample_does_not_depend_on_its_grid_row(hw):
+    """One call on three samples against three calls on one sample each, same rows: a sample's result is the same bits whichever
+    blockIdx.y it ran on (16-byte pieces at W = 12, scalar at H*W = 15).  CFG, blend 1 and step noise on: every operand is indexed."""
+    B, Cc, (Hh, Ww) = 3, 4, hw
+    x, e_u, e_c, nz, guide, init = (synth_input("k_sg_" + n, (B, Cc, Hh, Ww)).cuda() for n in ("x", "eu", "ec", "nz", "g", "i"))
+    mask = (synth_input("k_sg_m", (B, 1, Hh, Ww)) > 0).float().cuda()
+    coef = (synth_input("k_sg_c", (B, 5)).abs() + 0.25).cuda()                   # a row of its own for every sample
+    qc = (synth_input("k_sg_q", (B, 2)).abs() + 0.25).cuda()
+
+    def run(lo, n, out):
+        p = L.StepParams(x=x[lo:].data_ptr(), eps=e_u[lo:].data_ptr(), eps_cond=e_c[lo:].data_ptr(), noise=nz[lo:].data_ptr(),
+                         out=out[lo:].data_ptr(), coef=coef[lo:].data_ptr(), cfg_scale=6.0, blend_mode=1, guide=guide[lo:].data_ptr(),
+                         init_noise=init[lo:].data_ptr(), mask=mask[lo:].data_ptr(), qcoef=qc[lo:].data_ptr(), B=n, CHW=Cc * Hh * Ww,
+                         HW=Hh * Ww)
+        L.call("ds_ddim_step", C.byref(p), L.current_stream())
+
+    together, alone = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
+    run(0, B, together)
+    for b in range(B):
+        run(b, 1, alone)
+    torch.cuda.synchronize()
+    assert torch.isfinite(together).all()
+    assert torch.equal(together, alone)
 
 
 def test_philox_normal_and_gather():
