@@ -8,7 +8,10 @@ launch per bucket that applies each row's own guidance scale, coefficients, inpa
 "dpmpp_2m" sampler share buckets and U-Net batches with the others: their rows are stepped by one ``ds_dpm_step_rows`` launch per
 bucket, each request on history rows of its own that stay where they are for the request's lifetime.  Requests whose sampler has
 a guidance rescale (``activate_classifier_free_guidance(..., guidance_rescale=phi)``) get their combined eps from one
-``ds_cfg_rescale_rows`` launch per bucket in front of the step launches, written over their unconditional eps rows.
+``ds_cfg_rescale_rows`` launch per bucket in front of the step launches, written over their unconditional eps rows.  Requests whose
+sampler has a condition mix (``set_condition_mix``: K prompts per sample) occupy ``B * (1 + K)`` U-Net rows and get theirs from one
+``ds_cfg_compose_rows`` launch per bucket beside it (a request is in exactly one of the two); one ``ds_copy_rows`` launch per bucket
+then writes the copies of their state rows that the step kernel's one duplicate does not cover.
 
     b = SamplingBatcher(unet, max_rows=128)
     h = b.submit(dss, "inpaint_sample", shape, 0.7, guide, mask, condition=c, sampler="ddpm", use_dynamic_mask=True, seed=7)
@@ -80,10 +83,12 @@ class _Request:
     def __init__(self, dss, method, prog, args, unet_dev):
         self.dss, self.method, self.prog = dss, method, prog
         self.B, self.C, self.H, self.W = prog.shape
-        self.cfg = dss.CFG != 1.0
+        self.mix = dss._mix                         # condition mix (set_condition_mix): (K,) or (K, W) float32, or None
+        self.cfg = dss.CFG != 1.0 or self.mix is not None       # the request has unconditional rows
+        self.K = (1 if self.mix is None else self.mix.shape[0]) if self.cfg else 0      # its conditional row groups
         self.scale = float(dss.CFG)
         self.phi = float(dss.guidance_rescale) if self.cfg else 0.0     # guidance rescale (applied under CFG only, as in the sampler)
-        self.unet_rows = self.B * (2 if self.cfg else 1)
+        self.unet_rows = self.B * (1 + self.K)
         self.sampler = args["sampler"]
         cond = args["condition"]
         self.cond = None if cond is None else cond.to(unet_dev)
@@ -115,12 +120,17 @@ class _Bucket:
 class _Tables:
     """The one upload of a bucket tick, each part at a 16-byte boundary: the U-Net timesteps, the DS_SR_* tables of the R step rows
     (rows [0, R1): ds_step_rows, [R1, R): ds_dpm_step_rows), the history addresses of the solver rows, the column tables of the DDPM
-    requests (one per distinct layout) and the DS_CR_* tables of the Rg rows of the ds_cfg_rescale_rows launch (guidance rescale)."""
+    requests (one per distinct layout), the DS_CR_* tables of the Rg rows of the ds_cfg_rescale_rows launch (guidance rescale), the
+    DS_CC_* tables and the weights of the Rm rows of the ds_cfg_compose_rows launch (condition mixes: one weight table per request)
+    and the Rp (src, dst) pairs of the ds_copy_rows launch (the copies of a state row beyond the step kernel's one duplicate)."""
 
     def __init__(self, reqs, Bu):
         self.R = R = sum(r.B for r in reqs)
         self.R1 = R1 = sum(r.B for r in reqs if not r.solver)
-        self.Rg = Rg = sum(r.B for r in reqs if r.phi > 0.0)
+        self.Rg = Rg = sum(r.B for r in reqs if r.phi > 0.0 and r.mix is None)
+        self.Rm = Rm = sum(r.B for r in reqs if r.mix is not None)
+        self.Rp = Rp = sum(r.B * (r.K - 1) for r in reqs if r.mix is not None)
+        self.n_wt = n_wt = sum(r.mix.size for r in reqs if r.mix is not None)
         self.col_tabs, self.n_cols = {}, 0          # layout -> offset of its columns in cols
         for r in reqs:
             if r.sampler == "ddpm" and tuple(r.cols) not in self.col_tabs:
@@ -129,7 +139,9 @@ class _Tables:
         self.parts = {"tim": (np.int64, (Bu,), 0), "irow": (np.int32, (R, L.SR["DS_SR_NI"]), 0),        # name: (type, shape, floor)
                       "frow": (np.float32, (R, L.SR["DS_SR_NF"]), 0), "prow": (np.uint64, (R, L.SR["DS_SR_NP"]), 0),
                       "hrow": (np.uint64, (R - R1,), 1), "cols": (np.int32, (max(self.n_cols, 1),), 1),
-                      "girow": (np.int32, (Rg, L.CR["DS_CR_NI"]), 0), "gfrow": (np.float32, (Rg, L.CR["DS_CR_NF"]), 0)}
+                      "girow": (np.int32, (Rg, L.CR["DS_CR_NI"]), 0), "gfrow": (np.float32, (Rg, L.CR["DS_CR_NF"]), 0),
+                      "mirow": (np.int32, (Rm, L.CC["DS_CC_NI"]), 0), "mfrow": (np.float32, (Rm, L.CC["DS_CC_NF"]), 0),
+                      "mwt": (np.float32, (n_wt,), 0), "pairs": (np.int32, (Rp, 2), 0)}
         self.off, o = {}, 0                                             # part -> its byte offset in the upload
         for name, (dt, shape, floor) in self.parts.items():             # (floor: the least number of elements the part reserves)
             self.off[name] = o
@@ -137,7 +149,7 @@ class _Tables:
         self.nbytes = o
 
     def bind(self, hb):
-        """Numpy views of the parts in the staged bytes ``hb`` (attributes tim, irow, ..., gfrow); writes the column tables."""
+        """Numpy views of the parts in the staged bytes ``hb`` (attributes tim, irow, ..., pairs); writes the column tables."""
         for name, (dt, shape, _) in self.parts.items():
             o = self.off[name]
             setattr(self, name, hb[o:o + np.dtype(dt).itemsize * int(np.prod(shape))].view(dt).reshape(shape))
@@ -150,7 +162,7 @@ class _Tables:
 
 
 class SamplingBatcher:
-    """See the module docstring.  ``max_rows`` bounds the U-Net rows (CFG rows counted twice) of all requests in flight and
+    """See the module docstring.  ``max_rows`` bounds the U-Net rows (CFG rows counted twice, rows of a K-prompt mix 1 + K times) of all requests in flight and
     ``max_buckets`` (default: the number of plans the U-Net's engine keeps, DS_MAX_PLANS) the buckets live at once; requests are
     admitted first in, first out at the start of a tick, and a request that does not fit waits (and holds back the ones after it).
     Not thread-safe; the U-Net is run on the current stream."""
@@ -197,7 +209,7 @@ class SamplingBatcher:
             assert shape[1] == self._geometry[1] and dss.channels == self._geometry[1], "shape[1] != self.channels"
             assert shape[2] == self._geometry[0] and dss.height == self._geometry[0], "shape[2] != self.height"
         cfg = dss.CFG != 1.0
-        rows = shape[0] * (2 if cfg else 1)
+        rows = shape[0] * ((2 if cfg else 1) if dss._mix is None else 1 + dss._mix.shape[0])
         if rows > self.max_rows:
             raise ValueError("the request needs %d U-Net rows, more than max_rows=%d" % (rows, self.max_rows))
         if cfg and a["condition"] is None:
@@ -271,8 +283,10 @@ class SamplingBatcher:
 
     def _layout(self, b):
         """Row layout of the bucket's U-Net batch: per request (x row of its first state row, eps row, conditional eps row or -1,
-        duplicate row or -1), the U-Net batch size and whether it is the paired [x; x] form."""
-        paired = all(r.cfg for r in b.reqs)
+        duplicate row or -1), the U-Net batch size and whether it is the paired [x; x] form.  A condition mix of K prompts lies
+        as [u rows; c_1 rows; ...; c_K rows]: its further conditional groups follow the first at a distance of B rows each, and a
+        bucket that holds one with K >= 2 is not paired."""
+        paired = all(r.K == 1 for r in b.reqs)
         lay, base = [], 0
         if paired:
             n = sum(r.B for r in b.reqs)
@@ -294,12 +308,15 @@ class SamplingBatcher:
         if b.paired:
             xs = [r.state for r in b.reqs] * 2
             if b.key[2]:
-                conds = [r.uncond for r in b.reqs] + [r.cond for r in b.reqs]
+                conds = [r.uncond for r in b.reqs] + [r.cond if r.mix is None else r.cond[:, 0] for r in b.reqs]
         else:
             for r in b.reqs:
-                xs += [r.state, r.state] if r.cfg else [r.state]
+                xs += [r.state] * (1 + r.K)
                 if b.key[2]:
-                    conds += [r.uncond, r.cond] if r.cfg else [r.cond]
+                    if r.mix is not None:
+                        conds += [r.uncond] + [r.cond[:, k] for k in range(r.K)]
+                    else:
+                        conds += [r.uncond, r.cond] if r.cfg else [r.cond]
         b.x = torch.cat(xs, 0).contiguous()
         b.cond = torch.cat(conds, 0).contiguous() if conds else None
         b.dirty = False
@@ -317,11 +334,12 @@ class SamplingBatcher:
 
     def _fill_rows(self, b, tb):
         """The table rows of every request of the bucket, in layout order.  Returns the tensors the launches must keep alive."""
-        S, CR, (H, W), Cc = L.SR, L.CR, b.key[:2], b.reqs[0].C
+        S, CR, CC, (H, W), Cc = L.SR, L.CR, L.CC, b.key[:2], b.reqs[0].C
         CHW = Cc * H * W
         keep = []
         nxt = [0, tb.R1]                # next table row of a ds_step_rows request, of a solver request
         gnxt = 0                        # next row of the rescale tables
+        mnxt = wnxt = pnxt = 0          # next row of the compose tables, next weight, next copy pair
         for r, (x0, e0, ec0, d0) in zip(b.reqs, b.lay):
             k, B, prog = r.k, r.B, r.prog
             row = nxt[r.solver]
@@ -331,12 +349,25 @@ class SamplingBatcher:
             ar64 = ar.astype(np.uint64)
             tb.tim[x0:x0 + B] = r.mapped[k]
             if r.cfg:
-                tb.tim[ec0:ec0 + B] = r.mapped[k]
+                tb.tim[ec0:ec0 + B * r.K] = r.mapped[k]
             irow, frow, prow = tb.irow[sl], tb.frow[sl], tb.prow[sl]
             irow[:] = 0
             irow[:, S["DS_SR_X"]] = x0 + ar
             irow[:, S["DS_SR_EPS"]] = e0 + ar
-            if r.phi > 0.0:             # the rescale launch combines into the unconditional eps rows: the step sees a plain eps
+            if r.mix is not None:       # the compose launch combines into the unconditional eps rows: the step sees a plain eps
+                msl = slice(mnxt, mnxt + B)
+                mnxt += B
+                tb.mirow[msl, CC["DS_CC_U"]] = tb.mirow[msl, CC["DS_CC_OUT"]] = e0 + ar
+                tb.mirow[msl, CC["DS_CC_K"]], tb.mirow[msl, CC["DS_CC_C0"]], tb.mirow[msl, CC["DS_CC_CSTRIDE"]] = r.K, ec0 + ar, B
+                tb.mirow[msl, CC["DS_CC_WT"]], tb.mirow[msl, CC["DS_CC_WTW"]] = wnxt, r.mix.size // r.K
+                tb.mfrow[msl, CC["DS_CC_SCALE"]], tb.mfrow[msl, CC["DS_CC_PHI"]] = r.scale, r.phi
+                tb.mwt[wnxt:wnxt + r.mix.size] = r.mix.ravel()
+                wnxt += r.mix.size
+                for j in range(1, r.K):     # the step launch writes the state row and one duplicate; ds_copy_rows the other K - 1
+                    tb.pairs[pnxt:pnxt + B, 0], tb.pairs[pnxt:pnxt + B, 1] = x0 + ar, d0 + j * B + ar
+                    pnxt += B
+                irow[:, S["DS_SR_EPSC"]] = -1
+            elif r.phi > 0.0:           # the rescale launch combines into the unconditional eps rows: the step sees a plain eps
                 gsl = slice(gnxt, gnxt + B)
                 gnxt += B
                 tb.girow[gsl, CR["DS_CR_U"]] = tb.girow[gsl, CR["DS_CR_OUT"]] = e0 + ar
@@ -401,6 +432,10 @@ class SamplingBatcher:
             g = L.CfgRescaleRowsParams(eps=eps.data_ptr(), irow=tb.at(dev, "girow"), frow=tb.at(dev, "gfrow"), gain=None,
                                        R=tb.Rg, CHW=Cc * H * W, Beps=eps.shape[0])
             L.call("ds_cfg_rescale_rows", C.byref(g), L.current_stream())
+        if tb.Rm:
+            m = L.CfgComposeRowsParams(eps=eps.data_ptr(), irow=tb.at(dev, "mirow"), frow=tb.at(dev, "mfrow"), wt=tb.at(dev, "mwt"), gain=None,
+                                       R=tb.Rm, CHW=Cc * H * W, W=W, Beps=eps.shape[0], n_wt=tb.n_wt)
+            L.call("ds_cfg_compose_rows", C.byref(m), L.current_stream())
         for name, first, n, hrow in (("ds_step_rows", 0, tb.R1, ()), ("ds_dpm_step_rows", tb.R1, tb.R - tb.R1, (tb.at(dev, "hrow"),))):
             if n == 0:
                 continue
@@ -408,6 +443,8 @@ class SamplingBatcher:
                                  frow=tb.at(dev, "frow", first), prow=tb.at(dev, "prow", first), cols=tb.at(dev, "cols") if tb.n_cols else None,
                                  R=n, C=Cc, H=H, W=W, Bx=Bu, Beps=eps.shape[0], Bout=Bu, n_cols=tb.n_cols)
             L.call(name, C.byref(p), *hrow, L.current_stream())
+        if tb.Rp:
+            L.call("ds_copy_rows", out.data_ptr(), tb.at(dev, "pairs"), tb.Rp, Cc * H * W, Bu, L.current_stream())
         del keep
         b.x = out
         done = []

@@ -1,5 +1,5 @@
 // The sampler's per-step arithmetic: the first-order (DDIM / DDPM) and the DPM-Solver++(2M) step of one call and of the batcher's row
-// tables, the Philox normal stream they draw from, the column gather of the step noise and the guidance rescale.  fp32 NCHW throughout.
+// tables, the Philox normal stream they draw from, the column gather of the step noise, the guidance rescale and the weighted multi-prompt combine.  fp32 NCHW throughout.
 // The four step kernels decode their row into one descriptor (step_row) and run one loop (step_row_loop): a row of a rows form is the
 // same bits as the call form on the same inputs because it is the same code.
 #include "common.hpp"
@@ -444,6 +444,159 @@ __global__ __launch_bounds__(CR_THREADS) void cfg_rescale_rows_kernel(const ds_c
     if (p.gain && threadIdx.x == 0) p.gain[r] = g;
 }
 
+// ------------------------------------------------------------------------------------------------ multi-prompt guidance
+// out = g e with acc = sum_k a_k(j) (c_k - u), p = u + acc, e = u + S acc and g = phi std(p) / std(e) + (1 - phi) over one row
+// (include/diffusynth_hip.h: ds_cfg_compose).  cfg_rescale_row's structure: one block of CR_THREADS per row, piece v belongs to thread
+// v % CR_THREADS in the 16-byte and in the scalar form alike, float64 sums in two passes about the mean.  The row's weight table
+// ([K][wtw], wtw in {1, W}) is staged in LDS once.  cfg_compose_kernel and cfg_compose_rows_kernel both run cfg_compose_row.
+struct cc_row {
+    const float* u; const float* c0; float* out;        // c_k (k = 1 ... K) at c0 + (k - 1) * cstride
+    long long cstride;                                  // in elements
+    int K, wtw;
+    float scale, phi;
+};
+#pragma clang fp contract(off)
+// p and e of the piece at element i0 (n of its 4 elements are inside the row); wl: the row's weight table in LDS
+__device__ __forceinline__ void cc_piece(const cc_row& a, const float* wl, int W, int i0, int n, bool vec, float (&p)[4], float (&e)[4]) {
+    float uv[4], cv[DS_CC_MAXK][4], acc[4] = {};
+    cr_load(a.u, i0, n, vec, uv);
+#pragma unroll
+    for (int k = 0; k < DS_CC_MAXK; ++k)
+        if (k < a.K) cr_load(a.c0 + k * a.cstride, i0, n, vec, cv[k]);       // (block-uniform; every load is issued before the first use)
+    const int j0 = a.wtw == 1 ? 0 : i0 % W;
+#pragma unroll
+    for (int k = 0; k < DS_CC_MAXK; ++k)
+        if (k < a.K) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                int j = 0;
+                if (a.wtw != 1) {
+                    j = j0 + q;
+                    if (j >= W) j %= W;                 // (scalar form only: a piece may cross an image row)
+                }
+                const float d = cv[k][q] - uv[q];
+                const float t = wl[k * a.wtw + j] * d;
+                acc[q] = k == 0 ? t : acc[q] + t;
+            }
+        }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        p[q] = uv[q] + acc[q];
+        const float sa = a.scale * acc[q];
+        e[q] = uv[q] + sa;
+    }
+}
+__device__ __forceinline__ float cfg_compose_row(const cc_row& a, const float* wt, float* wl, int N, int W, double (&red)[2][2][CR_WAVES]) {
+    for (int i = threadIdx.x; i < a.K * a.wtw; i += CR_THREADS) wl[i] = wt[i];
+    __syncthreads();
+    uint64_t addr = (uint64_t)a.u | (uint64_t)a.out;
+    for (int k = 0; k < a.K; ++k) addr |= (uint64_t)(a.c0 + k * a.cstride);
+    const bool vec = W % 4 == 0 && (addr & 15) == 0;    // (N % W == 0: with W % 4 == 0 every piece is whole and inside one image row)
+    const int nv = (N + 3) / 4;
+    float g = 1.0f;
+    if (a.phi != 0.f) {                                 // (block-uniform)
+        double sp = 0.0, se = 0.0;
+        for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
+            const int i0 = v * 4, n = min(4, N - i0);
+            float p[4], e[4];
+            cc_piece(a, wl, W, i0, n, vec, p, e);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) {
+                    sp += (double)p[k];
+                    se += (double)e[k];
+                }
+        }
+        cr_block_sum(sp, se, red[0]);
+        const double mp = sp / N, me = se / N;
+        double qp = 0.0, qe = 0.0;
+        for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
+            const int i0 = v * 4, n = min(4, N - i0);
+            float p[4], e[4];
+            cc_piece(a, wl, W, i0, n, vec, p, e);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) {
+                    const double dp = (double)p[k] - mp, de = (double)e[k] - me;
+                    qp += dp * dp;
+                    qe += de * de;
+                }
+        }
+        cr_block_sum(qp, qe, red[1]);
+        const double ratio = qe > 0.0 ? sqrt(qp / qe) : 1.0;          // std(e) == 0: nothing to scale
+        g = (float)((double)a.phi * ratio + (1.0 - (double)a.phi));
+    }
+    for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
+        const int i0 = v * 4, n = min(4, N - i0);
+        float p[4], e[4];
+        cc_piece(a, wl, W, i0, n, vec, p, e);
+        if (a.phi != 0.f)                               // phi == 0: the row is multiplied by nothing
+#pragma unroll
+            for (int k = 0; k < 4; ++k) e[k] = g * e[k];
+        if (vec) store_v<4>(a.out + i0, true, e);
+        else
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) a.out[i0 + k] = e[k];
+    }
+    return g;
+}
+#pragma clang fp contract(fast)
+
+// grid: one block per sample
+__global__ __launch_bounds__(CR_THREADS) void cfg_compose_kernel(const ds_cfg_compose_params p) {
+    __shared__ double red[2][2][CR_WAVES];
+    __shared__ float wl[DS_CC_MAXK * DS_CC_MAXW];
+    const size_t off = (size_t)blockIdx.x * p.CHW;
+    const cc_row a = {p.eps_u + off, p.eps_c + off, p.out + off, (long long)p.B * p.CHW, p.K, p.wt_w, p.cfg_scale, p.phi};
+    const float g = cfg_compose_row(a, p.wt, wl, p.CHW, p.W, red);
+    if (p.gain && threadIdx.x == 0) p.gain[blockIdx.x] = g;
+}
+
+// grid: one block per table row.  The table is the host's: a malformed row reads nothing (see ds_cfg_compose_rows)
+__global__ __launch_bounds__(CR_THREADS) void cfg_compose_rows_kernel(const ds_cfg_compose_rows_params p) {
+    __shared__ double red[2][2][CR_WAVES];
+    __shared__ float wl[DS_CC_MAXK * DS_CC_MAXW];
+    const int r = blockIdx.x;
+    const int32_t* ir = p.irow + (size_t)r * DS_CC_NI;
+    const float* fr = p.frow + (size_t)r * DS_CC_NF;
+    const int ur = ir[DS_CC_U], orow = ir[DS_CC_OUT], K = ir[DS_CC_K], c0 = ir[DS_CC_C0], cs = ir[DS_CC_CSTRIDE];
+    const int wo = ir[DS_CC_WT], ww = ir[DS_CC_WTW];
+    const float scale = fr[DS_CC_SCALE], phi = fr[DS_CC_PHI];
+    bool bad = ur < 0 || ur >= p.Beps || K < 1 || K > DS_CC_MAXK || c0 < 0 || c0 >= p.Beps || (ww != 1 && ww != p.W) || ww > DS_CC_MAXW ||
+               wo < 0 || !(phi >= 0.f && phi <= 1.f);
+    if (!bad) {                                         // (K and ww are small here: no overflow)
+        const long long last = (long long)c0 + (long long)(K - 1) * cs;       // the rows of c_1 ... c_K lie between c0 and last
+        bad = last < 0 || last >= p.Beps || (long long)wo + K * ww > p.n_wt;
+    }
+    float g = __builtin_nanf("");
+    if (orow >= 0 && orow < p.Beps) {                   // (block-uniform, like bad)
+        float* out = p.eps + (size_t)orow * p.CHW;
+        if (bad) {
+            for (int i = threadIdx.x; i < p.CHW; i += CR_THREADS) out[i] = g;
+        } else {
+            const cc_row a = {p.eps + (size_t)ur * p.CHW, p.eps + (size_t)c0 * p.CHW, out, (long long)cs * p.CHW, K, ww, scale, phi};
+            g = cfg_compose_row(a, p.wt + wo, wl, p.CHW, p.W, red);
+        }
+    }
+    if (p.gain && threadIdx.x == 0) p.gain[r] = g;
+}
+
+// grid (x: pieces of a row, y: pair)
+template <int V>
+__global__ __launch_bounds__(256) void copy_rows_kernel(float* buf, const int32_t* pairs, int CHW, int Bbuf) {
+    const int s = pairs[2 * blockIdx.y], d = pairs[2 * blockIdx.y + 1];
+    if (s < 0 || s >= Bbuf || d < 0 || d >= Bbuf || s == d) return;
+    const float* src = buf + (size_t)s * CHW;
+    float* dst = buf + (size_t)d * CHW;
+    const size_t nv = (size_t)CHW / V;
+    for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < nv; v += (size_t)gridDim.x * blockDim.x) {
+        float t[V];
+        load_v<V>(src + v * V, true, t);
+        store_v<V>(dst + v * V, true, t);
+    }
+}
+
 __global__ void gather_cols_kernel(const float* src, int src_w, const int32_t* cols, int out_w, float* out, size_t total) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t row = i / out_w;
@@ -545,6 +698,40 @@ extern "C" int ds_cfg_rescale_rows(const ds_cfg_rescale_rows_params* p, void* st
                p->Beps);
     hipLaunchKernelGGL(cfg_rescale_rows_kernel, dim3((unsigned)p->R), dim3(CR_THREADS), 0, reinterpret_cast<hipStream_t>(stream), *p);
     DS_CHECK_LAUNCH("cfg_rescale_rows");
+    return DS_OK;
+}
+
+extern "C" int ds_cfg_compose(const ds_cfg_compose_params* p, void* stream) {
+    DS_REQUIRE(p && p->eps_u && p->eps_c && p->wt && p->out, "cfg_compose: null pointer");
+    DS_REQUIRE(p->B > 0 && p->CHW > 0 && p->CHW <= (1 << 30) && p->W > 0 && p->CHW % p->W == 0, "cfg_compose: bad sizes (B=%d CHW=%d W=%d)", p->B,
+               p->CHW, p->W);
+    DS_REQUIRE(p->K >= 1 && p->K <= DS_CC_MAXK, "cfg_compose: K %d is not in [1, %d]", p->K, DS_CC_MAXK);
+    DS_REQUIRE(p->wt_w == 1 || (p->wt_w == p->W && p->W <= DS_CC_MAXW), "cfg_compose: wt_w %d is neither 1 nor W=%d (at most %d)", p->wt_w, p->W,
+               DS_CC_MAXW);
+    DS_REQUIRE(p->phi >= 0.f && p->phi <= 1.f, "cfg_compose: phi %g is not in [0, 1]", (double)p->phi);
+    hipLaunchKernelGGL(cfg_compose_kernel, dim3((unsigned)p->B), dim3(CR_THREADS), 0, reinterpret_cast<hipStream_t>(stream), *p);
+    DS_CHECK_LAUNCH("cfg_compose");
+    return DS_OK;
+}
+
+extern "C" int ds_cfg_compose_rows(const ds_cfg_compose_rows_params* p, void* stream) {
+    DS_REQUIRE(p && p->eps && p->irow && p->frow && p->wt, "cfg_compose_rows: null pointer");
+    DS_REQUIRE(p->R > 0 && p->CHW > 0 && p->CHW <= (1 << 30) && p->W > 0 && p->CHW % p->W == 0 && p->Beps > 0 && p->n_wt > 0,
+               "cfg_compose_rows: bad sizes (R=%d CHW=%d W=%d Beps=%d n_wt=%d)", p->R, p->CHW, p->W, p->Beps, p->n_wt);
+    hipLaunchKernelGGL(cfg_compose_rows_kernel, dim3((unsigned)p->R), dim3(CR_THREADS), 0, reinterpret_cast<hipStream_t>(stream), *p);
+    DS_CHECK_LAUNCH("cfg_compose_rows");
+    return DS_OK;
+}
+
+extern "C" int ds_copy_rows(float* buf, const int32_t* pairs, int R, int CHW, int Bbuf, void* stream) {
+    DS_REQUIRE(buf && pairs, "copy_rows: null pointer");
+    DS_REQUIRE(R > 0 && R <= 65535 && CHW > 0 && Bbuf > 0, "copy_rows: bad sizes (R=%d CHW=%d Bbuf=%d)", R, CHW, Bbuf);
+    const bool vec = CHW % 4 == 0 && ds_aligned16(buf);
+    const dim3 grid = step_grid(vec, (size_t)CHW, R);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL(copy_rows_kernel<4>, grid, dim3(256), 0, st, buf, pairs, CHW, Bbuf);
+    else hipLaunchKernelGGL(copy_rows_kernel<1>, grid, dim3(256), 0, st, buf, pairs, CHW, Bbuf);
+    DS_CHECK_LAUNCH("copy_rows");
     return DS_OK;
 }
 

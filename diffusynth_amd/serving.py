@@ -13,7 +13,25 @@ fp32 tier — and in the bf16x3 / bf16 tiers on a model pinned with ``model.pin_
 import numpy as np
 import torch
 
-from .sampler import DiffSynthSampler
+from .sampler import DiffSynthSampler, mix_weights
+
+
+def _request_mix(r, unconditional_condition):
+    """The weights of a multi-prompt request as float32 numpy, (K,) or (K, width) — None for a single-prompt request."""
+    if "conditions" not in r and "weights" not in r:
+        return None
+    if r.get("condition") is not None:
+        raise ValueError("a request carries either 'condition' or 'conditions' with 'weights', not both")
+    if r.get("conditions") is None or r.get("weights") is None:
+        raise ValueError("a multi-prompt request needs both 'conditions' (K, D) and 'weights' (K,) or (K, width)")
+    if unconditional_condition is None:
+        raise ValueError("a multi-prompt request needs an unconditional_condition (the negative-prompt embedding)")
+    w = mix_weights(r["weights"])                   # (K in 1 ... 8, finite values: the sampler's own checks)
+    K, width = r["conditions"].shape[0], int(r["width"])
+    if r["conditions"].dim() != 2 or w.shape not in ((K,), (K, width)):
+        raise ValueError("weights must be (K,) or (K, width) = (%d,) or (%d, %d) for conditions (K, D), got weights %r and conditions %r"
+                         % (K, K, width, tuple(w.shape), tuple(r["conditions"].shape)))
+    return w
 
 
 @torch.no_grad()
@@ -22,6 +40,9 @@ def sample_mixed_widths(model, requests, steps, *, timesteps=1000, height=128, c
                         guidance_rescale=0.0):
     """requests: list of dicts ``{"width": int, "condition": (label_dim,) tensor or None, "seed": int}``.
     Returns a list (request order) of final latents (4, height, width) — or of trajectories when asked.
+    Instead of ``"condition"`` a request may carry ``"conditions": (K, label_dim)`` with ``"weights": (K,)`` or ``(K, width)``: K prompts
+    guiding one sound (``DiffSynthSampler.set_condition_mix``; needs ``unconditional_condition``, ``cfg_scale == 1`` is allowed).  Such
+    a request takes 1 + K U-Net rows.  Both forms in one request, or weights that do not match K and the width, raise ``ValueError``.
 
     Each request's initial noise is drawn like a batch-1 reference call with its seed would draw it
     (``torch.manual_seed(seed)``; ``randn((1, C, H, train_width))``, on a private generator); requests of one width then share the
@@ -37,13 +58,16 @@ def sample_mixed_widths(model, requests, steps, *, timesteps=1000, height=128, c
                                   "shared bucket would make a request's result depend on its bucket mates (got %r)" % (sampler,))
     if cfg_scale != 1.0 and unconditional_condition is None:
         raise ValueError("cfg_scale != 1 needs an unconditional_condition (the negative-prompt embedding)")
+    mixes = [_request_mix(r, unconditional_condition) for r in requests]        # (every request is checked before any device work)
     from .batching import SamplingBatcher
     # one group per (width, condition present), run one after the other: every group is one U-Net batch (as many plans are built as
     # there are groups, however many widths the list holds — the engine keeps DS_MAX_PLANS), and every request a batch-1 call
     groups = {}
     for i, r in enumerate(requests):
-        groups.setdefault((int(r["width"]), r.get("condition") is None), []).append(i)
-    rows = max(len(idxs) for idxs in groups.values()) * (2 if cfg_scale != 1.0 else 1) if groups else 1
+        groups.setdefault((int(r["width"]), r.get("condition") is None and mixes[i] is None), []).append(i)
+    # U-Net rows of a request: 1 + K with a mix of K prompts, 2 under CFG, 1 otherwise
+    need = [(2 if cfg_scale != 1.0 else 1) if m is None else 1 + m.shape[0] for m in mixes]
+    rows = max(sum(need[i] for i in idxs) for idxs in groups.values()) if groups else 1
     b = SamplingBatcher(model, max_rows=rows)
     out = [None] * len(requests)
     for (width, nocond), idxs in groups.items():
@@ -52,9 +76,13 @@ def sample_mixed_widths(model, requests, steps, *, timesteps=1000, height=128, c
             s = DiffSynthSampler(timesteps, mute=True, device=device, height=height, max_batchsize=1, channels=channels,
                                  noise_device=noise_device)
             s.respace(list(np.linspace(0, timesteps - 1, steps, dtype=np.int32)) if use_timesteps is None else list(use_timesteps))
-            if cfg_scale != 1.0 or guidance_rescale != 0.0:
+            if cfg_scale != 1.0 or guidance_rescale != 0.0 or mixes[i] is not None:
                 s.activate_classifier_free_guidance(cfg_scale, unconditional_condition, guidance_rescale)
-            c = None if nocond else requests[i]["condition"].to(device).float()[None]
+            if mixes[i] is not None:
+                s.set_condition_mix(mixes[i])
+                c = requests[i]["conditions"].to(device).float()[None]
+            else:
+                c = None if nocond else requests[i]["condition"].to(device).float()[None]
             handles.append(b.submit(s, "sample", (1, channels, height, width), return_tensor=True, condition=c, sampler=sampler,
                                     seed=int(requests[i]["seed"])))
         b.run()

@@ -556,6 +556,72 @@ typedef struct {
     int32_t R, CHW, Beps;
 } ds_cfg_rescale_rows_params;
 int ds_cfg_rescale_rows(const ds_cfg_rescale_rows_params* p, void* stream);
+/* Weighted multi-prompt guidance: the classifier-free-guidance combine of one unconditional and K conditional predictions, with
+ * guidance rescale.  Per sample (one row of N = C*H*W elements, column j = i mod W):
+ *     u            the unconditional eps
+ *     c_1 ... c_K  the conditional eps, 1 <= K <= DS_CC_MAXK (8)
+ *     a_k(j)       the mixture weights: a scalar per condition, or one value per latent column (a time envelope); any finite sign or
+ *                  size, the sum is free
+ *     S, phi       the CFG scale and the guidance rescale
+ *
+ *     d_k = c_k - u
+ *     acc = a_1(j) d_1 + a_2(j) d_2 + ... + a_K(j) d_K      ascending k
+ *     p   = u + acc                                         the mixture's "conditional" prediction
+ *     e   = u + S acc
+ *     g   = phi std(p) / std(e) + (1 - phi)                 std over the row; std(e) == 0 -> ratio 1; phi == 0 -> g = 1
+ *     out = g e
+ * Every fp32 operation above is rounded on its own (no contraction into FMA); the products are summed in ascending k, starting from
+ * the first product, not from 0; the statistics are ds_cfg_rescale's (float64, two passes about the mean, a summation order that N
+ * alone decides: element i belongs to thread (i / 4) % 1024); with phi == 0 the row is multiplied by nothing (not by 1.0f).  So
+ * K = 1, a = 1, phi = 0 is ds_cfg_rescale(phi = 0) (the step kernels' combine) bit for bit, two copies of one condition at weights
+ * 0.5 / 0.5 are plain CFG's bits for that condition, and an envelope that is 1 on some columns and 0 on the others selects whole
+ * columns of the single-prompt results.  The step kernels then take `out` as a plain eps (eps_cond NULL / DS_SR_EPSC -1).
+ * eps_u [B][CHW]; eps_c [K][B][CHW], k-major (the chunks behind the first of a U-Net call on [u; c_1; ...; c_K]); wt [K][wt_w]
+ * device floats with wt_w in {1, W}: 1 = scalar weights (no column lookup), W = one weight per column (then W <= DS_CC_MAXW: the
+ * block keeps the row's table in LDS); out [B][CHW], out == eps_u is allowed (each element is read and written by the same
+ * thread); gain (may be NULL) receives g [B].  CHW % W == 0, phi in [0, 1].  One block per row; a row is moved in 16-byte pieces
+ * when W % 4 == 0 (a piece then never crosses an image row) and u, every c_k and out are 16-byte aligned, element by element
+ * otherwise, and either way a row is the same bits alone, in any batch, at any address and in either entry point. */
+#define DS_CC_MAXK 8
+#define DS_CC_MAXW 256
+typedef struct {
+    const float* eps_u; const float* eps_c; const float* wt; float* out;
+    float* gain;
+    float cfg_scale, phi;
+    int32_t B, K, CHW, W, wt_w;
+} ds_cfg_compose_params;
+int ds_cfg_compose(const ds_cfg_compose_params* p, void* stream);
+/* ds_cfg_compose over R rows that belong to different requests, inside one eps buffer of Beps rows (the U-Net output of a
+ * SamplingBatcher tick).  Row r reads u from eps[irow[r][DS_CC_U]] and c_k (k = 1 ... irow[r][DS_CC_K]) from
+ * eps[irow[r][DS_CC_C0] + (k - 1) * irow[r][DS_CC_CSTRIDE]], takes its weight table [K][irow[r][DS_CC_WTW]] at
+ * wt + irow[r][DS_CC_WT] (wt holds n_wt floats) and writes eps[irow[r][DS_CC_OUT]] (its own unconditional row is allowed, a row
+ * that another table row reads is not), with its own scale frow[r][DS_CC_SCALE] and phi frow[r][DS_CC_PHI]; gain (may be NULL)
+ * receives g [R].  Rows of eps that the table does not name are not touched.  A row that names an eps row outside [0, Beps), a K
+ * outside [1, DS_CC_MAXK], a weight table that does not fit n_wt, a DS_CC_WTW that is neither 1 nor W (or is W > DS_CC_MAXW) or a
+ * phi outside [0, 1] reads nothing: its output row is filled with NaN (and its gain is NaN); a row whose output row is out of
+ * range writes no eps.  A row is the same bits as ds_cfg_compose on the same inputs. */
+#define DS_CC_U 0
+#define DS_CC_OUT 1
+#define DS_CC_K 2
+#define DS_CC_C0 3                     /* the row of c_1 */
+#define DS_CC_CSTRIDE 4                /* the row distance from c_k to c_{k+1} */
+#define DS_CC_WT 5                     /* the offset of the row's weight table in wt */
+#define DS_CC_WTW 6                    /* 1 or W */
+#define DS_CC_NI 7
+#define DS_CC_SCALE 0                  /* frow */
+#define DS_CC_PHI 1
+#define DS_CC_NF 2
+typedef struct {
+    float* eps;
+    const int32_t* irow; const float* frow; const float* wt;
+    float* gain;
+    int32_t R, CHW, W, Beps, n_wt;
+} ds_cfg_compose_rows_params;
+int ds_cfg_compose_rows(const ds_cfg_compose_rows_params* p, void* stream);
+/* buf[pairs[r][1]] = buf[pairs[r][0]] for R (src, dst) pairs of device int32, rows of CHW floats inside buf [Bbuf][CHW] (the further
+ * copies of a multi-prompt request's state row in the next U-Net input).  A pair with a row outside [0, Bbuf), or with src == dst,
+ * is skipped.  No dst may be another pair's src: the pairs are copied in no particular order. */
+int ds_copy_rows(float* buf, const int32_t* pairs, int R, int CHW, int Bbuf, void* stream);
 /* counter-based N(0,1) generator (Philox4x32-10 + Box-Muller) for the throughput mode */
 int ds_philox_normal(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 /* column gather of the "repeat" noise layout (DiffSynthSampler.py:97-167): out[b][c][h][j] = src[b][c][h][cols[j]] */
