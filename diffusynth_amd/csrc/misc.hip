@@ -46,7 +46,9 @@ extern "C" int ds_split_planes(const float* x, void* out, long long npix, int C,
 extern "C" int ds_bounds_fetch_conv_igemm(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_conv_splitk(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_conv_halo3(ds_bounds_rec*, int);
+extern "C" int ds_bounds_fetch_conv_halo3_hp(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_conv_quad(ds_bounds_rec*, int);
+extern "C" int ds_bounds_fetch_conv_quad_split(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_conv_smalln(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_dwconv_gn(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_attn_fused(ds_bounds_rec*, int);
@@ -68,7 +70,7 @@ extern "C" int ds_bounds_report(char* buf, int n, int reset) {
                                    "stft_images", "latent_image", "pv_stft", "pv_vocode", "pv_istft", "resample_sinc", "peak_normalize", "mix_notes"};
     static const char* bnames[] = {"src0", "src1", "weights", "out", "res", "bias", "fold_t1", "fold_t2", "gn_ab", "gn_part", "stats_part",
                                    "aux0", "aux1", "aux2", "aux3"};
-    int (*fetch[])(ds_bounds_rec*, int) = {ds_bounds_fetch_conv_igemm, ds_bounds_fetch_conv_splitk, ds_bounds_fetch_conv_halo3, ds_bounds_fetch_conv_quad, ds_bounds_fetch_conv_smalln, ds_bounds_fetch_dwconv_gn,
+    int (*fetch[])(ds_bounds_rec*, int) = {ds_bounds_fetch_conv_igemm, ds_bounds_fetch_conv_splitk, ds_bounds_fetch_conv_halo3, ds_bounds_fetch_conv_halo3_hp, ds_bounds_fetch_conv_quad, ds_bounds_fetch_conv_quad_split, ds_bounds_fetch_conv_smalln, ds_bounds_fetch_dwconv_gn,
                                            ds_bounds_fetch_attn_fused, ds_bounds_fetch_attn_x3, ds_bounds_fetch_linattn, ds_bounds_fetch_conv1x1_x3, ds_bounds_fetch_conv7x7_c4, ds_bounds_fetch_convt4x4_c80, ds_bounds_fetch_conv3x3_c80, ds_bounds_fetch_conv3x3_f32_n4, ds_bounds_fetch_vq_attn,
                                            ds_bounds_fetch_ui_images, ds_bounds_fetch_arranger};
     int hits = 0, pos = 0;
