@@ -11,7 +11,9 @@ a guidance rescale (``activate_classifier_free_guidance(..., guidance_rescale=ph
 ``ds_cfg_rescale_rows`` launch per bucket in front of the step launches, written over their unconditional eps rows.  Requests whose
 sampler has a condition mix (``set_condition_mix``: K prompts per sample) occupy ``B * (1 + K)`` U-Net rows and get theirs from one
 ``ds_cfg_compose_rows`` launch per bucket beside it (a request is in exactly one of the two); one ``ds_copy_rows`` launch per bucket
-then writes the copies of their state rows that the step kernel's one duplicate does not cover.
+then writes the copies of their state rows that the step kernel's one duplicate does not cover.  An ``"edit_sample"`` request
+(``submit(dss, "edit_sample", inv, condition=c)``) is a "ddpm" request whose step noise is given: its rows read ``inv.z[k]`` as a raw
+draw of its own width through an identity column table, and it reserves no counters and draws nothing.
 
     b = SamplingBatcher(unet, max_rows=128)
     h = b.submit(dss, "inpaint_sample", shape, 0.7, guide, mask, condition=c, sampler="ddpm", use_dynamic_mask=True, seed=7)
@@ -44,7 +46,7 @@ import torch
 from . import _lib as L
 from .sampler import LOOP_PROGRAM
 
-METHODS = ("sample", "img_guided_sample", "inpaint_sample", "interpolate")
+METHODS = ("sample", "img_guided_sample", "inpaint_sample", "interpolate", "edit_sample")
 _NOISE_NONE, _NOISE_DRAW, _NOISE_PHILOX = 0, 1, 2
 
 
@@ -89,7 +91,8 @@ class _Request:
         self.scale = float(dss.CFG)
         self.phi = float(dss.guidance_rescale) if self.cfg else 0.0     # guidance rescale (applied under CFG only, as in the sampler)
         self.unet_rows = self.B * (1 + self.K)
-        self.sampler = args["sampler"]
+        self.sampler = prog.sampler
+        self.given = prog.step_noise is not None    # "edit_sample": the step noise is prog.step_noise[k], nothing is drawn
         cond = args["condition"]
         self.cond = None if cond is None else cond.to(unet_dev)
         self.uncond = None
@@ -102,7 +105,7 @@ class _Request:
         self.imgs = [prog.img]
         self.out = None
         if self.sampler == "ddpm":
-            self.draw_w, self.cols = dss._step_noise_layout(self.W)
+            self.draw_w, self.cols = (self.W, list(range(self.W))) if self.given else dss._step_noise_layout(self.W)
         self.solver = self.sampler == "dpmpp_2m"
         # the solver's history (the previous step's x0 prediction): the request's own rows, never part of the bucket's re-laid tensors
         self.hist = torch.empty(prog.shape, dtype=torch.float32, device=self.state.device) if self.solver else None
@@ -204,7 +207,7 @@ class SamplingBatcher:
         bound = inspect.signature(getattr(dss, method)).bind(LOOP_PROGRAM, *args, **kwargs)
         bound.apply_defaults()
         a = bound.arguments
-        shape = tuple(int(v) for v in a["shape"])
+        shape = tuple(int(v) for v in (a["inv"].shape if method == "edit_sample" else a["shape"]))
         if self._geometry is not None:
             assert shape[1] == self._geometry[1] and dss.channels == self._geometry[1], "shape[1] != self.channels"
             assert shape[2] == self._geometry[0] and dss.height == self._geometry[0], "shape[2] != self.height"
@@ -220,7 +223,7 @@ class SamplingBatcher:
             dss._generator = torch.Generator()
         else:
             dss._generator = torch.Generator(device=dss.device if dss.noise_device is None else dss.noise_device)
-            if a.get("seed") is None:
+            if a.get("seed") is None and method != "edit_sample":        # (an edit draws nothing: it takes no seed)
                 dss._generator.manual_seed(_seed_from_global())
         try:
             prog = getattr(dss, method)(LOOP_PROGRAM, *args, **kwargs)
@@ -401,7 +404,11 @@ class SamplingBatcher:
                 irow[:, S["DS_SR_DRAW_ROWS"]] = dss.max_batchsize
                 irow[:, S["DS_SR_DRAW_W"]] = r.draw_w
                 irow[:, S["DS_SR_COLS"]] = tb.col_tabs[tuple(r.cols)]
-                if dss.noise_device == "philox":        # the kernel computes the draw: only its counters are reserved
+                if r.given:                             # the request's own z[k], read as a draw of B rows of its width
+                    irow[:, S["DS_SR_DRAW_ROWS"]] = B
+                    irow[:, S["DS_SR_NOISE"]] = _NOISE_DRAW
+                    prow[:, S["DS_SR_DRAW"]] = prog.step_noise[k].data_ptr()
+                elif dss.noise_device == "philox":        # the kernel computes the draw: only its counters are reserved
                     irow[:, S["DS_SR_NOISE"]] = _NOISE_PHILOX
                     prow[:, S["DS_SR_SEED"]] = dss._philox_seed
                     prow[:, S["DS_SR_OFFSET"]] = dss._philox_take(int(np.prod(draw_shape)))

@@ -1,5 +1,6 @@
 // The sampler's per-step arithmetic: the first-order (DDIM / DDPM) and the DPM-Solver++(2M) step of one call and of the batcher's row
-// tables, the Philox normal stream they draw from, the column gather of the step noise, the guidance rescale and the weighted multi-prompt combine.  fp32 NCHW throughout.
+// tables, the Philox normal stream they draw from, the column gather of the step noise, the guidance rescale and the weighted multi-prompt combine,
+// and the two row kernels of DDPM inversion (q_sample at a timestep per row, the step noise that reproduces a given next state).  fp32 NCHW throughout.
 // The four step kernels decode their row into one descriptor (step_row) and run one loop (step_row_loop): a row of a rows form is the
 // same bits as the call form on the same inputs because it is the same code.
 #include "common.hpp"
@@ -100,13 +101,15 @@ __device__ __forceinline__ float predicted_x0(float x, float eps, float sigma_t,
     const float t1 = x - t0;
     return t1 / alpha_t;
 }
+// q_sample (DiffSynthSampler.py:291-293): two products, one sum
+__device__ __forceinline__ float q_sample_element(float x0, float noise, float q0, float q1) {
+    const float g0 = q0 * x0;
+    const float g1 = q1 * noise;
+    return g0 + g1;
+}
 __device__ __forceinline__ float inpaint_blend(float v, int blend_mode, float m, float g, float n0, float q0, float q1) {
     if (blend_mode) {
-        if (blend_mode == 1) {
-            const float g0 = q0 * g;
-            const float g1 = q1 * n0;
-            g = g0 + g1;
-        }
+        if (blend_mode == 1) g = q_sample_element(g, n0, q0, q1);
         const float w0 = m * g;
         const float w1 = (1.0f - m) * v;
         v = w0 + w1;
@@ -138,6 +141,17 @@ __device__ __forceinline__ float dpm_element(float x, float eps, bool cfg, float
     hist = x0;
     return inpaint_blend(v, blend_mode, m, g, n0, q0, q1);
 }
+// The step noise that makes step_element go from x to x_prev ("edit-friendly" DDPM inversion): z = (x_prev - mu) / sigma with mu the
+// first two terms of step_element's sum (cf[4] != 0: the caller's business)
+__device__ __forceinline__ float edit_noise_element(float x, float x_prev, float eps, bool cfg, float eps_c, float cfg_scale, const float (&cf)[5]) {
+    eps = guided_eps(eps, cfg, eps_c, cfg_scale);
+    const float x0 = predicted_x0(x, eps, cf[0], cf[1]);
+    const float u0 = cf[2] * x0;
+    const float u1 = cf[3] * eps;
+    const float mu = u0 + u1;
+    const float d = x_prev - mu;
+    return d / cf[4];
+}
 
 // One row (C*H*W elements of one sample) of a step launch, whichever entry point it came through.  eps_c / dup / hist may be null;
 // mask / guide / init are read only as blend says (mask: H*W floats, or C*H*W where mask_chw).  Step noise (first order only):
@@ -153,6 +167,19 @@ struct step_row {
     const float* nz;
     uint64_t seed, offset;
 };
+
+// V elements from element i0 on of the row's gathered noise (a.noise is NZ_DRAW or NZ_PHILOX; V == 4: the piece is inside one image row)
+template <int V>
+__device__ __forceinline__ void gathered_noise(const step_row& a, size_t i0, int W, uint64_t CH, const int32_t* cols, float (&nz)[V]) {
+    const int j0 = (int)(i0 % W);
+    const uint64_t e0 = ((uint64_t)a.sample * CH + i0 / W) * (uint64_t)a.draw_w;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        int col = cols[a.cols_off + j0 + k];
+        col = col < 0 ? 0 : (col >= a.draw_w ? a.draw_w - 1 : col);
+        nz[k] = a.noise == NZ_DRAW ? a.nz[e0 + (uint64_t)col] : philox_normal_at(a.seed, a.offset, e0 + (uint64_t)col);
+    }
+}
 
 // The row in pieces of V elements, grid-strided along x.  V == 4 only when x / eps / eps_c / out / dup (and a dense noise row) are
 // 16-byte aligned and a piece crosses neither a mask plane nor, for the gathered noise, an image row.  avec / hvec: the row's own blend
@@ -179,14 +206,7 @@ __device__ __forceinline__ void step_row_loop(const step_row& a, bool avec, bool
         } else if (a.noise == NZ_DENSE) {
             load_v<V>(a.nz + i0, true, nh);
         } else if (a.noise != NZ_NONE) {
-            const int j0 = (int)(i0 % W);
-            const uint64_t e0 = ((uint64_t)a.sample * CH + i0 / W) * (uint64_t)a.draw_w;
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                int col = cols[a.cols_off + j0 + k];
-                col = col < 0 ? 0 : (col >= a.draw_w ? a.draw_w - 1 : col);
-                nh[k] = a.noise == NZ_DRAW ? a.nz[e0 + (uint64_t)col] : philox_normal_at(a.seed, a.offset, e0 + (uint64_t)col);
-            }
+            gathered_noise<V>(a, i0, W, CH, cols, nh);
         }
 #pragma unroll
         for (int k = 0; k < V; ++k)
@@ -202,14 +222,14 @@ template <int V>
 __device__ __forceinline__ bool row_vec(const void* p0, const void* p1 = nullptr, const void* p2 = nullptr) {
     return V == 4 && ((((uint64_t)p0 | (uint64_t)p1 | (uint64_t)p2) & 15) == 0);
 }
-// a malformed row shows in the result
-__device__ __forceinline__ void nan_row(float* out, float* dup, size_t CHW) {
-    const float nan = __builtin_nanf("");
+__device__ __forceinline__ void fill_row(float* out, float* dup, size_t CHW, float v) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < CHW; i += (size_t)gridDim.x * blockDim.x) {
-        out[i] = nan;
-        if (dup) dup[i] = nan;
+        out[i] = v;
+        if (dup) dup[i] = v;
     }
 }
+// a malformed row shows in the result
+__device__ __forceinline__ void nan_row(float* out, float* dup, size_t CHW) { fill_row(out, dup, CHW, __builtin_nanf("")); }
 
 // Call form: sample b of ds_step_params / ds_dpm_step_params (no duplicate; the caller adds its noise or its history)
 template <class P>
@@ -321,6 +341,92 @@ __global__ __launch_bounds__(256) void dpm_step_rows_kernel(const ds_step_rows_p
     const size_t CHW = (size_t)p.C * HW;
     step_row a = {};
     if (table_row<true>(p, hrow, blockIdx.y, CHW, a)) step_row_loop<V, true>(a, row_vec<V>(a.guide, a.init, a.mask), row_vec<V>(a.hist), HW, CHW);
+}
+
+// ds_q_sample_rows: row r of the DS_QS_* tables is q_sample of one sample with its noise gathered as the step kernels gather theirs.
+// table_row's rule for a malformed row.  grid (x: pieces of a row, y: table row); V == 4 only when W % 4 == 0 and x0 / out are aligned
+template <int V>
+__global__ __launch_bounds__(256) void q_sample_rows_kernel(const ds_q_sample_rows_params p) {
+    const size_t CHW = (size_t)p.C * p.H * p.W;
+    const int32_t* ir = p.irow + (size_t)blockIdx.y * DS_QS_NI;
+    const float* fr = p.frow + (size_t)blockIdx.y * DS_QS_NF;
+    const uint64_t* pr = p.prow + (size_t)blockIdx.y * DS_QS_NP;
+    const int src = ir[DS_QS_SRC], orow = ir[DS_QS_OUT], dup = ir[DS_QS_DUP], drows = ir[DS_QS_DRAW_ROWS];
+    step_row a = {};
+    a.noise = ir[DS_QS_NOISE];
+    a.sample = ir[DS_QS_SAMPLE];
+    a.draw_w = ir[DS_QS_DRAW_W];
+    a.cols_off = ir[DS_QS_COLS];
+    a.nz = reinterpret_cast<const float*>(pr[DS_QS_DRAW]);
+    a.seed = pr[DS_QS_SEED];
+    a.offset = pr[DS_QS_OFFSET];
+    a.q0 = fr[DS_QS_Q0];
+    a.q1 = fr[DS_QS_Q1];
+    if (orow < 0 || orow >= p.Bout) return;
+    a.out = p.out + (size_t)orow * CHW;
+    a.dup = dup >= 0 && dup < p.Bout ? p.out + (size_t)dup * CHW : nullptr;
+    const bool bad = src < 0 || src >= p.Bx0 || dup >= p.Bout || (a.noise != NZ_DRAW && a.noise != NZ_PHILOX) || a.sample < 0 ||
+                     a.sample >= drows || a.draw_w <= 0 || a.cols_off < 0 || a.cols_off > p.n_cols - p.W || (a.noise == NZ_DRAW && !a.nz);
+    if (bad) {
+        nan_row(a.out, a.dup, CHW);
+        return;
+    }
+    a.x = p.x0 + (size_t)src * CHW;
+    const uint64_t CH = (uint64_t)p.C * p.H;
+    const size_t nv = CHW / V;
+    for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < nv; v += (size_t)gridDim.x * blockDim.x) {
+        const size_t i0 = v * V;
+        float xv[V], nz[V], o[V];
+        load_v<V>(a.x + i0, true, xv);
+        gathered_noise<V>(a, i0, p.W, CH, p.cols, nz);
+#pragma unroll
+        for (int k = 0; k < V; ++k) o[k] = q_sample_element(xv[k], nz[k], a.q0, a.q1);
+        store_v<V>(a.out + i0, true, o);
+        if (a.dup) store_v<V>(a.dup + i0, true, o);
+    }
+}
+
+// ds_edit_noise_rows: row r of the DS_EN_* tables.  x_prev is a row of X or the row's own address (16-byte pieces only where that
+// address allows: row_vec).  table_row's rule for a malformed row; a row with coef[4] == 0 is zeros and reads nothing.
+// grid (x: pieces of a row, y: table row); V == 4 only when W % 4 == 0 and X / eps / z are aligned
+template <int V>
+__global__ __launch_bounds__(256) void edit_noise_rows_kernel(const ds_edit_noise_rows_params p) {
+    const size_t CHW = (size_t)p.C * p.H * p.W;
+    const int32_t* ir = p.irow + (size_t)blockIdx.y * DS_EN_NI;
+    const float* fr = p.frow + (size_t)blockIdx.y * DS_EN_NF;
+    const int xr = ir[DS_EN_X], prow = ir[DS_EN_PREV], er = ir[DS_EN_EPS], ecr = ir[DS_EN_EPSC], orow = ir[DS_EN_OUT];
+    const float* prev = reinterpret_cast<const float*>(p.prow[(size_t)blockIdx.y * DS_EN_NP + DS_EN_PREVP]);
+    float cf[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) cf[k] = fr[DS_EN_COEF + k];
+    const float scale = fr[DS_EN_CFG];
+    if (orow < 0 || orow >= p.Bz) return;
+    float* out = p.z + (size_t)orow * CHW;
+    if (xr < 0 || xr >= p.Bx || prow >= p.Bx || (prow < 0 && !prev) || er < 0 || er >= p.Beps || ecr >= p.Beps) {
+        nan_row(out, nullptr, CHW);
+        return;
+    }
+    if (cf[4] == 0.f) {
+        fill_row(out, nullptr, CHW, 0.f);
+        return;
+    }
+    if (prow >= 0) prev = p.X + (size_t)prow * CHW;
+    const float* x = p.X + (size_t)xr * CHW;
+    const float* eps = p.eps + (size_t)er * CHW;
+    const float* eps_c = ecr >= 0 ? p.eps + (size_t)ecr * CHW : nullptr;
+    const bool cfg = eps_c != nullptr, pvec = row_vec<V>(prev);
+    const size_t nv = CHW / V;
+    for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < nv; v += (size_t)gridDim.x * blockDim.x) {
+        const size_t i0 = v * V;
+        float xv[V], pv[V], ev[V], ecv[V] = {}, o[V];
+        load_v<V>(x + i0, true, xv);
+        load_v<V>(prev + i0, pvec, pv);
+        load_v<V>(eps + i0, true, ev);
+        if (cfg) load_v<V>(eps_c + i0, true, ecv);
+#pragma unroll
+        for (int k = 0; k < V; ++k) o[k] = edit_noise_element(xv[k], pv[k], ev[k], cfg, ecv[k], scale, cf);
+        store_v<V>(out + i0, true, o);
+    }
 }
 #pragma clang fp contract(fast)
 
@@ -681,6 +787,35 @@ extern "C" int ds_dpm_step(const ds_dpm_step_params* p, void* stream) {
 
 extern "C" int ds_dpm_step_rows(const ds_step_rows_params* p, const uint64_t* hrow, void* stream) {
     return launch_step_rows<true>(p, hrow, stream, "dpm_step_rows");
+}
+
+extern "C" int ds_q_sample_rows(const ds_q_sample_rows_params* p, void* stream) {
+    DS_REQUIRE(p && p->x0 && p->out && p->irow && p->frow && p->prow, "q_sample_rows: null pointer");
+    DS_REQUIRE(p->R > 0 && p->R <= 65535 && p->C > 0 && p->H > 0 && p->W > 0, "q_sample_rows: bad sizes (R=%d C=%d H=%d W=%d)", p->R, p->C, p->H,
+               p->W);
+    DS_REQUIRE(p->Bx0 > 0 && p->Bout > 0 && p->n_cols >= 0, "q_sample_rows: bad row counts (Bx0=%d Bout=%d n_cols=%d)", p->Bx0, p->Bout, p->n_cols);
+    DS_REQUIRE(p->n_cols == 0 || p->cols, "q_sample_rows: n_cols > 0 needs cols");
+    const bool vec = p->W % 4 == 0 && ds_aligned16(p->x0) && ds_aligned16(p->out);
+    const dim3 grid = step_grid(vec, (size_t)p->C * p->H * p->W, p->R);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL(q_sample_rows_kernel<4>, grid, dim3(256), 0, st, *p);
+    else hipLaunchKernelGGL(q_sample_rows_kernel<1>, grid, dim3(256), 0, st, *p);
+    DS_CHECK_LAUNCH("q_sample_rows");
+    return DS_OK;
+}
+
+extern "C" int ds_edit_noise_rows(const ds_edit_noise_rows_params* p, void* stream) {
+    DS_REQUIRE(p && p->X && p->eps && p->z && p->irow && p->frow && p->prow, "edit_noise_rows: null pointer");
+    DS_REQUIRE(p->R > 0 && p->R <= 65535 && p->C > 0 && p->H > 0 && p->W > 0, "edit_noise_rows: bad sizes (R=%d C=%d H=%d W=%d)", p->R, p->C, p->H,
+               p->W);
+    DS_REQUIRE(p->Bx > 0 && p->Beps > 0 && p->Bz > 0, "edit_noise_rows: bad row counts (Bx=%d Beps=%d Bz=%d)", p->Bx, p->Beps, p->Bz);
+    const bool vec = p->W % 4 == 0 && ds_aligned16(p->X) && ds_aligned16(p->eps) && ds_aligned16(p->z);
+    const dim3 grid = step_grid(vec, (size_t)p->C * p->H * p->W, p->R);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL(edit_noise_rows_kernel<4>, grid, dim3(256), 0, st, *p);
+    else hipLaunchKernelGGL(edit_noise_rows_kernel<1>, grid, dim3(256), 0, st, *p);
+    DS_CHECK_LAUNCH("edit_noise_rows");
+    return DS_OK;
 }
 
 extern "C" int ds_cfg_rescale(const ds_cfg_rescale_params* p, void* stream) {

@@ -28,6 +28,10 @@ The default 0.0 is the reference's combine, bit for bit.
 ``set_condition_mix(weights)`` guides one sound with up to eight prompts (``condition`` then is ``(B, K, D)``): per prompt a weight, or
 a weight per latent column — a timbre that moves along the note (ds_cfg_compose).  A sampler that never sets a mix runs
 the code above unchanged.
+
+``edit_invert(model, x0, ...)`` and ``edit_sample(model, inv, condition=...)`` edit an existing sound by prompt ("edit-friendly" DDPM
+inversion; ds_q_sample_rows, ds_edit_noise_rows): the first computes the step noises under which the "ddpm" sampler
+reproduces ``x0`` under the prompt that describes it, the second runs that sampler with them under a new prompt.
 """
 import ctypes as C
 
@@ -405,10 +409,12 @@ class DiffSynthSampler:
         return out
 
     @torch.no_grad()
-    def ddim_sample(self, model, x, t, condition=None, ddim_eta=0.0, _coef=None, _blend=None):
+    def ddim_sample(self, model, x, t, condition=None, ddim_eta=0.0, _coef=None, _blend=None, _noise=None):
         mapped_t = self._timestep_map_on(t.device, t.dtype)[t]
         eps, eps_c = self._predict(model, x, mapped_t, condition)
-        if self.noise_device == "philox" and ddim_eta == 0.0 and x.is_cuda:
+        if _noise is not None:
+            step_noise = _noise                  # given (edit_sample): nothing is drawn
+        elif self.noise_device == "philox" and ddim_eta == 0.0 and x.is_cuda:
             step_noise = x                       # sigma == 0: the term vanishes, skip the generator
         else:
             step_noise, _ = self.get_deterministic_noise_tensor(x.shape[0], x.shape[3])
@@ -564,7 +570,8 @@ class DiffSynthSampler:
             if solver:
                 img = self.dpm_sample(model, img, t, condition=prog.condition, _coef=coef, _hist=hist, _blend=blend)
             else:
-                img = self.ddim_sample(model, img, t, condition=prog.condition, ddim_eta=prog.eta, _coef=coef, _blend=blend)
+                img = self.ddim_sample(model, img, t, condition=prog.condition, ddim_eta=prog.eta, _coef=coef, _blend=blend,
+                                       _noise=None if prog.step_noise is None else prog.step_noise[k])
             imgs.append(img if prog.return_tensor else img.cpu().numpy())
         return imgs, prog.initial_noise
 
@@ -596,6 +603,138 @@ class DiffSynthSampler:
                                   end_noise_level_ratio=end_noise_level_ratio, return_tensor=return_tensor,
                                   condition=condition, guide_img=guide_img, mask=mask, sampler=sampler, inpaint=True,
                                   initial_noise=initial_noise, use_dynamic_mask=use_dynamic_mask, mask_flexivity=mask_flexivity)
+
+    # ------------------------------------------------------------------ text-guided editing (DDPM inversion)
+    def _check_edit(self, shape, condition):
+        """The host-side checks the two edit entry points share (before any device work)."""
+        if self.shard is not None:
+            raise ValueError("shard: a sharded sampler (shard=) takes no edit calls")
+        if self._mix is not None:
+            self._check_mix(shape, condition)
+        elif condition is not None and int(condition.shape[0]) != int(shape[0]):
+            raise ValueError("condition: its batch is %d, the sound's is %d" % (int(condition.shape[0]), int(shape[0])))
+        elif condition is None and self.CFG != 1.0:
+            raise ValueError("condition: classifier-free guidance (CFG != 1) needs one")
+
+    @torch.no_grad()
+    def edit_invert(self, model, x0, noising_strength=1.0, condition=None, seed=None, max_rows=128):
+        """"Edit-friendly" DDPM inversion (Huberman-Spiegelglas et al., 2024; beyond the reference): the step noises that make the
+        "ddpm" sampler reproduce ``x0`` — ``(B, channels, height, W)`` on the device, used as given — under ``condition`` and the
+        guidance this sampler holds.  With ``start = int(num_timesteps * noising_strength) >= 1``:
+            X_i = q_sample(x0, i) for i = start - 1 ... 0, one noise draw per index in that order (what ``start`` calls of
+                  ``q_sample`` on this sampler draw, under every ``noise_device`` and noise strategy);
+            z_i = (X_{i-1} - mu_i) / sigma_i for i = start - 1 ... 1, mu_i the mean of the eta = 1 step from X_i; z_0 = 0.
+        The X_i do not depend on each other, so the ``(start - 1) * B`` model evaluations run as calls of at most ``max_rows`` U-Net
+        rows (a row under CFG counts twice, under a K-prompt mix 1 + K times) with a timestep per row: ds_q_sample_rows builds a
+        chunk's states, ds_edit_noise_rows takes its z.  Returns an EditNoise for ``edit_sample``."""
+        if x0.dim() != 4 or x0.shape[1] != self.channels:
+            raise ValueError("x0: shape[1] != self.channels")
+        if x0.shape[2] != self.height:
+            raise ValueError("x0: shape[2] != self.height")
+        B, Cc, H, W = (int(v) for v in x0.shape)
+        if B > self.max_batchsize:
+            raise ValueError("x0: a batch of %d is more than max_batchsize=%d" % (B, self.max_batchsize))
+        start = int(self.num_timesteps * noising_strength)
+        if not 1 <= start <= self.num_timesteps:
+            raise ValueError("noising_strength: %r gives start = %d, not in [1, %d]" % (noising_strength, start, self.num_timesteps))
+        self._check_edit(x0.shape, condition)
+        K = 0 if (self.CFG == 1.0 and self._mix is None) else (1 if self._mix is None else self._mix.shape[0])
+        per = int(max_rows) // (1 + K)                 # evaluations of one model call
+        combine = K == 1 and self._mix is None and self.guidance_rescale == 0.0        # _guided leaves the combine to the kernel
+        if per < 1:
+            raise ValueError("max_rows: %r is less than the %d U-Net rows of one evaluation" % (max_rows, 1 + K))
+        if not x0.is_cuda:
+            raise RuntimeError("diffusynth_amd.DiffSynthSampler steps on the GPU only (edit_invert); got a CPU tensor")
+        self._seed(seed)
+        dev = x0.device
+        x0 = x0.contiguous().float()
+        QS, EN = L.QS, L.EN
+        draw_w, cols = self._step_noise_layout(W)
+        draw_shape = (self.max_batchsize, Cc, H, draw_w)
+        philox = self.noise_device == "philox"
+        # draw k belongs to index start - 1 - k.  Philox: the kernel computes the draws, only their counters are reserved
+        offs = np.array([self._philox_take(int(np.prod(draw_shape))) for _ in range(start)] if philox else [], dtype=np.uint64)
+        draws, next_draw = {}, 0                        # torch generators: the raw draws the current chunk reads
+        z = torch.empty((start, B, Cc, H, W), dtype=torch.float32, device=dev)
+        z[-1].zero_()
+        q_all = np.stack([self.sqrt_alphas_cumprod[:start], self.sqrt_one_minus_alphas_cumprod[:start]], axis=1).astype(np.float32)
+        coef_all = self._step_coefficients(torch.arange(start), 1.0).numpy()          # by index
+        tmap = np.asarray(self.timestep_map, dtype=np.int64)
+        n_eval, f0, x_start = (start - 1) * B, 0, None
+        while True:
+            # rows [f0, f1) of the (index descending, sample) list are evaluated; their x_prev are B rows further on
+            f1 = min(f0 + per, n_eval)
+            n, ns = f1 - f0, min(f1 + B, start * B) - f0
+            fl = np.arange(f0, f0 + ns)
+            kk, bb = fl // B, fl % B
+            ii = start - 1 - kk
+            ar = np.arange(n, dtype=np.int32)
+            qi = np.zeros((ns, QS["DS_QS_NI"]), dtype=np.int32)
+            qp = np.zeros((ns, QS["DS_QS_NP"]), dtype=np.uint64)
+            qi[:, QS["DS_QS_SRC"]] = qi[:, QS["DS_QS_SAMPLE"]] = bb
+            qi[:, QS["DS_QS_OUT"]] = np.arange(ns)
+            qi[:, QS["DS_QS_DUP"]] = -1
+            qi[:, QS["DS_QS_DRAW_ROWS"]], qi[:, QS["DS_QS_DRAW_W"]] = self.max_batchsize, draw_w
+            if philox:
+                qi[:, QS["DS_QS_NOISE"]] = 2
+                qp[:, QS["DS_QS_SEED"]], qp[:, QS["DS_QS_OFFSET"]] = np.uint64(self._philox_seed & (2 ** 64 - 1)), offs[kk]
+            else:
+                for k in [k for k in draws if k < kk[0]]:
+                    del draws[k]
+                while next_draw <= kk[-1]:
+                    draws[next_draw] = self._randn(draw_shape, B).contiguous()
+                    next_draw += 1
+                qi[:, QS["DS_QS_NOISE"]] = 1
+                qp[:, QS["DS_QS_DRAW"]] = [draws[int(k)].data_ptr() for k in kk]
+            ei = np.zeros((n, EN["DS_EN_NI"]), dtype=np.int32)
+            ef = np.zeros((n, EN["DS_EN_NF"]), dtype=np.float32)
+            ei[:, EN["DS_EN_X"]] = ei[:, EN["DS_EN_EPS"]] = ar
+            ei[:, EN["DS_EN_PREV"]] = ar + B
+            ei[:, EN["DS_EN_EPSC"]] = (n + ar) if combine else -1
+            ei[:, EN["DS_EN_OUT"]] = f0 + ar
+            ef[:, EN["DS_EN_COEF"]:EN["DS_EN_COEF"] + 5] = coef_all[ii[:n]]
+            ef[:, EN["DS_EN_CFG"]] = float(self.CFG)
+            t_dev, b_dev, qi, qf, qp, cols_dev, ei, ef, ep = _upload(
+                dev, tmap[ii[:n]], bb[:n].astype(np.int64), qi, q_all[ii], qp, np.asarray(cols, dtype=np.int32), ei, ef,
+                np.zeros((n, EN["DS_EN_NP"]), dtype=np.uint64))
+            X = torch.empty((ns, Cc, H, W), dtype=torch.float32, device=dev)
+            p = L.QSampleRowsParams(x0=x0.data_ptr(), out=X.data_ptr(), irow=qi.data_ptr(), frow=qf.data_ptr(), prow=qp.data_ptr(),
+                                    cols=cols_dev.data_ptr(), R=ns, C=Cc, H=H, W=W, Bx0=B, Bout=ns, n_cols=len(cols))
+            L.call("ds_q_sample_rows", C.byref(p), L.current_stream())
+            if f0 == 0:
+                x_start = X[:B].clone()
+            if n:
+                eps, eps_c = self._guided(*self._predict(model, X[:n], t_dev, None if condition is None else condition[b_dev]))
+                assert (eps_c is not None) == combine
+                if combine and eps_c.data_ptr() != eps.data_ptr() + 4 * eps.numel():
+                    eps = torch.cat([eps, eps_c])       # (a model of this package returns both halves in one buffer)
+                p = L.EditNoiseRowsParams(X=X.data_ptr(), eps=eps.data_ptr(), z=z.data_ptr(), irow=ei.data_ptr(), frow=ef.data_ptr(),
+                                          prow=ep.data_ptr(), R=n, C=Cc, H=H, W=W, Bx=ns, Beps=2 * n if combine else n, Bz=start * B)
+                L.call("ds_edit_noise_rows", C.byref(p), L.current_stream())
+            f0 = f1
+            if f0 >= n_eval:
+                break
+        return EditNoise(x_start=x_start, z=z, steps=list(range(start - 1, -1, -1)), shape=(B, Cc, H, W),
+                         timestep_map=list(self.timestep_map), num_timesteps=self.num_timesteps)
+
+    @torch.no_grad()
+    def edit_sample(self, model, inv, condition=None, return_tensor=False):
+        """The edit: from ``inv.x_start`` the "ddpm" step (ds_ddim_step, eta 1) for every index of ``inv.steps`` with ``inv.z[k]`` in
+        place of the drawn noise, under ``condition`` and the guidance this sampler holds now.  Draws nothing.  Under the condition
+        and guidance of ``edit_invert`` the steps return the inverted states to rounding (the last one, whose sigma is 0, returns the
+        model's x0 prediction from X_0).  Returns
+        ``(imgs, inv.x_start)`` with ``len(inv.steps) + 1`` entries in ``imgs``, as ``p_sample_loop`` returns them."""
+        if list(inv.timestep_map) != list(self.timestep_map) or inv.num_timesteps != self.num_timesteps:
+            raise ValueError("inv: it was made on another schedule (%d timesteps, this sampler has %d)" % (inv.num_timesteps, self.num_timesteps))
+        self._check_edit(inv.shape, condition)
+        steps = list(inv.steps)
+        prog = LoopProgram(shape=tuple(inv.shape), sampler="ddpm", eta=1.0, steps=steps, n_total=len(steps), img=inv.x_start,
+                           initial_noise=inv.x_start, condition=condition, return_tensor=return_tensor, inpaint=False, step_noise=inv.z)
+        prog.coef_cpu = self._step_coefficients(torch.tensor(steps, dtype=torch.long), 1.0)
+        prog.coef_all = prog.coef_cpu.to(self.device)
+        if model is LOOP_PROGRAM:
+            return prog
+        return self._loop(model, prog)
 
     def _seed(self, seed):
         if seed is not None:
@@ -631,8 +770,35 @@ def mix_weights(weights):
     return np.ascontiguousarray(w)
 
 
+_TORCH_OF = {np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64, np.dtype(np.uint64): torch.int64,
+             np.dtype(np.float32): torch.float32}
+
+
+def _upload(dev, *arrays):
+    """One host-to-device copy of several numpy tables, each at a 16-byte boundary: their device views (uint64 as int64)."""
+    offs, o = [], 0
+    for a in arrays:
+        offs.append(o)
+        o += (a.nbytes + 15) & ~15
+    host = np.zeros(max(o, 16), dtype=np.uint8)
+    for a, off in zip(arrays, offs):
+        host[off:off + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    buf = torch.from_numpy(host).to(dev)
+    return [buf[off:off + a.nbytes].view(_TORCH_OF[a.dtype]).view(a.shape) for a, off in zip(arrays, offs)]
+
+
+class EditNoise:
+    """What ``edit_invert`` returns and ``edit_sample`` takes: ``x_start`` (B, C, H, W), the state in front of ``steps[0]``; ``z``
+    (T, B, C, H, W), the noise of step ``steps[k]`` at ``z[k]`` (``z[-1]``, the step to the clean sample, is zeros); ``steps`` (the
+    indices T - 1 ... 0), ``shape``, and the schedule it was made on (``timestep_map``, ``num_timesteps``)."""
+
+    def __init__(self, x_start, z, steps, shape, timestep_map, num_timesteps):
+        self.x_start, self.z, self.steps, self.shape = x_start, z, steps, shape
+        self.timestep_map, self.num_timesteps = timestep_map, num_timesteps
+
+
 class _LoopProgramRequest:
-    """Passed as ``model`` to an entry point (sample, img_guided_sample, inpaint_sample, interpolate), it stops the call after
+    """Passed as ``model`` to an entry point (sample, img_guided_sample, inpaint_sample, interpolate, edit_sample), it stops the call after
     p_sample_loop's prologue: the call returns its LoopProgram (diffusynth_amd.batching runs the steps)."""
 
     def __repr__(self):
@@ -646,9 +812,10 @@ class LoopProgram:
     """What p_sample_loop's prologue derives for one call: the sampler's name, the steps (timestep indices, descending), their
     coefficient rows (``coef_cpu`` [T][5] — ds_ddim_step's, or ds_dpm_step's for "dpmpp_2m", then with ``orders[k]`` in (1, 2) —
     ``q_cpu`` [T][2] for inpainting; ``coef_all`` / ``q_all`` on the device), and for inpainting the guide, the initial noise and per
-    step ``blends[k] = (mode, mask)``; ``img`` is the state before the first step."""
+    step ``blends[k] = (mode, mask)``; ``img`` is the state before the first step.  ``step_noise`` ([T] + shape, edit_sample only):
+    step k takes ``step_noise[k]`` in place of a draw."""
 
     def __init__(self, **kw):
-        self.coef_cpu = self.coef_all = self.q_cpu = self.q_all = self.guide = self.init = self.orders = None
+        self.coef_cpu = self.coef_all = self.q_cpu = self.q_all = self.guide = self.init = self.orders = self.step_noise = None
         self.blends = []
         self.__dict__.update(kw)

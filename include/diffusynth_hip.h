@@ -622,6 +622,69 @@ int ds_cfg_compose_rows(const ds_cfg_compose_rows_params* p, void* stream);
  * copies of a multi-prompt request's state row in the next U-Net input).  A pair with a row outside [0, Bbuf), or with src == dst,
  * is skipped.  No dst may be another pair's src: the pairs are copied in no particular order. */
 int ds_copy_rows(float* buf, const int32_t* pairs, int R, int CHW, int Bbuf, void* stream);
+/* q_sample (DiffSynthSampler.py:271-294) over R rows with a coefficient pair each: the noisy states of a DDPM inversion
+ * (diffusynth_amd/sampler.py: edit_invert), one launch for rows at different timesteps.  Row r writes
+ *     out[irow[r][DS_QS_OUT]] = q0 * x0[irow[r][DS_QS_SRC]] + q1 * noise          (two products, one sum: no FMA contraction)
+ * and, when irow[r][DS_QS_DUP] >= 0, a second copy to that row of out.  The noise is the step noise of ds_step_rows: element
+ * (c, h, j) is element e = ((sample * C + c) * H + h) * draw_w + cols[cols_off + j] of the row's raw draw of shape
+ * (draw_rows, C, H, draw_w) (irow DS_QS_NOISE == 1, prow DS_QS_DRAW) or of the Philox stream (seed, offset) (DS_QS_NOISE == 2, prow
+ * DS_QS_SEED / DS_QS_OFFSET), so a row is the bits of q_sample on the tensor get_deterministic_noise_tensor returns.  Rows are C*H*W
+ * fp32; x0 has Bx0 rows, out Bout, cols n_cols entries.  16-byte pieces when W % 4 == 0 and x0 / out are 16-byte aligned.  A row
+ * whose entries fall outside those bounds (or name another noise mode, or lack the draw) reads nothing: its output row, and its
+ * duplicate when that is in range, is filled with NaN; a row whose output row is out of range writes nothing. */
+#define DS_QS_SRC 0
+#define DS_QS_OUT 1
+#define DS_QS_DUP 2
+#define DS_QS_NOISE 3
+#define DS_QS_SAMPLE 4
+#define DS_QS_DRAW_ROWS 5
+#define DS_QS_DRAW_W 6
+#define DS_QS_COLS 7
+#define DS_QS_NI 8
+#define DS_QS_Q0 0                     /* frow: sqrt(acp[i]), sqrt(1 - acp[i]) */
+#define DS_QS_Q1 1
+#define DS_QS_NF 2
+#define DS_QS_DRAW 0                   /* prow */
+#define DS_QS_SEED 1
+#define DS_QS_OFFSET 2
+#define DS_QS_NP 3
+typedef struct {
+    const float* x0; float* out;
+    const int32_t* irow; const float* frow; const uint64_t* prow;
+    const int32_t* cols;
+    int32_t R, C, H, W;
+    int32_t Bx0, Bout, n_cols;
+} ds_q_sample_rows_params;
+int ds_q_sample_rows(const ds_q_sample_rows_params* p, void* stream);
+/* The step noise of "edit-friendly" DDPM inversion (Huberman-Spiegelglas et al., 2024): the z for which the eta = 1 step of
+ * ds_ddim_step goes from x to x_prev.  Row r, with coef[5] = frow[r][DS_EN_COEF ...] as ds_step_params.coef and the step kernels'
+ * guidance combine (eps_c read only when irow[r][DS_EN_EPSC] >= 0, with the scale frow[r][DS_EN_CFG]):
+ *     e  = guided eps of eps[irow[r][DS_EN_EPS]]                x^ = (x - coef[0] e) / coef[1]        x = X[irow[r][DS_EN_X]]
+ *     u0 = coef[2] x^     u1 = coef[3] e     mu = u0 + u1       d = x_prev - mu                       z = d / coef[4]
+ * every operation rounded on its own, written to z[irow[r][DS_EN_OUT]].  x_prev is X[irow[r][DS_EN_PREV]] or, when that is < 0, the
+ * C*H*W floats at the address prow[r][DS_EN_PREVP] (any 4-byte alignment: such a row is read element by element).  A row with
+ * coef[4] == 0 (the step to the clean sample) is zeros and reads nothing but its table.  X / eps / z have Bx / Beps / Bz rows of
+ * C*H*W fp32; 16-byte pieces when W % 4 == 0 and X / eps / z are 16-byte aligned.  A row that points outside those bounds, or has
+ * neither a row nor an address for x_prev, reads nothing and is filled with NaN; a row whose output row is out of range writes
+ * nothing. */
+#define DS_EN_X 0
+#define DS_EN_PREV 1
+#define DS_EN_EPS 2
+#define DS_EN_EPSC 3
+#define DS_EN_OUT 4
+#define DS_EN_NI 5
+#define DS_EN_COEF 0                   /* frow: coef[5] at 0..4 */
+#define DS_EN_CFG 5
+#define DS_EN_NF 6
+#define DS_EN_PREVP 0                  /* prow */
+#define DS_EN_NP 1
+typedef struct {
+    const float* X; const float* eps; float* z;
+    const int32_t* irow; const float* frow; const uint64_t* prow;
+    int32_t R, C, H, W;
+    int32_t Bx, Beps, Bz;
+} ds_edit_noise_rows_params;
+int ds_edit_noise_rows(const ds_edit_noise_rows_params* p, void* stream);
 /* counter-based N(0,1) generator (Philox4x32-10 + Box-Muller) for the throughput mode */
 int ds_philox_normal(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 /* column gather of the "repeat" noise layout (DiffSynthSampler.py:97-167): out[b][c][h][j] = src[b][c][h][cols[j]] */
