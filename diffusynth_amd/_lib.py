@@ -54,6 +54,8 @@ CR = _parse_defines(_HEADER_TEXT, "DS_CR_")     # ds_cfg_rescale_rows table layo
 CC = _parse_defines(_HEADER_TEXT, "DS_CC_")     # ds_cfg_compose_rows table layout, DS_CC_MAXK, DS_CC_MAXW
 QS = _parse_defines(_HEADER_TEXT, "DS_QS_")     # ds_q_sample_rows table layout
 EN = _parse_defines(_HEADER_TEXT, "DS_EN_")     # ds_edit_noise_rows table layout
+WS = _parse_defines(_HEADER_TEXT, "DS_WS_")     # ds_window_split table layout
+WM = _parse_defines(_HEADER_TEXT, "DS_WM_")     # ds_window_merge column tables, DS_WM_MAXM
 DW_FAMILY ={v: k[6:].lower() for k, v in _parse_defines(_HEADER_TEXT, "DS_DW_").items()}     # ds_dwconv_launch_choice: family code -> name
 PV = _parse_defines(_HEADER_TEXT, "DS_PV_")     # arranger signal table (field indices and row width)
 MIX_BLOCK = _parse_defines(_HEADER_TEXT, "DS_MIX_")["DS_MIX_BLOCK"]
@@ -72,6 +74,8 @@ CfgComposeParams = _STRUCTS["ds_cfg_compose_params"]
 CfgComposeRowsParams = _STRUCTS["ds_cfg_compose_rows_params"]
 QSampleRowsParams = _STRUCTS["ds_q_sample_rows_params"]
 EditNoiseRowsParams = _STRUCTS["ds_edit_noise_rows_params"]
+WindowSplitParams = _STRUCTS["ds_window_split_params"]
+WindowMergeParams = _STRUCTS["ds_window_merge_params"]
 AttnFusedParams = _STRUCTS["ds_attn_fused_params"]
 AttnX3Params = _STRUCTS["ds_attn_x3_params"]
 VqAttnParams = _STRUCTS["ds_vq_attn_params"]
@@ -142,6 +146,8 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_cfg_compose_rows": (C.c_int, [C.POINTER(CfgComposeRowsParams), _P]),
     "ds_q_sample_rows": (C.c_int, [C.POINTER(QSampleRowsParams), _P]),
     "ds_edit_noise_rows": (C.c_int, [C.POINTER(EditNoiseRowsParams), _P]),
+    "ds_window_split": (C.c_int, [C.POINTER(WindowSplitParams), _P]),
+    "ds_window_merge": (C.c_int, [C.POINTER(WindowMergeParams), _P]),
     "ds_copy_rows": (C.c_int, [_P, _P, _I, _I, _I, _P]),
     "ds_philox_normal": (C.c_int, [_P, _SZ, _U64, _U64, _P]),
     "ds_gather_cols": (C.c_int, [_P, _I, _I, _P, _I, _P, _P]),

@@ -13,7 +13,9 @@ sampler has a condition mix (``set_condition_mix``: K prompts per sample) occupy
 ``ds_cfg_compose_rows`` launch per bucket beside it (a request is in exactly one of the two); one ``ds_copy_rows`` launch per bucket
 then writes the copies of their state rows that the step kernel's one duplicate does not cover.  An ``"edit_sample"`` request
 (``submit(dss, "edit_sample", inv, condition=c)``) is a "ddpm" request whose step noise is given: its rows read ``inv.z[k]`` as a raw
-draw of its own width through an identity column table, and it reserves no counters and draws nothing.
+draw of its own width through an identity column table, and it reserves no counters and draws nothing.  On a windowed model
+(``diffusynth_amd.windowed.WindowedUnet``: a wide state is evaluated as ``rows_per_sample(width)`` windows per row) nothing of this
+changes but the accounting: a request's rows count that many times against ``max_rows``.
 
     b = SamplingBatcher(unet, max_rows=128)
     h = b.submit(dss, "inpaint_sample", shape, 0.7, guide, mask, condition=c, sampler="ddpm", use_dynamic_mask=True, seed=7)
@@ -82,7 +84,7 @@ class SamplingHandle:
 
 
 class _Request:
-    def __init__(self, dss, method, prog, args, unet_dev):
+    def __init__(self, dss, method, prog, args, unet_dev, rows_per_sample=1):
         self.dss, self.method, self.prog = dss, method, prog
         self.B, self.C, self.H, self.W = prog.shape
         self.mix = dss._mix                         # condition mix (set_condition_mix): (K,) or (K, W) float32, or None
@@ -90,7 +92,8 @@ class _Request:
         self.K = (1 if self.mix is None else self.mix.shape[0]) if self.cfg else 0      # its conditional row groups
         self.scale = float(dss.CFG)
         self.phi = float(dss.guidance_rescale) if self.cfg else 0.0     # guidance rescale (applied under CFG only, as in the sampler)
-        self.unet_rows = self.B * (1 + self.K)
+        self.batch_rows = self.B * (1 + self.K)     # its rows in the bucket's batch
+        self.unet_rows = self.batch_rows * rows_per_sample          # what the U-Net runs for them (a windowed model: a row per window)
         self.sampler = prog.sampler
         self.given = prog.step_noise is not None    # "edit_sample": the step noise is prog.step_noise[k], nothing is drawn
         cond = args["condition"]
@@ -165,7 +168,8 @@ class _Tables:
 
 
 class SamplingBatcher:
-    """See the module docstring.  ``max_rows`` bounds the U-Net rows (CFG rows counted twice, rows of a K-prompt mix 1 + K times) of all requests in flight and
+    """See the module docstring.  ``max_rows`` bounds the U-Net rows (CFG rows counted twice, rows of a K-prompt mix 1 + K times, and on a
+    windowed model — diffusynth_amd.windowed.WindowedUnet — every row ``unet.rows_per_sample(width)`` times: a row per window) of all requests in flight and
     ``max_buckets`` (default: the number of plans the U-Net's engine keeps, DS_MAX_PLANS) the buckets live at once; requests are
     admitted first in, first out at the start of a tick, and a request that does not fit waits (and holds back the ones after it).
     Not thread-safe; the U-Net is run on the current stream."""
@@ -191,7 +195,7 @@ class SamplingBatcher:
         self.ticks = 0
         self.plan_builds = 0
         self.host_seconds = 0.0
-        self.unet_batches = set()       # distinct (U-Net batch, H, W, has condition, paired) the ticks have run
+        self.unet_batches = set()       # distinct (U-Net rows, H, W, has condition, paired) the ticks have run
 
     # ------------------------------------------------------------------ submission
     def submit(self, dss, method, /, *args, **kwargs):
@@ -212,7 +216,8 @@ class SamplingBatcher:
             assert shape[1] == self._geometry[1] and dss.channels == self._geometry[1], "shape[1] != self.channels"
             assert shape[2] == self._geometry[0] and dss.height == self._geometry[0], "shape[2] != self.height"
         cfg = dss.CFG != 1.0
-        rows = shape[0] * ((2 if cfg else 1) if dss._mix is None else 1 + dss._mix.shape[0])
+        rps = self._rows_per_sample(shape[3])
+        rows = shape[0] * ((2 if cfg else 1) if dss._mix is None else 1 + dss._mix.shape[0]) * rps
         if rows > self.max_rows:
             raise ValueError("the request needs %d U-Net rows, more than max_rows=%d" % (rows, self.max_rows))
         if cfg and a["condition"] is None:
@@ -227,7 +232,7 @@ class SamplingBatcher:
                 dss._generator.manual_seed(_seed_from_global())
         try:
             prog = getattr(dss, method)(LOOP_PROGRAM, *args, **kwargs)
-            req = _Request(dss, method, prog, a, self.dev)
+            req = _Request(dss, method, prog, a, self.dev, rps)
         except BaseException:
             dss._generator = None
             raise
@@ -239,6 +244,11 @@ class SamplingBatcher:
         else:
             self._pending.append(req)
         return h
+
+    def _rows_per_sample(self, W):
+        """U-Net rows per batch row at width W: 1, or the number of windows of a windowed model (diffusynth_amd.windowed)."""
+        rps = getattr(self.unet, "rows_per_sample", None)
+        return 1 if rps is None else int(rps(W))
 
     def _retire(self, req):
         req.out = (req.imgs, req.prog.initial_noise)
@@ -302,7 +312,7 @@ class SamplingBatcher:
                 lay.append((base, base, base + r.B, base + r.B))
             else:
                 lay.append((base, base, -1, -1))
-            base += r.unet_rows
+            base += r.batch_rows
         return lay, base, False
 
     def _relayout(self, b):
@@ -432,7 +442,7 @@ class SamplingBatcher:
         ev.record()
         t_dev = dev[tb.off["tim"]:tb.off["tim"] + 8 * Bu].view(torch.int64)
         paired = b.paired and getattr(self.unet, "cfg_paired_halves", False)
-        self.unet_batches.add((Bu, H, W, b.key[2], paired))
+        self.unet_batches.add((Bu * self._rows_per_sample(W), H, W, b.key[2], paired))
         eps = self.unet(b.x, t_dev, b.cond, paired_halves=True) if paired else self.unet(b.x, t_dev, b.cond)
         out = torch.empty_like(b.x)
         if tb.Rg:

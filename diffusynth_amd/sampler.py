@@ -32,6 +32,9 @@ the code above unchanged.
 ``edit_invert(model, x0, ...)`` and ``edit_sample(model, inv, condition=...)`` edit an existing sound by prompt ("edit-friendly" DDPM
 inversion; ds_q_sample_rows, ds_edit_noise_rows): the first computes the step noises under which the "ddpm" sampler
 reproduces ``x0`` under the prompt that describes it, the second runs that sampler with them under a new prompt.
+
+Long and looping sounds need nothing here: pass ``diffusynth_amd.windowed.WindowedUnet(model)`` as the model (MultiDiffusion windows of
+the trained width) and, for ``noise_strategy="non_repeat"``, a ``max_width`` that holds the sound.
 """
 import ctypes as C
 

@@ -66,7 +66,9 @@ def sample_mixed_widths(model, requests, steps, *, timesteps=1000, height=128, c
     for i, r in enumerate(requests):
         groups.setdefault((int(r["width"]), r.get("condition") is None and mixes[i] is None), []).append(i)
     # U-Net rows of a request: 1 + K with a mix of K prompts, 2 under CFG, 1 otherwise
-    need = [(2 if cfg_scale != 1.0 else 1) if m is None else 1 + m.shape[0] for m in mixes]
+    # (times the windows of its width on a windowed model, diffusynth_amd.windowed)
+    rps = getattr(model, "rows_per_sample", lambda width: 1)
+    need = [((2 if cfg_scale != 1.0 else 1) if m is None else 1 + m.shape[0]) * int(rps(int(r["width"]))) for m, r in zip(mixes, requests)]
     rows = max(sum(need[i] for i in idxs) for idxs in groups.values()) if groups else 1
     b = SamplingBatcher(model, max_rows=rows)
     out = [None] * len(requests)

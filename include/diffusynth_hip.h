@@ -685,6 +685,46 @@ typedef struct {
     int32_t Bx, Beps, Bz;
 } ds_edit_noise_rows_params;
 int ds_edit_noise_rows(const ds_edit_noise_rows_params* p, void* stream);
+/* Windowed sampling (MultiDiffusion; diffusynth_amd/windowed.py): the windows of a wide latent as one batch of rows of
+ * the trained width.  Row i of the table rows[R][DS_WS_NI] copies, for c in [0, w),
+ *     out[rows[i][DS_WS_DST]][:, :, c] = x[rows[i][DS_WS_SRC]][:, :, (rows[i][DS_WS_OFF] + c) mod W]
+ * x: [Bx][C][H][W] fp32, out: [Bout][C][H][w] fp32, w <= W; the destination row is the caller's to choose (paired halves, chunks).  A
+ * pure copy: the bits of the source.  16-byte pieces when W % 4 == 0, w % 4 == 0 and x / out are 16-byte aligned, for the rows whose
+ * offset is a multiple of 4 (the others go element by element).  A row whose source row or offset ([0, W)) is out of range reads
+ * nothing: its destination row is filled with NaN; a row whose destination row is out of range writes nothing. */
+#define DS_WS_SRC 0
+#define DS_WS_OFF 1
+#define DS_WS_DST 2
+#define DS_WS_NI 3
+typedef struct {
+    const float* x; float* out;
+    const int32_t* rows;
+    int32_t R, C, H, W, w;
+    int32_t Bx, Bout;
+} ds_window_split_params;
+int ds_window_split(const ds_window_split_params* p, void* stream);
+/* The blend of the windows' predictions with a partition of unity.  Output row r in [0, R) of out [Bout][C][H][W] is
+ *     out[r][:, :, x] = sum_m wcoef[m][x] * eps[erow[r * n + j]][:, :, c]        j = wcol[m][x][DS_WM_WIN], c = wcol[m][x][DS_WM_COL]
+ * over the entries m = 0, 1, ... of column x up to the first with j < 0 (at most DS_WM_MAXM; ascending in j, the rest padded with
+ * j = -1): every product is rounded on its own, the first one starts the sum and the others are added in table order (no FMA
+ * contraction), so a coefficient of 1.0 returns the window's bits.  eps: [Beps][C][H][w] fp32; erow [R][n]: the eps row of window j of
+ * output row r; wcol [DS_WM_MAXM][W][DS_WM_NI] int32 and wcoef [DS_WM_MAXM][W] fp32 belong to the call, not to a row.  Only the eps
+ * rows and columns the tables name are read.  16-byte pieces when W % 4 == 0, w % 4 == 0 and eps / out / wcol / wcoef are 16-byte
+ * aligned, for the pieces whose four columns name the same windows at four adjacent source columns from a multiple of 4 on (so it
+ * is when every window offset is a multiple of 4); the others go element by element.  A row with an erow entry outside [0, Beps)
+ * reads nothing and is filled with NaN; a column entry with j >= n or c outside [0, w) makes that column NaN; rows of out from R on
+ * are not written. */
+#define DS_WM_MAXM 8
+#define DS_WM_WIN 0
+#define DS_WM_COL 1
+#define DS_WM_NI 2
+typedef struct {
+    const float* eps; float* out;
+    const int32_t* erow; const int32_t* wcol; const float* wcoef;
+    int32_t R, n, C, H, W, w;
+    int32_t Beps, Bout;
+} ds_window_merge_params;
+int ds_window_merge(const ds_window_merge_params* p, void* stream);
 /* counter-based N(0,1) generator (Philox4x32-10 + Box-Muller) for the throughput mode */
 int ds_philox_normal(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 /* column gather of the "repeat" noise layout (DiffSynthSampler.py:97-167): out[b][c][h][j] = src[b][c][h][cols[j]] */
