@@ -76,6 +76,7 @@ QSampleRowsParams = _STRUCTS["ds_q_sample_rows_params"]
 EditNoiseRowsParams = _STRUCTS["ds_edit_noise_rows_params"]
 WindowSplitParams = _STRUCTS["ds_window_split_params"]
 WindowMergeParams = _STRUCTS["ds_window_merge_params"]
+StftWindowMergeParams = _STRUCTS["ds_stft_window_merge_params"]
 AttnFusedParams = _STRUCTS["ds_attn_fused_params"]
 AttnX3Params = _STRUCTS["ds_attn_x3_params"]
 VqAttnParams = _STRUCTS["ds_vq_attn_params"]
@@ -148,6 +149,7 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_edit_noise_rows": (C.c_int, [C.POINTER(EditNoiseRowsParams), _P]),
     "ds_window_split": (C.c_int, [C.POINTER(WindowSplitParams), _P]),
     "ds_window_merge": (C.c_int, [C.POINTER(WindowMergeParams), _P]),
+    "ds_stft_window_merge": (C.c_int, [C.POINTER(StftWindowMergeParams), _P]),
     "ds_copy_rows": (C.c_int, [_P, _P, _I, _I, _I, _P]),
     "ds_philox_normal": (C.c_int, [_P, _SZ, _U64, _U64, _P]),
     "ds_gather_cols": (C.c_int, [_P, _I, _I, _P, _I, _P, _P]),
@@ -173,6 +175,7 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_convt4x4_c80": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "ds_istft_plus": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "ds_istft_ws_floats": (_SZ, [_I, _I, _I]),
+    "ds_istft_plus_loop": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "ds_stft_plus": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "ds_stft_images_ws_floats": (_SZ, [_I, _I, _I]),
     "ds_stft_images": (C.c_int, [_P, _P, C.c_longlong, _I, _I, _I, _P, _P, _P, _P]),

@@ -1,6 +1,7 @@
 // Latent -> audio tail: nearest-code vector quantiser, decoder output activations, ISTFT+ and the
 // inverse STFT (per-frame 1024-point inverse FFT in LDS, windowed overlap-add as a gather) (gfx950).
 #include "common.hpp"
+#include "stft_codec.hpp"
 
 namespace {
 
@@ -257,21 +258,9 @@ __global__ __launch_bounds__(256) void istft_frames_r4_kernel(const float* enc, 
         }
 #pragma unroll
         for (int f = 0; f < IF_FR; ++f) {
-            // mag * exp(i atan2(sin, cos)) = mag * (cos, sin) / |(cos, sin)| — no atan2f / cosf / sinf (three libm calls per bin were half of
-            // the first kernel's 168 us); atan2(0, 0) = 0 in the reference's formula: (mag, 0)
-            const float mag = expm1f(c0[f]);
-            // (the pair is first scaled by an exact power of two so that max(|cos|, |sin|) lies in [0.5, 1): c^2 + s^2 neither underflows —
-            // v_rsq_f32 returns +inf for a denormal argument, and a pair of 1e-23s used to lose its phase to n2 == 0 — nor overflows)
-            const float pm = fmaxf(fabsf(c1[f]), fabsf(c2[f]));
-            const bool z0 = !(pm > 0.f) || !(pm < 3.0e38f);               // 0 (and nothing finite): the reference's phase is 0 (resp. undefined)
-            const int pe = z0 ? 0 : __builtin_amdgcn_frexp_expf(pm);
-            const float pa = ldexpf(c1[f], -pe), pb = ldexpf(c2[f], -pe);
-            const float n2 = pa * pa + pb * pb;
-            float ri = __builtin_amdgcn_rsqf(n2);
-            ri = ri * (1.5f - 0.5f * n2 * ri * ri);
-            const float xr = z0 ? mag : mag * (pa * ri), xi = z0 ? 0.f : mag * (pb * ri);
-            buf0[f * NFFT + kk] = float2{xr, xi};
-            if (kk < F) buf0[f * NFFT + NFFT - kk] = float2{xr, -xi};
+            const float2 d = stft_plus_decode(c0[f], c1[f], c2[f]);       // (stft_codec.hpp)
+            buf0[f * NFFT + kk] = d;
+            if (kk < F) buf0[f * NFFT + NFFT - kk] = float2{d.x, -d.y};
         }
     }
     if (tid < IF_FR) buf0[tid * NFFT] = float2{0.f, 0.f};            // DC
@@ -329,6 +318,24 @@ __global__ void istft_ola_kernel(const float* frames, int T, int hop, float* aud
     audio[(size_t)b * L + s] = wss > 1.17549435e-38f ? y / wss : y;
 }
 
+// One period of a loop: the T frames lie on a circle of L = hop * T samples, and sample s sums the NFFT / hop frames that reach it, in
+// order of the position n INSIDE the frame — the same addends in the same order wherever the loop is cut, so rolling the frames rolls
+// the audio bit for bit.  T >= NFFT / hop (the launcher's): no frame reaches a sample twice.
+__global__ void istft_ola_loop_kernel(const float* frames, int T, int hop, float* audio, int L) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (s >= L) return;
+    const int pos = s + NFFT / 2;
+    float y = 0.f, wss = 0.f;
+    for (int n = pos % hop; n < NFFT; n += hop) {
+        int t = ((pos - n) / hop) % T;                  // (pos - n is a multiple of hop, in (-NFFT / 2, L + NFFT / 2))
+        if (t < 0) t += T;
+        const float w = 0.5f - 0.5f * cospif(2.0f * (float)n / (float)NFFT);
+        y += frames[((size_t)b * T + t) * NFFT + n];
+        wss += w * w;
+    }
+    audio[(size_t)b * L + s] = wss > 1.17549435e-38f ? y / wss : y;
+}
+
 // ------------------------------------------------------------------------------------------------ STFT+
 // One block per (frame, sample): gather the centred 1024-sample frame (zero or reflect padding), periodic Hann,
 // forward radix-2 FFT in LDS, then bins 1..512 -> (log1p|X|, cos arg X, sin arg X).  Columns past the signal's
@@ -378,11 +385,11 @@ __global__ __launch_bounds__(256) void stft_plus_kernel(const float* audio, int 
         __syncthreads();
     }
     for (int k = tid; k < F; k += 256) {
-        const float xr = re[k + 1], xi = im[k + 1];
-        const float mag = sqrtf(xr * xr + xi * xi);
-        e0[(size_t)k * T_out + t] = log1pf(mag);
-        e0[((size_t)F + k) * T_out + t] = mag > 0.f ? xr / mag : 1.f;
-        e0[((size_t)2 * F + k) * T_out + t] = mag > 0.f ? xi / mag : 0.f;
+        float c0, c1, c2;
+        stft_plus_encode(re[k + 1], im[k + 1], c0, c1, c2);                // (stft_codec.hpp)
+        e0[(size_t)k * T_out + t] = c0;
+        e0[((size_t)F + k) * T_out + t] = c1;
+        e0[((size_t)2 * F + k) * T_out + t] = c2;
     }
 }
 
@@ -523,5 +530,21 @@ extern "C" int ds_istft_plus(const float* enc, int B, int F, int T, int hop, flo
     const int L = hop * (T - 1);
     hipLaunchKernelGGL(istft_ola_kernel, dim3((L + 255) / 256, B), dim3(256), 0, st, ws, T, hop, audio, L);
     DS_CHECK_LAUNCH("istft_ola");
+    return DS_OK;
+}
+
+extern "C" int ds_istft_plus_loop(const float* enc, int B, int F, int T, int hop, float* ws, float* audio, void* stream) {
+    DS_REQUIRE(enc && ws && audio && B > 0 && T > 1 && hop > 0, "istft_plus_loop: bad args");
+    DS_REQUIRE(2 * F == NFFT, "istft_plus_loop: n_fft = 2*F must be %d (got F=%d)", NFFT, F);
+    DS_REQUIRE(NFFT % hop == 0, "istft_plus_loop: hop %d must divide n_fft", hop);
+    DS_REQUIRE(T >= NFFT / hop, "istft_plus_loop: a loop of %d frames is shorter than the %d frames that overlap", T, NFFT / hop);
+    DS_REQUIRE((long long)hop * T <= 0x7fffffffLL - NFFT, "istft_plus_loop: hop * T = %lld samples", (long long)hop * T);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    DS_SET_MAX_LDS(istft_frames_r4_kernel, R4_LDS, "istft_frames_r4");
+    hipLaunchKernelGGL(istft_frames_r4_kernel, dim3((T + IF_FR - 1) / IF_FR, B), dim3(256), R4_LDS, st, enc, F, T, ws);
+    DS_CHECK_LAUNCH("istft_frames");
+    const int L = hop * T;
+    hipLaunchKernelGGL(istft_ola_loop_kernel, dim3((L + 255) / 256, B), dim3(256), 0, st, ws, T, hop, audio, L);
+    DS_CHECK_LAUNCH("istft_ola_loop");
     return DS_OK;
 }

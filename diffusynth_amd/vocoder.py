@@ -19,24 +19,32 @@ from .ui_images import stft_images
 
 
 @torch.no_grad()
-def stft_representation_to_audio(enc, hop_length=256):
+def stft_representation_to_audio(enc, hop_length=256, loop=False):
     """enc: (B, 3, F, T) fp32 CUDA tensor [log1p|D|, cos, sin] (F = n_fft/2 rows, DC row implied zero)
-    -> (B, hop*(T-1)) fp32 audio."""
+    -> (B, hop*(T-1)) fp32 audio.  ``loop=True``: the frames lie on a circle (frame 0 follows frame T-1; ds_istft_plus_loop)
+    -> (B, hop*T), one period; T >= n_fft/hop."""
     if not enc.is_cuda:
         raise RuntimeError("diffusynth_amd vocoder runs on MI355X only (ds_istft_plus); no CPU fallback")
     enc = enc.float().contiguous()
     B, three, F, T = enc.shape
     assert three == 3, "expected (B, 3, F, T)"
     ws = torch.empty(L.load().ds_istft_ws_floats(B, F, T), dtype=torch.float32, device=enc.device)
-    audio = torch.empty((B, hop_length * (T - 1)), dtype=torch.float32, device=enc.device)
-    L.call("ds_istft_plus", enc.data_ptr(), B, F, T, hop_length, ws.data_ptr(), audio.data_ptr(), L.current_stream())
+    audio = torch.empty((B, hop_length * (T if loop else T - 1)), dtype=torch.float32, device=enc.device)
+    L.call("ds_istft_plus_loop" if loop else "ds_istft_plus", enc.data_ptr(), B, F, T, hop_length, ws.data_ptr(), audio.data_ptr(),
+           L.current_stream())
     return audio
+
+
+def _loops(module):
+    """A WindowedDecoder / WindowedEncoder with ``loop=True`` stands for one period of a loop: its audio is that period."""
+    return bool(getattr(module, "loop", False))
 
 
 @torch.no_grad()
 def latents_to_audio(decoder, quantized_latents):
-    """(B, 4, H, W) quantised latents -> (B, 256*(4W-1)) audio: decoder + ISTFT+ + iSTFT, all on device."""
-    return stft_representation_to_audio(decoder(quantized_latents))
+    """(B, 4, H, W) quantised latents -> (B, 256*(4W-1)) audio: decoder + ISTFT+ + iSTFT, all on device.  A decoder with ``loop=True``
+    (windowed.WindowedDecoder): (B, 256*4W), one period."""
+    return stft_representation_to_audio(decoder(quantized_latents), loop=_loops(decoder))
 
 
 def _image_lists(enc, original_amp=None):
@@ -45,8 +53,8 @@ def _image_lists(enc, original_amp=None):
     return list(spec.cpu().numpy()), list(phase.cpu().numpy())
 
 
-def _signals(enc):
-    return [s.astype(np.float64) for s in stft_representation_to_audio(enc).cpu().numpy()]
+def _signals(enc, loop=False):
+    return [s.astype(np.float64) for s in stft_representation_to_audio(enc, loop=loop).cpu().numpy()]
 
 
 def encodeBatch2GradioOutput_STFT(decoder, latent_vector_batch, resolution=(512, 256), original_STFT_batch=None):
@@ -57,14 +65,14 @@ def encodeBatch2GradioOutput_STFT(decoder, latent_vector_batch, resolution=(512,
     if isinstance(latent_vector_batch, np.ndarray):
         latent_vector_batch = torch.from_numpy(latent_vector_batch)
     rec = decoder(latent_vector_batch.to(dev))
-    signals = _signals(rec)
+    signals = _signals(rec, _loops(decoder))
     specs, phases = _image_lists(rec)
     specs_amp, phases_amp, with_amp = [], [], []
     if original_STFT_batch is not None:
         orig = torch.as_tensor(original_STFT_batch).to(dev)
         mixed = rec.clone()
         mixed[:, 0] = orig[:, 0]
-        with_amp = _signals(mixed)
+        with_amp = _signals(mixed, _loops(decoder))
         specs_amp, phases_amp = _image_lists(rec, orig)
     return specs, phases, signals, specs_amp, phases_amp, with_amp
 
@@ -97,4 +105,4 @@ def InputBatch2Encode_STFT(encoder, STFT_batch, resolution=(512, 256), quantizer
     z = encoder(x)
     q = quantizer(z)[0] if quantizer is not None else None
     specs, phases = _image_lists(x)
-    return specs, phases, _signals(x), z, q
+    return specs, phases, _signals(x, _loops(encoder)), z, q

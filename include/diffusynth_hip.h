@@ -725,6 +725,26 @@ typedef struct {
     int32_t Beps, Bout;
 } ds_window_merge_params;
 int ds_window_merge(const ds_window_merge_params* p, void* stream);
+/* Windowed decoding (diffusynth_amd/windowed.py WindowedDecoder): the blend of decoded windows, which are STFT+
+ * representations (log1p|D|, cos, sin) and so no linear space, on the complex spectrum.  encw: [Bw][3][F][w] fp32, out: [Bout][3][F][T]
+ * fp32; erow [R][n], wcol [DS_WM_MAXM][T][DS_WM_NI] and wcoef [DS_WM_MAXM][T] are ds_window_merge's tables, in frames.  Per output
+ * row r, bin k and frame x:
+ *   one entry:      the three values of that window frame, bit for bit (its coefficient is 1.0 in a plan);
+ *   two or more:    every entry is decoded as ds_istft_plus decodes (magnitude expm1, the (cos, sin) pair normalised — it need not be
+ *                   of unit length —, phase 0 for a (0, 0) or non-finite pair), z = sum_m wcoef[m][x] * (re_m, im_m) by
+ *                   ds_window_merge's rule (every product rounded on its own, the first starts the sum, the others are added in
+ *                   table order: two windows commute), and out = (log1p|z|, z / |z|), (0, 1, 0) where z is 0 as from ds_stft_plus.
+ * 16-byte pieces when T % 4 == 0, w % 4 == 0 and encw / out / wcol / wcoef are 16-byte aligned, for the pieces whose four frames
+ * name the same windows at four adjacent frames from a multiple of 4 on (so it is for a frame plan made of a latent plan); the
+ * others go element by element.  A row with an erow entry outside [0, Bw) reads nothing and is filled with NaN; an entry with j >= n or
+ * c outside [0, w) makes that frame NaN in all three channels; rows of out from R on are not written. */
+typedef struct {
+    const float* encw; float* out;
+    const int32_t* erow; const int32_t* wcol; const float* wcoef;
+    int32_t R, n, F, T, w;
+    int32_t Bw, Bout;
+} ds_stft_window_merge_params;
+int ds_stft_window_merge(const ds_stft_window_merge_params* p, void* stream);
 /* counter-based N(0,1) generator (Philox4x32-10 + Box-Muller) for the throughput mode */
 int ds_philox_normal(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 /* column gather of the "repeat" noise layout (DiffSynthSampler.py:97-167): out[b][c][h][j] = src[b][c][h][cols[j]] */
@@ -803,6 +823,11 @@ int ds_dec_final(const void* x, int B, int H, int W, int C, const float* gn_ab, 
  * n_fft = 2*F, window = periodic Hann(n_fft), center=True. */
 int ds_istft_plus(const float* enc, int B, int F, int T, int hop, float* frames_ws, float* audio, void* stream);
 size_t ds_istft_ws_floats(int B, int F, int T);
+/* One period of a loop: the T frames lie on a circle of hop*T samples (frame 0 follows frame T-1), audio [B][hop*T].  Sample s sums the
+ * n_fft/hop frames that reach it in order of the position inside the frame, n = ((s + n_fft/2) mod hop) + k*hop, and is divided by the
+ * sum of the squared window over the same positions: rolling enc by d frames rolls audio by d*hop samples bit for bit.  T >= n_fft/hop
+ * (no frame overlaps itself); workspace as for ds_istft_plus. */
+int ds_istft_plus_loop(const float* enc, int B, int F, int T, int hop, float* frames_ws, float* audio, void* stream);
 /* Audio -> STFT+ representation: librosa.stft(y, n_fft=1024, hop_length=hop, win_length=1024)
  * (call sites load_presets.py:68, sound2sound_with_text.py:85, inpaint_with_text.py:97) + tools.pad_STFT
  * (tools.py:170-182: drop the DC row, zero-pad time to T_out) + tools.encode_stft (tools.py:320-331), fused:
