@@ -1,35 +1,13 @@
 // The sampler's per-step arithmetic: the first-order (DDIM / DDPM) and the DPM-Solver++(2M) step of one call and of the batcher's row
 // tables, the Philox normal stream they draw from, the column gather of the step noise, the guidance rescale and the weighted multi-prompt combine,
 // and the two row kernels of DDPM inversion (q_sample at a timestep per row, the step noise that reproduces a given next state).  fp32 NCHW throughout.
-// The four step kernels decode their row into one descriptor (step_row) and run one loop (step_row_loop): a row of a rows form is the
-// same bits as the call form on the same inputs because it is the same code.
-#include "common.hpp"
+// Row kernels are written from the parts of row_kernels.hpp.  The four step kernels decode their row into one descriptor
+// (step_row) and run one loop (step_row_loop), and the two gain kernels run one two-pass routine (gain_row) on their piece policies: a
+// row of a rows form is the same bits as the call form on the same inputs because it is the same code.  (The gathered-noise fields are
+// still decoded and checked twice, in table_row and in q_sample_rows_kernel: see profiles/row_kernels_refactor_ab.txt.)
+#include "row_kernels.hpp"
 
 namespace {
-
-template <int V>
-__device__ __forceinline__ void load_v(const float* p, bool vec, float (&v)[V]) {
-    if constexpr (V == 4) {
-        if (vec) {
-            const float4 t = *reinterpret_cast<const float4*>(p);
-            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-            return;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < V; ++k) v[k] = p[k];
-}
-template <int V>
-__device__ __forceinline__ void store_v(float* p, bool vec, const float (&v)[V]) {
-    if constexpr (V == 4) {
-        if (vec) {
-            *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-            return;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < V; ++k) p[k] = v[k];
-}
 
 // ------------------------------------------------------------------------------------------------ Philox4x32-10
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
@@ -188,9 +166,7 @@ template <int V, bool SOLVER>
 __device__ __forceinline__ void step_row_loop(const step_row& a, bool avec, bool hvec, int HW, size_t CHW, int W = 0, uint64_t CH = 0,
                                               const int32_t* cols = nullptr) {
     const bool cfg = a.eps_c != nullptr, second = SOLVER && a.cf[4] != 0.f;
-    const size_t nv = CHW / V;
-    for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < nv; v += (size_t)gridDim.x * blockDim.x) {
-        const size_t i0 = v * V;
+    DS_FOR_PIECES(V, CHW, i0) {
         float xv[V], ev[V], ecv[V] = {}, mv[V] = {}, gv[V] = {}, n0[V] = {}, o[V];
         float nh[V] = {};                                             // step noise (first order) / history (solver)
         load_v<V>(a.x + i0, true, xv);
@@ -217,20 +193,6 @@ __device__ __forceinline__ void step_row_loop(const step_row& a, bool avec, bool
         if (SOLVER && a.hist) store_v<V>(a.hist + i0, hvec, nh);
     }
 }
-// what a row owns itself (its blend operands, its history) may be moved in 16-byte pieces: looked at per row
-template <int V>
-__device__ __forceinline__ bool row_vec(const void* p0, const void* p1 = nullptr, const void* p2 = nullptr) {
-    return V == 4 && ((((uint64_t)p0 | (uint64_t)p1 | (uint64_t)p2) & 15) == 0);
-}
-__device__ __forceinline__ void fill_row(float* out, float* dup, size_t CHW, float v) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < CHW; i += (size_t)gridDim.x * blockDim.x) {
-        out[i] = v;
-        if (dup) dup[i] = v;
-    }
-}
-// a malformed row shows in the result
-__device__ __forceinline__ void nan_row(float* out, float* dup, size_t CHW) { fill_row(out, dup, CHW, __builtin_nanf("")); }
-
 // Call form: sample b of ds_step_params / ds_dpm_step_params (no duplicate; the caller adds its noise or its history)
 template <class P>
 __device__ __forceinline__ step_row call_row(const P& p, int b, int HW, size_t CHW) {
@@ -343,8 +305,9 @@ __global__ __launch_bounds__(256) void dpm_step_rows_kernel(const ds_step_rows_p
     if (table_row<true>(p, hrow, blockIdx.y, CHW, a)) step_row_loop<V, true>(a, row_vec<V>(a.guide, a.init, a.mask), row_vec<V>(a.hist), HW, CHW);
 }
 
-// ds_q_sample_rows: row r of the DS_QS_* tables is q_sample of one sample with its noise gathered as the step kernels gather theirs.
-// table_row's rule for a malformed row.  grid (x: pieces of a row, y: table row); V == 4 only when W % 4 == 0 and x0 / out are aligned
+// ds_q_sample_rows: row r of the DS_QS_* tables is q_sample of one sample with its noise gathered as the step kernels gather theirs
+// (gathered_noise; the fields and their checks are table_row's).  table_row's rule for a malformed row.  grid (x: pieces of a row, y: table row); V == 4 only when
+// W % 4 == 0 and x0 / out are aligned
 template <int V>
 __global__ __launch_bounds__(256) void q_sample_rows_kernel(const ds_q_sample_rows_params p) {
     const size_t CHW = (size_t)p.C * p.H * p.W;
@@ -373,9 +336,7 @@ __global__ __launch_bounds__(256) void q_sample_rows_kernel(const ds_q_sample_ro
     }
     a.x = p.x0 + (size_t)src * CHW;
     const uint64_t CH = (uint64_t)p.C * p.H;
-    const size_t nv = CHW / V;
-    for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < nv; v += (size_t)gridDim.x * blockDim.x) {
-        const size_t i0 = v * V;
+    DS_FOR_PIECES(V, CHW, i0) {
         float xv[V], nz[V], o[V];
         load_v<V>(a.x + i0, true, xv);
         gathered_noise<V>(a, i0, p.W, CH, p.cols, nz);
@@ -415,9 +376,7 @@ __global__ __launch_bounds__(256) void edit_noise_rows_kernel(const ds_edit_nois
     const float* eps = p.eps + (size_t)er * CHW;
     const float* eps_c = ecr >= 0 ? p.eps + (size_t)ecr * CHW : nullptr;
     const bool cfg = eps_c != nullptr, pvec = row_vec<V>(prev);
-    const size_t nv = CHW / V;
-    for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < nv; v += (size_t)gridDim.x * blockDim.x) {
-        const size_t i0 = v * V;
+    DS_FOR_PIECES(V, CHW, i0) {
         float xv[V], pv[V], ev[V], ecv[V] = {}, o[V];
         load_v<V>(x + i0, true, xv);
         load_v<V>(prev + i0, pvec, pv);
@@ -465,59 +424,80 @@ __device__ __forceinline__ void cr_block_sum(double& a, double& b, double (&red)
     }
 }
 #pragma clang fp contract(off)
-__device__ __forceinline__ float cfg_rescale_row(const float* u, const float* c, float* out, int N, float scale, float phi,
-                                                 double (&red)[2][2][CR_WAVES]) {
-    const bool vec = N % 4 == 0 && ((((uint64_t)u | (uint64_t)c | (uint64_t)out) & 15) == 0);
+// The gain of one row and the scaled row: g = phi std(p) / std(e) + (1 - phi), out = g e, with (p, e) the row's two sequences as the
+// piece policy gives them: piece(i0, n, vec, p, e) fills the piece at element i0, of which n (1..4) elements are inside the row.
+// phi == 0: g = 1 and nothing is summed; Piece::UNIT_GAIN_MULTIPLIES says whether the store pass then still multiplies by g
+template <class Piece>
+__device__ __forceinline__ float gain_row(const Piece& piece, float* out, int N, bool vec, float phi, double (&red)[2][2][CR_WAVES]) {
     const int nv = (N + 3) / 4;
     float g = 1.0f;
     if (phi != 0.f) {                                   // (block-uniform)
-        double sc = 0.0, se = 0.0;
+        double sp = 0.0, se = 0.0;
         for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
             const int i0 = v * 4, n = min(4, N - i0);
-            float uv[4], cv[4];
-            cr_load(u, i0, n, vec, uv);
-            cr_load(c, i0, n, vec, cv);
+            float p[4], e[4];
+            piece(i0, n, vec, p, e);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (k < n) {
-                    sc += (double)cv[k];
-                    se += (double)guided_eps(uv[k], true, cv[k], scale);
+                    sp += (double)p[k];
+                    se += (double)e[k];
                 }
         }
-        cr_block_sum(sc, se, red[0]);
-        const double mc = sc / N, me = se / N;
-        double qc = 0.0, qe = 0.0;
+        cr_block_sum(sp, se, red[0]);
+        const double mp = sp / N, me = se / N;
+        double qp = 0.0, qe = 0.0;
         for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
             const int i0 = v * 4, n = min(4, N - i0);
-            float uv[4], cv[4];
-            cr_load(u, i0, n, vec, uv);
-            cr_load(c, i0, n, vec, cv);
+            float p[4], e[4];
+            piece(i0, n, vec, p, e);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (k < n) {
-                    const double dc = (double)cv[k] - mc, de = (double)guided_eps(uv[k], true, cv[k], scale) - me;
-                    qc += dc * dc;
+                    const double dp = (double)p[k] - mp, de = (double)e[k] - me;
+                    qp += dp * dp;
                     qe += de * de;
                 }
         }
-        cr_block_sum(qc, qe, red[1]);
-        const double ratio = qe > 0.0 ? sqrt(qc / qe) : 1.0;          // std(e) == 0: nothing to scale
+        cr_block_sum(qp, qe, red[1]);
+        const double ratio = qe > 0.0 ? sqrt(qp / qe) : 1.0;          // std(e) == 0: nothing to scale
         g = (float)((double)phi * ratio + (1.0 - (double)phi));
     }
     for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
         const int i0 = v * 4, n = min(4, N - i0);
-        float uv[4], cv[4], o[4];
-        cr_load(u, i0, n, vec, uv);
-        cr_load(c, i0, n, vec, cv);
+        float p[4], e[4];
+        piece(i0, n, vec, p, e);
+        if (Piece::UNIT_GAIN_MULTIPLIES || phi != 0.f)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = g * guided_eps(uv[k], true, cv[k], scale);
-        if (vec) store_v<4>(out + i0, true, o);
+            for (int k = 0; k < 4; ++k) e[k] = g * e[k];
+        if (vec) store_v<4>(out + i0, true, e);
         else
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (k < n) out[i0 + k] = o[k];
+                if (k < n) out[i0 + k] = e[k];
     }
     return g;
+}
+// guidance rescale: p = eps_c, e = guided_eps(eps_u, eps_c, s); g == 1.0f multiplies the row of phi == 0 too
+struct cr_piece {
+    const float* u; const float* c;
+    float scale;
+    static constexpr bool UNIT_GAIN_MULTIPLIES = true;
+    __device__ __forceinline__ void operator()(int i0, int n, bool vec, float (&p)[4], float (&e)[4]) const {
+        float uv[4], cv[4];
+        cr_load(u, i0, n, vec, uv);
+        cr_load(c, i0, n, vec, cv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            p[k] = cv[k];
+            e[k] = guided_eps(uv[k], true, cv[k], scale);
+        }
+    }
+};
+__device__ __forceinline__ float cfg_rescale_row(const float* u, const float* c, float* out, int N, float scale, float phi,
+                                                 double (&red)[2][2][CR_WAVES]) {
+    const bool vec = N % 4 == 0 && ((((uint64_t)u | (uint64_t)c | (uint64_t)out) & 15) == 0);
+    return gain_row(cr_piece{u, c, scale}, out, N, vec, phi, red);
 }
 #pragma clang fp contract(fast)
 
@@ -542,8 +522,7 @@ __global__ __launch_bounds__(CR_THREADS) void cfg_rescale_rows_kernel(const ds_c
     float g = __builtin_nanf("");
     if (orow >= 0 && orow < p.Beps) {                   // (block-uniform, like bad)
         float* out = p.eps + (size_t)orow * p.CHW;
-        if (bad)
-            for (int i = threadIdx.x; i < p.CHW; i += CR_THREADS) out[i] = g;
+        if (bad) nan_row(out, nullptr, p.CHW, (int)threadIdx.x, CR_THREADS);
         else
             g = cfg_rescale_row(p.eps + (size_t)ur * p.CHW, p.eps + (size_t)cr * p.CHW, out, p.CHW, scale, phi, red);
     }
@@ -592,60 +571,20 @@ __device__ __forceinline__ void cc_piece(const cc_row& a, const float* wl, int W
         e[q] = uv[q] + sa;
     }
 }
+// multi-prompt guidance: (p, e) of cc_piece; the row of phi == 0 is multiplied by nothing
+struct cc_pieces {
+    const cc_row& a; const float* wl;
+    int W;
+    static constexpr bool UNIT_GAIN_MULTIPLIES = false;
+    __device__ __forceinline__ void operator()(int i0, int n, bool vec, float (&p)[4], float (&e)[4]) const { cc_piece(a, wl, W, i0, n, vec, p, e); }
+};
 __device__ __forceinline__ float cfg_compose_row(const cc_row& a, const float* wt, float* wl, int N, int W, double (&red)[2][2][CR_WAVES]) {
     for (int i = threadIdx.x; i < a.K * a.wtw; i += CR_THREADS) wl[i] = wt[i];
     __syncthreads();
     uint64_t addr = (uint64_t)a.u | (uint64_t)a.out;
     for (int k = 0; k < a.K; ++k) addr |= (uint64_t)(a.c0 + k * a.cstride);
     const bool vec = W % 4 == 0 && (addr & 15) == 0;    // (N % W == 0: with W % 4 == 0 every piece is whole and inside one image row)
-    const int nv = (N + 3) / 4;
-    float g = 1.0f;
-    if (a.phi != 0.f) {                                 // (block-uniform)
-        double sp = 0.0, se = 0.0;
-        for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
-            const int i0 = v * 4, n = min(4, N - i0);
-            float p[4], e[4];
-            cc_piece(a, wl, W, i0, n, vec, p, e);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < n) {
-                    sp += (double)p[k];
-                    se += (double)e[k];
-                }
-        }
-        cr_block_sum(sp, se, red[0]);
-        const double mp = sp / N, me = se / N;
-        double qp = 0.0, qe = 0.0;
-        for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
-            const int i0 = v * 4, n = min(4, N - i0);
-            float p[4], e[4];
-            cc_piece(a, wl, W, i0, n, vec, p, e);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < n) {
-                    const double dp = (double)p[k] - mp, de = (double)e[k] - me;
-                    qp += dp * dp;
-                    qe += de * de;
-                }
-        }
-        cr_block_sum(qp, qe, red[1]);
-        const double ratio = qe > 0.0 ? sqrt(qp / qe) : 1.0;          // std(e) == 0: nothing to scale
-        g = (float)((double)a.phi * ratio + (1.0 - (double)a.phi));
-    }
-    for (int v = threadIdx.x; v < nv; v += CR_THREADS) {
-        const int i0 = v * 4, n = min(4, N - i0);
-        float p[4], e[4];
-        cc_piece(a, wl, W, i0, n, vec, p, e);
-        if (a.phi != 0.f)                               // phi == 0: the row is multiplied by nothing
-#pragma unroll
-            for (int k = 0; k < 4; ++k) e[k] = g * e[k];
-        if (vec) store_v<4>(a.out + i0, true, e);
-        else
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < n) a.out[i0 + k] = e[k];
-    }
-    return g;
+    return gain_row(cc_pieces{a, wl, W}, a.out, N, vec, a.phi, red);
 }
 #pragma clang fp contract(fast)
 
@@ -679,7 +618,7 @@ __global__ __launch_bounds__(CR_THREADS) void cfg_compose_rows_kernel(const ds_c
     if (orow >= 0 && orow < p.Beps) {                   // (block-uniform, like bad)
         float* out = p.eps + (size_t)orow * p.CHW;
         if (bad) {
-            for (int i = threadIdx.x; i < p.CHW; i += CR_THREADS) out[i] = g;
+            nan_row(out, nullptr, p.CHW, (int)threadIdx.x, CR_THREADS);
         } else {
             const cc_row a = {p.eps + (size_t)ur * p.CHW, p.eps + (size_t)c0 * p.CHW, out, (long long)cs * p.CHW, K, ww, scale, phi};
             g = cfg_compose_row(a, p.wt + wo, wl, p.CHW, p.W, red);
@@ -695,11 +634,10 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(float* buf, const int32_
     if (s < 0 || s >= Bbuf || d < 0 || d >= Bbuf || s == d) return;
     const float* src = buf + (size_t)s * CHW;
     float* dst = buf + (size_t)d * CHW;
-    const size_t nv = (size_t)CHW / V;
-    for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < nv; v += (size_t)gridDim.x * blockDim.x) {
+    DS_FOR_PIECES(V, CHW, i0) {
         float t[V];
-        load_v<V>(src + v * V, true, t);
-        store_v<V>(dst + v * V, true, t);
+        load_v<V>(src + i0, true, t);
+        store_v<V>(dst + i0, true, t);
     }
 }
 
@@ -720,14 +658,11 @@ int check_blend(const P* p, const char* name) {
     DS_REQUIRE(p->blend_mode != 1 || (p->init_noise && p->qcoef), "%s: blend 1 needs init_noise and qcoef", name);
     return DS_OK;
 }
-// grid (x: pieces of one row of CHW elements, y: rows) of the 16-byte (vec) or the scalar instantiation
-dim3 step_grid(bool vec, size_t CHW, int rows) { return dim3((unsigned)blocks_for(vec ? CHW / 4 : CHW, 4096), (unsigned)rows); }
-
 // both rows forms: the solver form takes hrow and no column table
 template <bool SOLVER>
 int launch_step_rows(const ds_step_rows_params* p, const uint64_t* hrow, void* stream, const char* name) {
     DS_REQUIRE(p && p->x && p->eps && p->out && p->irow && p->frow && p->prow && (!SOLVER || hrow), "%s: null pointer", name);
-    DS_REQUIRE(p->R > 0 && p->R <= 65535 && p->C > 0 && p->H > 0 && p->W > 0, "%s: bad sizes (R=%d C=%d H=%d W=%d)", name, p->R, p->C, p->H, p->W);
+    DS_REQUIRE_ROW_SIZES(name, p, R, C, H, W);
     if constexpr (SOLVER) {
         DS_REQUIRE(p->Bx > 0 && p->Beps > 0 && p->Bout > 0, "%s: bad row counts (Bx=%d Beps=%d Bout=%d)", name, p->Bx, p->Beps, p->Bout);
     } else {
@@ -736,16 +671,9 @@ int launch_step_rows(const ds_step_rows_params* p, const uint64_t* hrow, void* s
         DS_REQUIRE(p->n_cols == 0 || p->cols, "%s: n_cols > 0 needs cols", name);
     }
     const bool vec = p->W % 4 == 0 && ds_aligned16(p->x) && ds_aligned16(p->eps) && ds_aligned16(p->out);
-    const dim3 grid = step_grid(vec, (size_t)p->C * p->H * p->W, p->R);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if constexpr (SOLVER) {
-        if (vec) hipLaunchKernelGGL(dpm_step_rows_kernel<4>, grid, dim3(256), 0, st, *p, hrow);
-        else hipLaunchKernelGGL(dpm_step_rows_kernel<1>, grid, dim3(256), 0, st, *p, hrow);
-    } else {
-        if (vec) hipLaunchKernelGGL(step_rows_kernel<4>, grid, dim3(256), 0, st, *p);
-        else hipLaunchKernelGGL(step_rows_kernel<1>, grid, dim3(256), 0, st, *p);
-    }
-    DS_CHECK_LAUNCH(name);
+    const size_t CHW = (size_t)p->C * p->H * p->W;
+    if constexpr (SOLVER) DS_LAUNCH_ROWS(dpm_step_rows_kernel, name, vec, CHW, p->R, stream, *p, hrow);
+    else DS_LAUNCH_ROWS(step_rows_kernel, name, vec, CHW, p->R, stream, *p);
     return DS_OK;
 }
 
@@ -760,11 +688,7 @@ extern "C" int ds_ddim_step(const ds_step_params* p, void* stream) {
     // are looked at per row
     const bool vec = p->HW % 4 == 0 && ds_aligned16(p->x) && ds_aligned16(p->eps) && ds_aligned16(p->eps_cond) && ds_aligned16(p->noise) &&
                      ds_aligned16(p->out);
-    const dim3 grid = step_grid(vec, (size_t)p->CHW, p->B < 65535 ? p->B : 65535);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL(ddim_step_kernel<4>, grid, dim3(256), 0, st, *p);
-    else hipLaunchKernelGGL(ddim_step_kernel<1>, grid, dim3(256), 0, st, *p);
-    DS_CHECK_LAUNCH("ddim_step");
+    DS_LAUNCH_ROWS(ddim_step_kernel, "ddim_step", vec, (size_t)p->CHW, p->B < 65535 ? p->B : 65535, stream, *p);
     return DS_OK;
 }
 
@@ -772,16 +696,12 @@ extern "C" int ds_step_rows(const ds_step_rows_params* p, void* stream) { return
 
 extern "C" int ds_dpm_step(const ds_dpm_step_params* p, void* stream) {
     DS_REQUIRE(p && p->x && p->eps && p->out && p->coef, "dpm_step: null pointer");
-    DS_REQUIRE(p->B > 0 && p->B <= 65535 && p->C > 0 && p->H > 0 && p->W > 0, "dpm_step: bad sizes (B=%d C=%d H=%d W=%d)", p->B, p->C, p->H, p->W);
+    DS_REQUIRE_ROW_SIZES("dpm_step", p, B, C, H, W);
     if (const int rc = check_blend(p, "dpm_step")) return rc;
     // (NULL is 16-byte aligned: an operand that is not given does not decide the path)
     const bool vec = p->W % 4 == 0 && ds_aligned16(p->x) && ds_aligned16(p->eps) && ds_aligned16(p->eps_cond) && ds_aligned16(p->hist) &&
                      ds_aligned16(p->out) && ds_aligned16(p->guide) && ds_aligned16(p->init_noise) && ds_aligned16(p->mask);
-    const dim3 grid = step_grid(vec, (size_t)p->C * p->H * p->W, p->B);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL(dpm_step_kernel<4>, grid, dim3(256), 0, st, *p);
-    else hipLaunchKernelGGL(dpm_step_kernel<1>, grid, dim3(256), 0, st, *p);
-    DS_CHECK_LAUNCH("dpm_step");
+    DS_LAUNCH_ROWS(dpm_step_kernel, "dpm_step", vec, (size_t)p->C * p->H * p->W, p->B, stream, *p);
     return DS_OK;
 }
 
@@ -791,30 +711,20 @@ extern "C" int ds_dpm_step_rows(const ds_step_rows_params* p, const uint64_t* hr
 
 extern "C" int ds_q_sample_rows(const ds_q_sample_rows_params* p, void* stream) {
     DS_REQUIRE(p && p->x0 && p->out && p->irow && p->frow && p->prow, "q_sample_rows: null pointer");
-    DS_REQUIRE(p->R > 0 && p->R <= 65535 && p->C > 0 && p->H > 0 && p->W > 0, "q_sample_rows: bad sizes (R=%d C=%d H=%d W=%d)", p->R, p->C, p->H,
-               p->W);
+    DS_REQUIRE_ROW_SIZES("q_sample_rows", p, R, C, H, W);
     DS_REQUIRE(p->Bx0 > 0 && p->Bout > 0 && p->n_cols >= 0, "q_sample_rows: bad row counts (Bx0=%d Bout=%d n_cols=%d)", p->Bx0, p->Bout, p->n_cols);
     DS_REQUIRE(p->n_cols == 0 || p->cols, "q_sample_rows: n_cols > 0 needs cols");
     const bool vec = p->W % 4 == 0 && ds_aligned16(p->x0) && ds_aligned16(p->out);
-    const dim3 grid = step_grid(vec, (size_t)p->C * p->H * p->W, p->R);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL(q_sample_rows_kernel<4>, grid, dim3(256), 0, st, *p);
-    else hipLaunchKernelGGL(q_sample_rows_kernel<1>, grid, dim3(256), 0, st, *p);
-    DS_CHECK_LAUNCH("q_sample_rows");
+    DS_LAUNCH_ROWS(q_sample_rows_kernel, "q_sample_rows", vec, (size_t)p->C * p->H * p->W, p->R, stream, *p);
     return DS_OK;
 }
 
 extern "C" int ds_edit_noise_rows(const ds_edit_noise_rows_params* p, void* stream) {
     DS_REQUIRE(p && p->X && p->eps && p->z && p->irow && p->frow && p->prow, "edit_noise_rows: null pointer");
-    DS_REQUIRE(p->R > 0 && p->R <= 65535 && p->C > 0 && p->H > 0 && p->W > 0, "edit_noise_rows: bad sizes (R=%d C=%d H=%d W=%d)", p->R, p->C, p->H,
-               p->W);
+    DS_REQUIRE_ROW_SIZES("edit_noise_rows", p, R, C, H, W);
     DS_REQUIRE(p->Bx > 0 && p->Beps > 0 && p->Bz > 0, "edit_noise_rows: bad row counts (Bx=%d Beps=%d Bz=%d)", p->Bx, p->Beps, p->Bz);
     const bool vec = p->W % 4 == 0 && ds_aligned16(p->X) && ds_aligned16(p->eps) && ds_aligned16(p->z);
-    const dim3 grid = step_grid(vec, (size_t)p->C * p->H * p->W, p->R);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL(edit_noise_rows_kernel<4>, grid, dim3(256), 0, st, *p);
-    else hipLaunchKernelGGL(edit_noise_rows_kernel<1>, grid, dim3(256), 0, st, *p);
-    DS_CHECK_LAUNCH("edit_noise_rows");
+    DS_LAUNCH_ROWS(edit_noise_rows_kernel, "edit_noise_rows", vec, (size_t)p->C * p->H * p->W, p->R, stream, *p);
     return DS_OK;
 }
 
@@ -862,11 +772,7 @@ extern "C" int ds_copy_rows(float* buf, const int32_t* pairs, int R, int CHW, in
     DS_REQUIRE(buf && pairs, "copy_rows: null pointer");
     DS_REQUIRE(R > 0 && R <= 65535 && CHW > 0 && Bbuf > 0, "copy_rows: bad sizes (R=%d CHW=%d Bbuf=%d)", R, CHW, Bbuf);
     const bool vec = CHW % 4 == 0 && ds_aligned16(buf);
-    const dim3 grid = step_grid(vec, (size_t)CHW, R);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL(copy_rows_kernel<4>, grid, dim3(256), 0, st, buf, pairs, CHW, Bbuf);
-    else hipLaunchKernelGGL(copy_rows_kernel<1>, grid, dim3(256), 0, st, buf, pairs, CHW, Bbuf);
-    DS_CHECK_LAUNCH("copy_rows");
+    DS_LAUNCH_ROWS(copy_rows_kernel, "copy_rows", vec, (size_t)CHW, R, stream, buf, pairs, CHW, Bbuf);
     return DS_OK;
 }
 

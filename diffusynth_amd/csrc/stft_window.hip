@@ -1,10 +1,10 @@
 // Windowed decoding (diffusynth_amd/windowed.py WindowedDecoder): the blend of the decoded windows of a long or looping
 // latent, on the complex spectrum.  The windows are STFT+ representations (log1p|D|, cos, sin), which is no linear space: a frame
 // under two or more windows is decoded like istft_frames_r4_kernel decodes it (stft_codec.hpp), blended with ds_window_merge's tables
-// and rule, and encoded again; a frame under one window keeps that window's bits.  window.hip's conventions: tables are the host's, a
-// malformed row reads nothing and shows as NaN, 16-byte pieces where alignment allows and scalar ones otherwise, no LDS.
-#include "common.hpp"
+// and rule, and encoded again; a frame under one window keeps that window's bits.  A row kernel (row_kernels.hpp): the tables are
+// the host's and are read through window_tables.hpp, a malformed row reads nothing and shows as NaN, no LDS.
 #include "stft_codec.hpp"
+#include "window_tables.hpp"
 
 namespace {
 
@@ -22,15 +22,12 @@ __global__ __launch_bounds__(256) void stft_window_merge_kernel(const ds_stft_wi
     const size_t FT = (size_t)p.F * p.T, Fw = (size_t)p.F * p.w;
     float* out = p.out + (size_t)r * 3 * FT;
     const int32_t* er = p.erow + (size_t)r * p.n;
-    bool bad = false;
-    for (int j = 0; j < p.n; ++j) bad |= er[j] < 0 || er[j] >= p.Bw;              // (block-uniform)
-    if (bad) {
-        for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < 3 * FT; i += (size_t)gridDim.x * blockDim.x) out[i] = kNaN;
+    if (!window_rows_ok(er, p.n, p.Bw)) {
+        nan_row(out, nullptr, 3 * FT, blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
         return;
     }
-    const size_t nv = FT / V;
-    for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < nv; v += (size_t)gridDim.x * blockDim.x) {
-        const size_t i0 = v * V, k = i0 / p.T;
+    DS_FOR_PIECES(V, FT, i0) {
+        const size_t k = i0 / p.T;
         const int x = (int)(i0 % p.T);
         // a frame's state: cnt entries so far; with one, its three values e0 and its coefficient f0; from the second on the sum z
         int cnt[V];
@@ -41,42 +38,29 @@ __global__ __launch_bounds__(256) void stft_window_merge_kernel(const ds_stft_wi
             e0[q][0] = e0[q][1] = e0[q][2] = kNaN;       // a frame without an entry shows
         }
         for (int m = 0; m < DS_WM_MAXM; ++m) {
-            const size_t t0 = (size_t)m * p.T + x;
             int j[V], c[V];
             float f[V], e[V][3];
-            if constexpr (V == 4) {
-                const int4 a = *reinterpret_cast<const int4*>(p.wcol + t0 * DS_WM_NI);
-                const int4 b = *reinterpret_cast<const int4*>(p.wcol + (t0 + 2) * DS_WM_NI);
-                const float4 g = *reinterpret_cast<const float4*>(p.wcoef + t0);
-                j[0] = a.x; c[0] = a.y; j[1] = a.z; c[1] = a.w; j[2] = b.x; c[2] = b.y; j[3] = b.z; c[3] = b.w;
-                f[0] = g.x; f[1] = g.y; f[2] = g.z; f[3] = g.w;
-            } else {
-                j[0] = p.wcol[t0 * DS_WM_NI + DS_WM_WIN];
-                c[0] = p.wcol[t0 * DS_WM_NI + DS_WM_COL];
-                f[0] = p.wcoef[t0];
-            }
+            window_entry<V>(p.wcol, p.wcoef, (size_t)m * p.T + x, j, c, f);
             bool any = false;
 #pragma unroll
             for (int q = 0; q < V; ++q) any |= j[q] >= 0;
             if (!any) break;
-            bool one = false;
-            if constexpr (V == 4) {
-                one = j[0] >= 0 && j[0] < p.n && j[1] == j[0] && j[2] == j[0] && j[3] == j[0] && c[0] >= 0 && (c[0] & 3) == 0 && c[0] + 3 < p.w &&
-                      c[1] == c[0] + 1 && c[2] == c[0] + 2 && c[3] == c[0] + 3;
-                if (one) {
-                    const float* src = p.encw + (size_t)er[j[0]] * 3 * Fw + k * p.w + c[0];
+            const bool one = window_entry_one<V>(j, c, p.n, p.w);
+            if (one) {
+                const float* src = p.encw + (size_t)er[j[0]] * 3 * Fw + k * p.w + c[0];
 #pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) {
-                        const float4 t = *reinterpret_cast<const float4*>(src + ch * Fw);
-                        e[0][ch] = t.x; e[1][ch] = t.y; e[2][ch] = t.z; e[3][ch] = t.w;
-                    }
+                for (int ch = 0; ch < 3; ++ch) {
+                    float s4[V];
+                    load_v<V>(src + ch * Fw, true, s4);
+#pragma unroll
+                    for (int q = 0; q < V; ++q) e[q][ch] = s4[q];
                 }
             }
 #pragma unroll
             for (int q = 0; q < V; ++q) {
                 if (j[q] < 0) continue;                 // (the frame's entries are over)
                 if (!one) {
-                    const bool ok = j[q] < p.n && c[q] >= 0 && c[q] < p.w;        // (a malformed entry reads nothing)
+                    const bool ok = window_entry_ok(j[q], c[q], p.n, p.w);        // (a malformed entry reads nothing)
                     const float* src = p.encw + (ok ? (size_t)er[j[q]] * 3 * Fw + k * p.w + c[q] : 0);
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) e[q][ch] = ok ? src[ch * Fw] : kNaN;
@@ -109,13 +93,7 @@ __global__ __launch_bounds__(256) void stft_window_merge_kernel(const ds_stft_wi
             }
         }
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            if constexpr (V == 4) {
-                *reinterpret_cast<float4*>(out + ch * FT + i0) = make_float4(o[ch][0], o[ch][1], o[ch][2], o[ch][3]);
-            } else {
-                out[ch * FT + i0] = o[ch][0];
-            }
-        }
+        for (int ch = 0; ch < 3; ++ch) store_v<V>(out + ch * FT + i0, true, o[ch]);
     }
 }
 #pragma clang fp contract(fast)
@@ -124,16 +102,11 @@ __global__ __launch_bounds__(256) void stft_window_merge_kernel(const ds_stft_wi
 
 extern "C" int ds_stft_window_merge(const ds_stft_window_merge_params* p, void* stream) {
     DS_REQUIRE(p && p->encw && p->out && p->erow && p->wcol && p->wcoef, "stft_window_merge: null pointer");
-    DS_REQUIRE(p->R > 0 && p->R <= 65535 && p->n > 0 && p->F > 0 && p->T > 0 && p->w > 0, "stft_window_merge: bad sizes (R=%d n=%d F=%d T=%d w=%d)",
-               p->R, p->n, p->F, p->T, p->w);
+    DS_REQUIRE_ROW_SIZES("stft_window_merge", p, R, n, F, T);
+    DS_REQUIRE(p->w > 0, "stft_window_merge: bad sizes (w=%d)", p->w);
     DS_REQUIRE(p->Bw > 0 && p->Bout >= p->R, "stft_window_merge: bad row counts (Bw=%d Bout=%d R=%d)", p->Bw, p->Bout, p->R);
     const bool vec = p->T % 4 == 0 && p->w % 4 == 0 && ds_aligned16(p->encw) && ds_aligned16(p->out) && ds_aligned16(p->wcol) &&
                      ds_aligned16(p->wcoef);
-    const size_t n = (size_t)p->F * p->T;
-    const dim3 grid((unsigned)blocks_for(vec ? n / 4 : n, 4096), (unsigned)p->R);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL(stft_window_merge_kernel<4>, grid, dim3(256), 0, st, *p);
-    else hipLaunchKernelGGL(stft_window_merge_kernel<1>, grid, dim3(256), 0, st, *p);
-    DS_CHECK_LAUNCH("stft_window_merge");
+    DS_LAUNCH_ROWS(stft_window_merge_kernel, "stft_window_merge", vec, (size_t)p->F * p->T, p->R, stream, *p);
     return DS_OK;
 }

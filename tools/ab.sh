@@ -11,6 +11,7 @@
 #           dw     dw_microbench.py over the eleven depthwise layer shapes (-a e.g. "--dtype fp32split")
 #           attn   attn_microbench.py over the four attention levels (-a e.g. "--batch 128 --iters 20")
 #           small  the small-batch workloads: BASELINE configs[1] (batch 16) and batch 1 (bench.py --workload config2 / config1)
+#           rows   row_kernels_bench.py: device time per launch of the sampler-step, window and STFT-blend kernels (-a e.g. "--reps 100")
 # Rounds are interleaved (A B A B), so drift of the box shows up as disagreement between rounds.
 # The first command that exits non-zero (a fault, a time limit, a result line that does not parse) ends the script with ITS status (the
 # first failing stage of the pipeline: 124 / 134 / 139 of the measured program, not the 1 of the parser that then got no line):
@@ -24,7 +25,7 @@ fail() {      # $1 = variant, rest = the pipeline's PIPESTATUS
 MODE=bench; R=2; EXTRA=""
 while getopts "m:r:a:" o; do case $o in m) MODE=$OPTARG;; r) R=$OPTARG;; a) EXTRA=$OPTARG;; *) exit 2;; esac; done
 shift $((OPTIND - 1))
-[ $# -ge 1 ] || { sed -n 2,14p "$0"; exit 2; }
+[ $# -ge 1 ] || { sed -n 2,15p "$0"; exit 2; }
 JSON_LINE='import json,sys
 d=json.loads(sys.stdin.read()); r=d.get("roofline") or {}
 print("%.1f steps/s  %.3f ms/step" % (d["value"], d["ms_per_step"]) + ("  dominant kernel %.1f us, frac %.4f" % (r["avg_launch_us"], r["frac"]) if r else ""))'
@@ -55,6 +56,8 @@ for r in $(seq 1 $R); do
     attn)
       for L in $ATTN_LAYERS; do IFS=: read c n <<< "$L"; for v in "$@"; do printf "%-44s " "$v"
         run_variant "$v" timeout -k 10 120 python tools/attn_microbench.py --c $c --n $n --batch 128 --iters 20 $EXTRA 2>&1 | tail -1; fail "$v" "${PIPESTATUS[@]}"; done; done;;
+    rows)
+      for v in "$@"; do run_variant "$v" timeout -k 10 120 python tools/row_kernels_bench.py $EXTRA 2>&1 | grep "^rows " | sed "s|^rows|$(printf '%-44s' "$v")|"; fail "$v" "${PIPESTATUS[@]}"; done;;
     *) echo "unknown mode $MODE"; exit 2;;
   esac
 done

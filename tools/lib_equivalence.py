@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Bit equality of two builds of the library on one device: python tools/lib_equivalence.py --family attn_bf16 PARENT.so [NEW.so] [-o FILE]
+"""Bit equality of two builds of the library on one device: python tools/lib_equivalence.py --family FAMILY PARENT.so [NEW.so] [-o FILE]
 
 One fresh child process per library (DS_LIB=<file name under diffusynth_amd/>) runs the family's cases on the same synthetic inputs and
 prints the sha256 of every buffer the entry points write; this process (which never opens the device) lists them, one line per case:
@@ -76,7 +76,256 @@ def attn_bf16_cases():
         yield f"vq C={dim} HxW={H}x{W} B={B} wnin={int(skip)}", dict(part=part, ctx=cx, wfold=wfold, y=y, stats_ws=ws)
 
 
-FAMILIES = {"attn_bf16": attn_bf16_cases}
+def row_kernels_cases():
+    """Every entry point of sampler_step.hip, window.hip and stft_window.hip at the smallest shapes where they can go wrong: both forms
+    (16-byte / scalar, by size and by address), duplicates, and one malformed row of every class.  Output buffers start from a fixed
+    pattern, so a row that must not be written shows in the digest."""
+    import numpy as np
+    import torch
+    from diffusynth_amd import _lib as L
+    from diffusynth_amd.windowed import _Layout, window_plan
+    st = L.current_stream()
+    SR, QS, EN, CR, CC, WM = L.SR, L.QS, L.EN, L.CR, L.CC, L.WM
+    keep = []                                             # the device tables of a launch live until the case has been hashed
+
+    def dev(t, off=False):
+        """t on the device; off: one element behind an allocation's start (4 bytes off every 16-byte boundary)."""
+        t = t.contiguous()
+        if not off:
+            d = t.cuda()
+        else:
+            flat = torch.zeros(t.numel() + 1, dtype=t.dtype, device="cuda")
+            flat[1:] = t.reshape(-1).cuda()
+            d = flat[1:].view(t.shape)
+        keep.append(d)
+        return d
+
+    def pat(*shape):
+        n = int(np.prod(shape))
+        return ((torch.arange(n, dtype=torch.float32) % 97) * 0.5 - 7.0).reshape(shape)
+
+    def coefs(g, n, last=True):
+        c = torch.rand(n, 5, generator=g) + 0.25
+        if not last:
+            c[:, 4] = 0
+        return c
+
+    for (Cc, H, W), off in (((4, 8, 20), False), ((4, 8, 64), False), ((3, 5, 7), False), ((4, 8, 20), True)):
+        B, HW, CHW = 3, H * W, Cc * H * W
+        tag = "CxHxW=%dx%dx%d%s" % (Cc, H, W, " +4B" if off else "")
+        g = torch.Generator().manual_seed(31 * CHW + int(off))
+        rnd = lambda *s: _rand(g, *s)                                                         # noqa: E731
+        x, eps, epsc, noise = (dev(rnd(B, Cc, H, W), off) for _ in range(4))
+        guide, init = dev(rnd(B, Cc, H, W), off), dev(rnd(B, Cc, H, W), off)
+        mask1, maskc = dev((torch.rand(B, 1, H, W, generator=g) > 0.5).float(), off), dev((torch.rand(B, Cc, H, W, generator=g) > 0.5).float(), off)
+        cf, cf1, qc = dev(coefs(g, B)), dev(coefs(g, B, last=False)), dev(torch.rand(B, 2, generator=g) + 0.1)
+
+        # ---- call forms of the step kernels
+        for cfg, (blend, mask) in itertools.product((False, True), ((0, None), (1, mask1), (1, maskc), (2, mask1), (2, maskc))):
+            out = dev(pat(B, Cc, H, W), off)
+            p = L.StepParams(x=x.data_ptr(), eps=eps.data_ptr(), eps_cond=epsc.data_ptr() if cfg else None, noise=noise.data_ptr(),
+                             out=out.data_ptr(), coef=cf.data_ptr(), cfg_scale=3.5, blend_mode=blend, B=B, CHW=CHW, HW=HW)
+            if blend:
+                p.guide, p.init_noise, p.mask, p.qcoef, p.mask_chw = guide.data_ptr(), init.data_ptr(), mask.data_ptr(), qc.data_ptr(), int(mask is maskc)
+            L.call("ds_ddim_step", C.byref(p), st)
+            yield "ddim_step %s cfg=%d blend=%d mask=%s" % (tag, cfg, blend, "-" if mask is None else "chw" if mask is maskc else "hw"), dict(out=out)
+        for second, cfg, (blend, mask) in itertools.product((False, True), (False, True), ((0, None), (1, maskc), (2, mask1))):
+            out, hist = dev(pat(B, Cc, H, W), off), dev(rnd(B, Cc, H, W), off)
+            p = L.DpmStepParams(x=x.data_ptr(), eps=eps.data_ptr(), eps_cond=epsc.data_ptr() if cfg else None, hist=hist.data_ptr(),
+                                out=out.data_ptr(), coef=(cf if second else cf1).data_ptr(), cfg_scale=3.5, blend_mode=blend, B=B, C=Cc, H=H, W=W)
+            if blend:
+                p.guide, p.init_noise, p.mask, p.qcoef, p.mask_chw = guide.data_ptr(), init.data_ptr(), mask.data_ptr(), qc.data_ptr(), int(mask is maskc)
+            L.call("ds_dpm_step", C.byref(p), st)
+            yield "dpm_step %s order=%d cfg=%d blend=%d" % (tag, 1 + second, cfg, blend), dict(out=out, hist=hist)
+
+        # ---- rows forms: x of 4 rows, eps of 6, out of 9 (row 8 is never named); a draw of 2 x C x H x (W + 3) behind a repeat column table
+        draw_w, n_cols = W + 3, 2 * W
+        xs, es, draw = dev(rnd(4, Cc, H, W), off), dev(rnd(6, Cc, H, W), off), dev(rnd(2, Cc, H, draw_w), off)
+        cols = dev(torch.randint(0, draw_w, (n_cols,), generator=g, dtype=torch.int32))
+        g_off = dev(rnd(Cc, H, W), True)                                                       # a guide 4 bytes off, whatever the launch's form
+
+        def step_table(rows):
+            """rows: dicts of the fields that differ from a plain row (x 0, eps 0, no cfg, out r, no dup, no blend, no noise)."""
+            R = len(rows)
+            ir, fr, pr = torch.zeros(R, SR["DS_SR_NI"], dtype=torch.int32), torch.zeros(R, SR["DS_SR_NF"]), torch.zeros(R, SR["DS_SR_NP"], dtype=torch.int64)
+            hr = torch.zeros(R, dtype=torch.int64)
+            fr[:, :5] = coefs(g, R)
+            fr[:, SR["DS_SR_Q0"]], fr[:, SR["DS_SR_Q1"]], fr[:, SR["DS_SR_CFG"]] = 0.8, 0.6, 2.5
+            for r, d in enumerate(rows):
+                ir[r, SR["DS_SR_EPSC"]], ir[r, SR["DS_SR_DUP"]], ir[r, SR["DS_SR_OUT"]] = -1, -1, r
+                ir[r, SR["DS_SR_DRAW_ROWS"]], ir[r, SR["DS_SR_DRAW_W"]] = 2, draw_w
+                pr[r, SR["DS_SR_DRAW"]], pr[r, SR["DS_SR_SEED"]], pr[r, SR["DS_SR_OFFSET"]] = draw.data_ptr(), 1234 + r, 77
+                for k, v in d.items():
+                    if k == "hist":
+                        hr[r] = v
+                    elif k == "c4":
+                        fr[r, 4] = v
+                    elif "DS_SR_" + k in ("DS_SR_GUIDE", "DS_SR_INIT", "DS_SR_MASKP", "DS_SR_DRAW"):
+                        pr[r, SR["DS_SR_" + k]] = v
+                    else:
+                        ir[r, SR["DS_SR_" + k]] = v
+            return dev(ir), dev(fr), dev(pr), dev(hr)
+
+        blend1 = dict(BLEND=1, GUIDE=guide[1].data_ptr(), INIT=init[1].data_ptr(), MASKP=mask1[1].data_ptr())
+        blend2 = dict(BLEND=2, MASK_CHW=1, GUIDE=g_off.data_ptr(), MASKP=maskc[2].data_ptr())
+        rows = [dict(X=1, EPS=2),                                                              # no noise
+                dict(X=0, EPS=1, EPSC=3, DUP=7, NOISE=1, SAMPLE=1, COLS=0, **blend1),          # a draw, CFG, a duplicate row
+                dict(X=3, EPS=5, NOISE=2, SAMPLE=0, COLS=W, **blend2),                         # Philox, the second half of the column table
+                dict(X=4, EPS=0),                                                              # x out of range
+                dict(X=0, EPS=0, BLEND=3),                                                     # unknown blend
+                dict(X=0, EPS=0, BLEND=2, MASKP=mask1[0].data_ptr()),                          # missing guide
+                dict(X=0, EPS=0, NOISE=1, SAMPLE=2),                                           # bad noise fields: a sample beyond the draw's rows
+                dict(X=0, EPS=0, OUT=9)]                                                       # out-of-range output row
+        ir, fr, pr, _ = step_table(rows)
+        out = dev(pat(9, Cc, H, W), off)
+        p = L.StepRowsParams(x=xs.data_ptr(), eps=es.data_ptr(), out=out.data_ptr(), irow=ir.data_ptr(), frow=fr.data_ptr(), prow=pr.data_ptr(),
+                             cols=cols.data_ptr(), R=len(rows), C=Cc, H=H, W=W, Bx=4, Beps=6, Bout=9, n_cols=n_cols)
+        L.call("ds_step_rows", C.byref(p), st)
+        yield "step_rows " + tag, dict(out=out)
+
+        hists = [dev(rnd(Cc, H, W), off), dev(rnd(Cc, H, W), True)]
+        rows = [dict(X=1, EPS=2, c4=0.0),                                                      # first order, no history
+                dict(X=0, EPS=1, EPSC=3, DUP=7, hist=hists[0].data_ptr()),                     # second order, CFG, a duplicate row
+                dict(X=3, EPS=5, hist=hists[1].data_ptr(), **blend1),                          # second order, a history 4 bytes off, a blend
+                dict(X=2, EPS=4),                                                              # second order without a history
+                dict(X=0, EPS=0, c4=0.0, NOISE=1, SAMPLE=0),                                   # the solver draws no noise
+                dict(X=0, EPS=0, c4=0.0, OUT=9)]                                               # out-of-range output row
+        ir, fr, pr, hr = step_table(rows)
+        out = dev(pat(9, Cc, H, W), off)
+        p = L.StepRowsParams(x=xs.data_ptr(), eps=es.data_ptr(), out=out.data_ptr(), irow=ir.data_ptr(), frow=fr.data_ptr(), prow=pr.data_ptr(),
+                             cols=None, R=len(rows), C=Cc, H=H, W=W, Bx=4, Beps=6, Bout=9, n_cols=0)
+        L.call("ds_dpm_step_rows", C.byref(p), hr.data_ptr(), st)
+        yield "dpm_step_rows " + tag, dict(out=out, hist0=hists[0], hist1=hists[1])
+
+        # ---- the edit kernels
+        rows = [(0, 0, 1, 1, 1, 0), (2, 2, -1, 2, 0, W), (1, 3, -1, 0, 1, 0), (3, 4, -1, 1, 0, 0)]      # src, out, dup, noise, sample, cols
+        ir, fr, pr = torch.zeros(4, QS["DS_QS_NI"], dtype=torch.int32), torch.rand(4, QS["DS_QS_NF"], generator=g) + 0.1, torch.zeros(4, QS["DS_QS_NP"], dtype=torch.int64)
+        for r, (src, orow, dup, nz, sample, co) in enumerate(rows):                             # row 2: no noise mode; row 3: a source out of range
+            ir[r] = torch.tensor([src, orow, dup, nz, sample, 2, draw_w, co], dtype=torch.int32)
+            pr[r] = torch.tensor([draw.data_ptr(), 99 + r, 5], dtype=torch.int64)
+        assert [QS[k] for k in ("DS_QS_SRC", "DS_QS_OUT", "DS_QS_DUP", "DS_QS_NOISE", "DS_QS_SAMPLE", "DS_QS_DRAW_ROWS", "DS_QS_DRAW_W", "DS_QS_COLS")] == list(range(8))
+        assert [QS[k] for k in ("DS_QS_DRAW", "DS_QS_SEED", "DS_QS_OFFSET")] == [0, 1, 2]
+        ir, fr, pr = dev(ir), dev(fr), dev(pr)
+        x0, out = dev(rnd(3, Cc, H, W), off), dev(pat(6, Cc, H, W), off)
+        p = L.QSampleRowsParams(x0=x0.data_ptr(), out=out.data_ptr(), irow=ir.data_ptr(), frow=fr.data_ptr(), prow=pr.data_ptr(), cols=cols.data_ptr(),
+                                R=4, C=Cc, H=H, W=W, Bx0=3, Bout=6, n_cols=n_cols)
+        L.call("ds_q_sample_rows", C.byref(p), st)
+        yield "q_sample_rows " + tag, dict(out=out)
+
+        prev_a, prev_o = dev(rnd(Cc, H, W), off), dev(rnd(Cc, H, W), True)
+        rows = [(0, 1, 2, -1, 0, 0, None), (1, -1, 0, 3, 1, prev_o.data_ptr(), None), (2, 3, 1, -1, 2, 0, 0.0), (4, 0, 0, -1, 3, 0, None),
+                (0, -1, 0, -1, 4, 0, None), (3, -1, 5, 4, 5, prev_a.data_ptr(), None)]          # x, prev, eps, eps_c, out, prev address, coef[4]
+        assert [EN[k] for k in ("DS_EN_X", "DS_EN_PREV", "DS_EN_EPS", "DS_EN_EPSC", "DS_EN_OUT")] == list(range(5))
+        ir, fr, pr = torch.zeros(6, EN["DS_EN_NI"], dtype=torch.int32), torch.zeros(6, EN["DS_EN_NF"]), torch.zeros(6, EN["DS_EN_NP"], dtype=torch.int64)
+        fr[:, :5], fr[:, EN["DS_EN_CFG"]] = coefs(g, 6), 2.5
+        for r, (xr, pv, er, ecr, orow, addr, c4) in enumerate(rows):                            # row 2: coef[4] == 0; row 3: x out of range; row 4: no x_prev
+            ir[r] = torch.tensor([xr, pv, er, ecr, orow], dtype=torch.int32)
+            pr[r, EN["DS_EN_PREVP"]] = addr
+            if c4 is not None:
+                fr[r, 4] = c4
+        ir, fr, pr = dev(ir), dev(fr), dev(pr)
+        z = dev(pat(7, Cc, H, W), off)
+        p = L.EditNoiseRowsParams(X=xs.data_ptr(), eps=es.data_ptr(), z=z.data_ptr(), irow=ir.data_ptr(), frow=fr.data_ptr(), prow=pr.data_ptr(),
+                                  R=6, C=Cc, H=H, W=W, Bx=4, Beps=6, Bz=7)
+        L.call("ds_edit_noise_rows", C.byref(p), st)
+        yield "edit_noise_rows " + tag, dict(z=z)
+
+        # ---- the guidance kernels
+        for phi in (0.0, 0.7):
+            out, gain = dev(pat(B, Cc, H, W), off), dev(pat(B))
+            p = L.CfgRescaleParams(eps_u=eps.data_ptr(), eps_c=epsc.data_ptr(), out=out.data_ptr(), gain=gain.data_ptr(), cfg_scale=3.5, phi=phi, B=B, CHW=CHW)
+            L.call("ds_cfg_rescale", C.byref(p), st)
+            yield "cfg_rescale %s phi=%g" % (tag, phi), dict(out=out, gain=gain)
+            e7, gain = dev(torch.cat([rnd(4, Cc, H, W), pat(3, Cc, H, W)]), off), dev(pat(4))
+            ir = dev(torch.tensor([[0, 1, 4], [2, 3, 2], [0, 7, 5], [0, 1, 7]], dtype=torch.int32))      # row 1 writes its own u; row 2: c out of range; row 3: out
+            fr = dev(torch.tensor([[3.5, phi], [2.0, phi], [3.5, phi], [3.5, phi]]))
+            p = L.CfgRescaleRowsParams(eps=e7.data_ptr(), irow=ir.data_ptr(), frow=fr.data_ptr(), gain=gain.data_ptr(), R=4, CHW=CHW, Beps=7)
+            L.call("ds_cfg_rescale_rows", C.byref(p), st)
+            yield "cfg_rescale_rows %s phi=%g" % (tag, phi), dict(eps=e7, gain=gain)
+        for K, per_col, phi in itertools.product((1, 3, 8), (False, True), (0.0, 0.7)):
+            ww = W if per_col else 1
+            ck, wt = dev(rnd(K, B, Cc, H, W), off), dev(torch.rand(2 * K * ww, generator=g), off)
+            out, gain = dev(pat(B, Cc, H, W), off), dev(pat(B))
+            p = L.CfgComposeParams(eps_u=eps.data_ptr(), eps_c=ck.data_ptr(), wt=wt.data_ptr(), out=out.data_ptr(), gain=gain.data_ptr(), cfg_scale=3.5,
+                                   phi=phi, B=B, K=K, CHW=CHW, W=W, wt_w=ww)
+            L.call("ds_cfg_compose", C.byref(p), st)
+            yield "cfg_compose %s K=%d wt_w=%d phi=%g" % (tag, K, ww, phi), dict(out=out, gain=gain)
+            # eps of 14 rows: u 0, c 1..8, outputs 10 / 11 / 12, 13 never named.  Row 1 walks its c rows downwards and takes the second table
+            e14, gain = dev(torch.cat([rnd(9, Cc, H, W), pat(5, Cc, H, W)]), off), dev(pat(4))
+            assert [CC[k] for k in ("DS_CC_U", "DS_CC_OUT", "DS_CC_K", "DS_CC_C0", "DS_CC_CSTRIDE", "DS_CC_WT", "DS_CC_WTW")] == list(range(7))
+            ir = dev(torch.tensor([[0, 10, K, 1, 1, 0, ww], [0, 11, K, K, -1, K * ww, ww], [0, 12, K, 14 - K + 1, 1, 0, ww], [0, 14, K, 1, 1, 0, ww]],
+                                  dtype=torch.int32))                                            # row 2: c_K out of range; row 3: out out of range
+            fr = dev(torch.tensor([[3.5, phi], [2.0, phi], [3.5, phi], [3.5, phi]]))
+            p = L.CfgComposeRowsParams(eps=e14.data_ptr(), irow=ir.data_ptr(), frow=fr.data_ptr(), wt=wt.data_ptr(), gain=gain.data_ptr(), R=4, CHW=CHW,
+                                       W=W, Beps=14, n_wt=2 * K * ww)
+            L.call("ds_cfg_compose_rows", C.byref(p), st)
+            yield "cfg_compose_rows %s K=%d wt_w=%d phi=%g" % (tag, K, ww, phi), dict(eps=e14, gain=gain)
+
+        # ---- the other kernels of sampler_step.hip
+        buf = dev(torch.cat([rnd(4, Cc, H, W), pat(2, Cc, H, W)]), off)
+        pairs = dev(torch.tensor([[0, 4], [1, 1], [2, 9], [3, 5]], dtype=torch.int32))         # (1, 1) and (2, 9) copy nothing
+        L.call("ds_copy_rows", buf.data_ptr(), pairs.data_ptr(), 4, CHW, 6, st)
+        yield "copy_rows " + tag, dict(buf=buf)
+        gout = dev(pat(2 * Cc * H, W), off)
+        L.call("ds_gather_cols", draw.data_ptr(), 2 * Cc * H, draw_w, cols.data_ptr(), W, gout.data_ptr(), st)
+        yield "gather_cols " + tag, dict(out=gout)
+        nrm = dev(pat(12), off)
+        L.call("ds_philox_normal", nrm.data_ptr(), 10, 4321, 9, st)
+        yield "philox_normal n=10 " + tag, dict(out=nrm)
+        keep.clear()
+
+    # ---- the window kernels: C = 2, H = 3, B = 2; the STFT merge at F = 5 on the frame plans of scale 4
+    Cc, H, B, F = 2, 3, 2, 5
+    for W, window, stride, loop in ((40, 16, 8, False), (40, 16, 8, True), (37, 16, 5, True)):
+        tag = "W=%d window=%d stride=%d loop=%d" % (W, window, stride, loop)
+        g = torch.Generator().manual_seed(9000 + W + int(loop))
+        plan = window_plan(W, window, stride, loop)
+        lay = _Layout(plan, B, False, None)
+        x, rows = dev(_rand(g, B, Cc, H, W)), torch.from_numpy(lay.rows.copy())
+        for bad in (False, True):
+            if bad:
+                rows[1, L.WS["DS_WS_OFF"]], rows[2, L.WS["DS_WS_SRC"]], rows[3, L.WS["DS_WS_DST"]] = W, B, lay.Rw
+            xw, rd = dev(pat(lay.Rw, Cc, H, window)), dev(rows)
+            p = L.WindowSplitParams(x=x.data_ptr(), out=xw.data_ptr(), rows=rd.data_ptr(), R=lay.Rw, C=Cc, H=H, W=W, w=window, Bx=B, Bout=lay.Rw)
+            L.call("ds_window_split", C.byref(p), st)
+            yield "window_split %s%s" % (tag, " malformed rows" if bad else ""), dict(out=xw)
+
+        def merge_tables(pl, what):
+            """(erow, wcol, wcoef) of plan pl: as planned, with an erow entry out of range, or with two malformed column entries."""
+            erow = torch.from_numpy(lay.erow.copy())
+            wcol = torch.from_numpy(np.ascontiguousarray(np.stack([pl.win.T, pl.col.T], axis=2)))
+            if what == "erow":
+                erow[1, 0] = lay.Rw
+            if what == "wcol":
+                wcol[0, 5, WM["DS_WM_COL"]] = pl.window                                        # a column beyond the window
+                wcol[1, 9, WM["DS_WM_WIN"]] = pl.n                                             # a window that does not exist
+            return dev(erow), dev(wcol), dev(torch.from_numpy(np.ascontiguousarray(pl.coef.T)))
+
+        epsw = dev(_rand(g, lay.Rw, Cc, H, window))
+        fplan = window_plan(4 * W, 4 * window, 4 * stride, loop)
+        assert fplan.n == plan.n
+        enc = _rand(g, lay.Rw, 3, F, 4 * window)
+        encw = dev(torch.stack([enc[:, 0].abs(), torch.tanh(enc[:, 1]), torch.tanh(enc[:, 2])], 1))
+        for what in ("plan", "erow", "wcol", "plan +4B"):                                      # +4B: the scalar form forced by the address
+            off = what.endswith("+4B")
+            if off:
+                epsw, encw = dev(epsw, True), dev(encw, True)
+            erow, wcol, wcoef = merge_tables(plan, what)
+            out = dev(pat(B + 1, Cc, H, W), off)
+            p = L.WindowMergeParams(eps=epsw.data_ptr(), out=out.data_ptr(), erow=erow.data_ptr(), wcol=wcol.data_ptr(), wcoef=wcoef.data_ptr(),
+                                    R=B, n=plan.n, C=Cc, H=H, W=W, w=window, Beps=lay.Rw, Bout=B + 1)
+            L.call("ds_window_merge", C.byref(p), st)
+            yield "window_merge %s tables=%s" % (tag, what), dict(out=out)
+            erow, wcol, wcoef = merge_tables(fplan, what)
+            out = dev(pat(B + 1, 3, F, 4 * W), off)
+            p = L.StftWindowMergeParams(encw=encw.data_ptr(), out=out.data_ptr(), erow=erow.data_ptr(), wcol=wcol.data_ptr(), wcoef=wcoef.data_ptr(),
+                                        R=B, n=fplan.n, F=F, T=4 * W, w=4 * window, Bw=lay.Rw, Bout=B + 1)
+            L.call("ds_stft_window_merge", C.byref(p), st)
+            yield "stft_window_merge %s F=%d scale=4 tables=%s" % (tag, F, what), dict(out=out)
+        keep.clear()
+
+
+FAMILIES = {"attn_bf16": attn_bf16_cases, "row_kernels": row_kernels_cases}
 
 
 def child(family):
