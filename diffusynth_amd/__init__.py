@@ -9,3 +9,4 @@ Importing the package is cheap and works without a GPU; anything that computes l
 __version__ = "0.1.0"
 
 from .clap_text import ClapTextTower  # noqa: E402,F401
+from .pitch import PitchEstimate, estimate_pitch, yin  # noqa: E402,F401

@@ -7,6 +7,8 @@ every note of the same duration and total' >= 4 i), level by level, every level 
 ds_resample_sinc sequence over all its nodes, then one ds_mix_notes per track.
 
 Kept on purpose: the reference's rule for total <= 0 (range(ceil(total / 4)) is empty: notes at or below MIDI 52 are mixed unshifted).
+Opt-in (`tune=`, off by default): shift every note to its event's pitch in BOTH directions, from a stated source pitch or from the one
+pitch.estimate_pitch detects; signed chains through the same tree.
 Different on purpose: the resampler.  librosa's default (soxr_hq) is a closed third-party design; the windowed sinc of
 include/diffusynth_hip.h (fc = 0.95 min(1, rate), 32 zero crossings, Kaiser beta 12) is this package's definition.
 
@@ -39,6 +41,16 @@ def rate_of(n_steps):
 def chain_steps(total, step_size=4):
     """The n_steps of the reference's chained calls (track_maker.py:37-45): empty for total <= 0."""
     return [min(step_size, total - i * step_size) for i in range(int(math.ceil(total / step_size)))]
+
+
+def signed_chain(total, step_size=4, deadband=0.05):
+    """The n_steps of a chain that shifts by any real `total` of either sign: [] inside the deadband (|total| < deadband semitones: 5 cents
+    by default, below what is heard as mistuned), else sign * [step_size, ..., step_size, remainder].  chain_steps(total) for a positive integer."""
+    if not abs(total) >= deadband:
+        return []
+    sign, a = (1 if total > 0 else -1), abs(total)
+    n = int(math.ceil(a / step_size))
+    return [sign * step_size] * (n - 1) + [sign * (a - (n - 1) * step_size)]
 
 
 # ---------------------------------------------------------------------------------------------------- one batched pitch_shift
@@ -154,11 +166,35 @@ def shift_tree(requests, step_size=4):
     return levels
 
 
+def signed_tree(requests, step_size=4, deadband=0.05):
+    """shift_tree for real totals of either sign (signed_chain's chains): the node behind i whole steps is (key, +-step_size * i), the last
+    one (key, total) itself, so equal prefixes meet in one node by float equality and chains of opposite sign share only the root (key, 0).
+    A cumulative names its level, its parent and its n_steps, so (key, cumulative) appears once."""
+    levels, seen = [], set()
+    for k, t in sorted({(k, t) for k, t in requests if signed_chain(t, step_size, deadband)}, key=lambda kt: (str(kt[0]), kt[1])):
+        chain = signed_chain(t, step_size, deadband)
+        sign, lo = (1 if t > 0 else -1), 0
+        for i, st in enumerate(chain):
+            cum = t if i == len(chain) - 1 else sign * step_size * (i + 1)
+            if (k, cum) not in seen:
+                seen.add((k, cum))
+                while len(levels) <= i:
+                    levels.append([])
+                levels[i].append((k, lo, cum, st))
+            lo = cum
+    return levels
+
+
 def _run_tree(sources, requests, step_size=4):
     """sources {key: 1-D fp32 CUDA tensor}; -> {(key, cumulative): tensor} with (key, 0) = the source itself.  One batched launch sequence
     per level."""
+    return _run_levels(sources, shift_tree(requests, step_size))
+
+
+def _run_levels(sources, levels):
+    """_run_tree on built levels (shift_tree's or signed_tree's)."""
     have = {(k, 0): v for k, v in sources.items()}
-    for nodes in shift_tree(requests, step_size):
+    for nodes in levels:
         parents = [have[(k, lo)] for k, lo, _, _ in nodes]
         lengths = [p.numel() for p in parents]
         out, offs = _shift_flat(parents[0] if len(parents) == 1 else torch.cat(parents), lengths, [st for _, _, _, st in nodes])
@@ -168,10 +204,11 @@ def _run_tree(sources, requests, step_size=4):
 
 
 @torch.no_grad()
-def pitch_shift_chain(signals, totals, step_size=4):
+def pitch_shift_chain(signals, totals, step_size=4, *, signed=False):
     """The reference's pitch_shift_librosa (track_maker.py:12-47) for a batch: ceil(total / step_size) chained shifts of at most step_size
     semitones; total <= 0 returns the input unchanged (the reference's loop is empty).  Signals that are the same tensor share the common
-    prefix of their chains; the result is bit for bit what the chains run one by one give."""
+    prefix of their chains; the result is bit for bit what the chains run one by one give.  signed=True: real totals of either sign through
+    signed_chain (a total inside its deadband returns the input)."""
     if isinstance(signals, torch.Tensor) and signals.dim() == 2:
         _require_cuda(signals, "pitch_shift_chain")
         rows = list(signals)
@@ -186,8 +223,12 @@ def pitch_shift_chain(signals, totals, step_size=4):
         keys.append(key)
         if key not in sources:
             sources[key] = s.detach().float().contiguous()
-    have = _run_tree(sources, [(k, t) for k, t in zip(keys, tot) if t > 0], step_size)
-    out = [s if t <= 0 else have[(k, t)] for s, k, t in zip(rows, keys, tot)]
+    if signed:
+        have = _run_levels(sources, signed_tree(list(zip(keys, tot)), step_size))
+        out = [have[(k, t)] if signed_chain(t, step_size) else s for s, k, t in zip(rows, keys, tot)]
+    else:
+        have = _run_tree(sources, [(k, t) for k, t in zip(keys, tot) if t > 0], step_size)
+        out = [s if t <= 0 else have[(k, t)] for s, k, t in zip(rows, keys, tot)]
     if isinstance(signals, torch.Tensor):
         return torch.stack([o.float() for o in out])
     return out
@@ -258,6 +299,35 @@ def mix_notes(notes, events, track_len):
     L.call("ds_mix_notes", flat.data_ptr(), flat.numel(), base, len(ev), base + 4 * ev.size, base + 4 * (ev.size + ptr.size), len(lst), track.data_ptr(),
            track_len, L.current_stream())
     return track
+
+
+def _mix_nodes(have, placed, n):
+    """have {node: tensor}; placed: (node, start sample) per event in mixing order -> the track (every distinct node handed over once)."""
+    used, index = [], {}
+    for node, _ in placed:
+        if node not in index:
+            index[node] = len(used)
+            used.append(have[node])
+    return mix_notes(used, [(start, index[node]) for node, start in placed], n)
+
+
+# ---------------------------------------------------------------------------------------------------- tuned mode
+def _check_tune(tune):
+    """None, "detect" or a finite real number (returned as float); anything else is a ValueError, before any other work."""
+    if tune is None or (isinstance(tune, str) and tune == "detect"):
+        return tune
+    if isinstance(tune, (int, float, np.integer, np.floating)) and not isinstance(tune, (bool, np.bool_)) and math.isfinite(tune):
+        return float(tune)
+    raise ValueError(f"tune: None (the reference's rule), a MIDI pitch (a finite real number) or \"detect\", not {tune!r}")
+
+
+def _source_pitches(tune, keys, normed, sample_rate):
+    """{key: MIDI pitch of the normalised note}: the stated one, or ONE estimate_pitch call over all of them (nan = unpitched)."""
+    if tune != "detect":
+        return {k: tune for k in keys}
+    from . import pitch
+    est = pitch.estimate_pitch([normed[k] for k in keys], sample_rate=sample_rate)
+    return dict(zip(keys, est.midi.tolist()))
 
 
 # ---------------------------------------------------------------------------------------------------- Track (track_maker.py:50-187)
@@ -338,13 +408,37 @@ class Track:
     def track_length(self, sample_rate=16000):
         return int(self._get_total_time() * sample_rate)
 
+    last_pitches = None        # {duration key: MIDI pitch the note was taken to sit at, nan = unpitched} of the last tuned render
+
     @torch.no_grad()
-    def render(self, note_fn, sample_rate=16000, return_tensor=True, notes=None):
+    def render(self, note_fn, sample_rate=16000, return_tensor=True, notes=None, *, tune=None):
         """synthesize_track on the device.  note_fn(velocity, duration_sec) -> numpy array or tensor on either device, called once per distinct
         duration in event order (the reference's cache); notes: {duration key: tensor} sampled beforehand instead.  One peak normalisation,
-        one tree of chains over the distinct (duration, note) pairs, one mix."""
+        one tree of chains over the distinct (duration, note) pairs, one mix.
+
+        tune=None: the reference's rule (shift by note - 52, nothing at or below 52).  tune=p (a real number): every source is taken to sit
+        at MIDI p and each event is shifted by signed_chain(note - p), up or down; 52 is the reference's assumption without its <= 0 rule.
+        tune="detect": one pitch.estimate_pitch call over the normalised notes; a pitched note of detected pitch p_k is shifted by
+        signed_chain(note - p_k), an unpitched one (noise, percussion) follows the reference's rule.  The chains are planned on the host in
+        float64, so "detect" costs exactly one extra device -> host copy per render (a period and a count per distinct note).
+        last_pitches holds {duration key: p, p_k or nan} afterwards."""
+        tune = _check_tune(tune)
         if not torch.cuda.is_available():
             raise RuntimeError(_NO_GPU % "Track.render")
+        sched, n, raw = self._collect(note_fn, sample_rate, notes)
+        if not sched:
+            track = torch.zeros(n, dtype=torch.float32, device="cuda")
+            return track if return_tensor else track.cpu().numpy()
+        keys = list(raw)
+        normed = dict(zip(keys, peak_normalize([raw[k] for k in keys])))
+        if tune is None:
+            track = self._mix_reference(sched, n, normed)
+        else:
+            track = self._mix_tuned(sched, n, normed, _source_pitches(tune, keys, normed, sample_rate))
+        return track if return_tensor else track.cpu().numpy()
+
+    def _collect(self, note_fn, sample_rate, notes):
+        """(schedule, track length, {duration key: the raw 1-D fp32 CUDA note}) with the fit check."""
         sched = self.schedule(sample_rate)
         n = self.track_length(sample_rate)
         raw = {}
@@ -356,24 +450,28 @@ class Track:
         for key, _, start, _ in sched:
             if start + raw[key].numel() > n:
                 raise ValueError(f"Track: a note of {raw[key].numel()} samples at sample {start} ends past the track's {n} samples")
-        if not sched:
-            track = torch.zeros(n, dtype=torch.float32, device="cuda")
-            return track if return_tensor else track.cpu().numpy()
-        keys = list(raw)
-        normed = dict(zip(keys, peak_normalize([raw[k] for k in keys])))
+        return sched, n, raw
+
+    def _mix_reference(self, sched, n, normed):
         have = _run_tree(normed, [(key, total) for key, _, _, total in sched if total > 0])
-        used, index = [], {}
-        for key, _, _, total in sched:
-            node = (key, max(total, 0))
-            if node not in index:
-                index[node] = len(used)
-                used.append(have[node])
-        track = mix_notes(used, [(start, index[(key, max(total, 0))]) for key, _, start, total in sched], n)
-        return track if return_tensor else track.cpu().numpy()
+        return _mix_nodes(have, [((key, max(total, 0)), start) for key, _, start, total in sched], n)
+
+    def _mix_tuned(self, sched, n, normed, pitches):
+        """pitches {duration key: MIDI pitch of the normalised note, nan = unpitched}: the signed tree and the mix."""
+        self.last_pitches = {key: float(pitches[key]) for key in normed}
+        totals = []
+        for key, _, _, total in sched:                                         # total = note - 52
+            p = self.last_pitches[key]
+            totals.append(max(total, 0) if math.isnan(p) else (total + 52) - p)
+        have = _run_levels(normed, signed_tree([(key, t) for (key, _, _, _), t in zip(sched, totals)]))
+        return _mix_nodes(have, [((key, t if signed_chain(t) else 0), start) for (key, _, start, _), t in zip(sched, totals)], n)
 
     def synthesize_track(self, diffSynthSampler, sample_rate=16000):
         """The reference's method: float32 numpy array."""
         return self.render(diffSynthSampler, sample_rate, return_tensor=False)
+
+
+_UNSET = object()
 
 
 # ---------------------------------------------------------------------------------------------------- DiffSynth (track_maker.py:190-322)
@@ -388,7 +486,7 @@ class DiffSynth:
 
     def __init__(self, instruments_configs, noise_prediction_model, VAE_quantizer, VAE_decoder, text_encoder, CLAP_tokenizer, device,
                  model_sample_rate=16000, timesteps=1000, channels=4, freq_resolution=512, time_resolution=256, VAE_scale=4, squared=False, *,
-                 condition=None, noise_device="philox", seed=None):
+                 condition=None, noise_device="philox", seed=None, tune=None):
         self.noise_prediction_model, self.VAE_quantizer, self.VAE_decoder = noise_prediction_model, VAE_quantizer, VAE_decoder
         self.device, self.model_sample_rate, self.timesteps, self.channels = device, model_sample_rate, timesteps, channels
         self.freq_resolution, self.time_resolution, self.VAE_scale, self.squared = freq_resolution, time_resolution, VAE_scale, squared
@@ -396,7 +494,9 @@ class DiffSynth:
         self.text_encoder, self.CLAP_tokenizer = text_encoder, CLAP_tokenizer
         self.instruments_configs = instruments_configs
         self.condition, self.noise_device, self.seed = condition, noise_device, seed
+        self.tune = _check_tune(tune)                # Track.render's tune=, for every track of arrange / get_music
         self.last_batcher = None
+        self.last_pitches = None                     # {(instrument name, duration_sec): MIDI pitch or nan} of the last tuned arrange
 
     def _condition(self):
         if self.text_encoder is not None:
@@ -459,15 +559,46 @@ class DiffSynth:
         return [(instrument_names[i], dur) for i, t in enumerate(tracks) for _, dur, _, _ in t.schedule(sample_rate)]
 
     @torch.no_grad()
-    def arrange(self, tracks, instrument_names, notes, sample_rate=16000):
+    def arrange(self, tracks, instrument_names, notes, sample_rate=16000, *, tune=_UNSET):
         """The audio stage of get_music on sampled notes {(instrument name, duration_sec): signal}: normalise, chains and mix per track,
-        then the sum of the zero-padded tracks (track_maker.py:316-322), all on the device."""
-        audios = [t.render(None, sample_rate, notes={key: notes[(instrument_names[i], dur)] for key, dur, _, _ in t.schedule(sample_rate)})
-                  for i, t in enumerate(tracks)]
+        then the sum of the zero-padded tracks (track_maker.py:316-322), all on the device.  tune (default: the constructor's) as in
+        Track.render; with "detect" the distinct notes of ALL tracks are normalised in one launch and estimated in ONE estimate_pitch call
+        (one extra device -> host copy per call), and each track is then what its own tuned render gives, bit for bit."""
+        tune = self.tune if tune is _UNSET else _check_tune(tune)
+        per_track = [{key: notes[(instrument_names[i], dur)] for key, dur, _, _ in t.schedule(sample_rate)} for i, t in enumerate(tracks)]
+        if tune == "detect":
+            audios = self._arrange_detected(tracks, instrument_names, per_track, sample_rate)
+        else:
+            audios = [t.render(None, sample_rate, notes=per_track[i], tune=tune) for i, t in enumerate(tracks)]
+            if tune is not None:
+                self.last_pitches = {(instrument_names[i], dur): tune for i, t in enumerate(tracks) for _, dur, _, _ in t.schedule(sample_rate)}
         full = torch.zeros(max(a.numel() for a in audios), dtype=torch.float32, device=audios[0].device)
         for a in audios:                           # the reference's order: full_audio += pad(audio), track by track
             full[:a.numel()] += a
         return full
+
+    def _arrange_detected(self, tracks, instrument_names, per_track, sample_rate):
+        if not torch.cuda.is_available():
+            raise RuntimeError(_NO_GPU % "DiffSynth.arrange")
+        parts = [t._collect(None, sample_rate, per_track[i]) for i, t in enumerate(tracks)]
+        ids, flat = {}, []                                                      # every distinct (instrument, duration) note once
+        for i, (sched, _, raw) in enumerate(parts):
+            for key, dur, _, _ in sched:
+                if (instrument_names[i], dur) not in ids:
+                    ids[(instrument_names[i], dur)] = len(flat)
+                    flat.append(raw[key])
+        audios = [torch.zeros(n, dtype=torch.float32, device="cuda") for _, n, _ in parts]
+        if not flat:
+            self.last_pitches = {}
+            return audios
+        normed = peak_normalize(flat)
+        midi = _source_pitches("detect", list(range(len(flat))), normed, sample_rate)
+        self.last_pitches = {name_dur: midi[j] for name_dur, j in ids.items()}
+        for i, (sched, n, raw) in enumerate(parts):
+            if sched:
+                own = {key: ids[(instrument_names[i], dur)] for key, dur, _, _ in sched}
+                audios[i] = tracks[i]._mix_tuned(sched, n, {key: normed[j] for key, j in own.items()}, {key: midi[j] for key, j in own.items()})
+        return audios
 
     @torch.no_grad()
     def get_music(self, mid, instrument_names, sample_rate=16000, max_notes=100, return_tensor=False):

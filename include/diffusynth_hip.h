@@ -903,6 +903,34 @@ int ds_peak_normalize(const float* x, const int32_t* tab, int n_signals, int max
 int ds_mix_notes(const float* notes, long long total_samples, const int32_t* ev, int n_events, const int32_t* blk_ptr, const int32_t* blk_ev,
                  int n_blk_ev, float* track, int track_len, void* stream);
 
+/* ---------------------------------------------------------------- pitch detection (csrc/pitch.hip): YIN (de Cheveigne & Kawahara 2002), fp32
+ * ds_yin_frames: period and aperiodicity of every frame of a ragged batch.  A signal is row s of tab, a device array
+ * [n_signals][DS_YIN_NI] int32: XOFF, LEN its samples in x; FOFF, NF its frames in period / aperiodicity, NF = max(0, (LEN - W - tau_max) / hop
+ * + 1) computed by the host in integers (W = frame_length); frame i reads samples [i hop, i hop + W + tau_max).  A signal of zero frames is
+ * legal; a row or a frame that does not fit its extents or the stated totals reads and writes nothing.  Per frame:
+ *   d(tau) = sum_{j < W} (s[j] - s[j + tau])^2, tau = 0 .. tau_max, as differences (four interleaved accumulators j mod 4 walked in j
+ *            order, summed as (a0 + a1) + (a2 + a3): a fixed order);
+ *   c(0) = 1, c(tau) = d(tau) tau / sum_{k = 1 .. tau} d(k) (the sum running in k order), 1 where that sum is 0: silence is unvoiced, not NaN;
+ *   pick = the smallest tau in [tau_min, tau_max) with c(tau) < threshold, then tau + 1 while tau + 1 < tau_max and c(tau + 1) < c(tau);
+ *   with a, b, c = c(pick - 1), c(pick), c(pick + 1): offset = 0.5 (a - c) / (a - 2 b + c) if that denominator is > 0 and b <= a and b <= c,
+ *   else 0;  period = pick + offset, aperiodicity = b.  No tau under the threshold: period = 0, aperiodicity = 1 (no global-minimum fallback).
+ * 1 <= W <= DS_YIN_MAX_W, hop >= 1, 2 <= tau_min < tau_max <= DS_YIN_MAX_TAU, 0 < threshold < 1.  No atomics; a frame's outputs are the same
+ * bits whatever shares the batch.
+ * ds_pitch_median: per signal (rows FOFF, NF of the same table) the LOWER median of the periods > 0 — the element of rank (n_voiced - 1) / 2,
+ * one of the input values bit for bit — and n_voiced; 0 and 0 when nothing is voiced.  NF <= DS_PITCH_MAX_FRAMES. */
+#define DS_YIN_XOFF 0
+#define DS_YIN_LEN 1
+#define DS_YIN_FOFF 2
+#define DS_YIN_NF 3
+#define DS_YIN_NI 4
+#define DS_YIN_MAX_W 2048
+#define DS_YIN_MAX_TAU 1024
+#define DS_PITCH_MAX_FRAMES 8192
+int ds_yin_frames(const float* x, const int32_t* tab, int n_signals, int max_frames, long long total_samples, long long total_frames,
+                  int frame_length, int hop, int tau_min, int tau_max, float threshold, float* period, float* aperiodicity, void* stream);
+int ds_pitch_median(const float* period, const int32_t* tab, int n_signals, int max_frames, long long total_frames, float* median,
+                    int32_t* voiced, void* stream);
+
 /* ---------------------------------------------------------------- timbre encoder (timbre_encoder_pretrain.py:39,71,81-84), fp32
  * One nn.LSTM layer over a whole sequence, h0 = c0 = 0:  c' = sigmoid(f) c + sigmoid(i) tanh(g),  h' = sigmoid(o) tanh(c')  with
  * [i f g o][b][t] = pre[b][t] + h[b][t-1] w_hh^T.  pre [B][T][4H] = x W_ih^T + b_ih + b_hh comes from the caller (one ds_linear over all B T rows;

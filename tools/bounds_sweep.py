@@ -69,6 +69,26 @@ def sweep_arranger(fail):
     report("mix_notes 9 events over 98 blocks + a 5-sample track", fail)
 
 
+def sweep_pitch(fail):
+    """Pitch detection (csrc/pitch.hip): a ragged batch with frameless signals at both ends and one sample either side of a frame, the
+    largest LDS image (frame_length 2048, tau_max 1024, tau_min 2) with an odd hop, an odd frame length, the median at its frame limit, and
+    the tuned arranger on top (signed chains of both signs)."""
+    from diffusynth_amd import arranger as A
+    from diffusynth_amd import pitch
+    sigs = [synth_input("bs_pitch%d" % n, (n,)).cuda() for n in (100, 28416, 1313, 1314, 1570, 30001, 4097, 77568, 1)]
+    t = torch.arange(28416, device="cuda") / 16000.0
+    tone = torch.sin(2 * torch.pi * 150.0 * t) * torch.exp(-1.5 * t)
+    pitch.estimate_pitch(sigs + [tone])
+    pitch.yin(torch.stack([tone, tone]))
+    report("estimate_pitch ragged batch of 10 + a (2, L) batch", fail)
+    pitch.estimate_pitch([sigs[1], tone, sigs[6]], fmin=15.625, fmax=8000.0, frame_length=2048, hop_length=301)
+    pitch.estimate_pitch([tone, sigs[5]], fmin=15.625, fmax=8000.0, frame_length=1023, hop_length=7)
+    pitch.estimate_pitch([tone[:1314 + 8191]], hop_length=1)
+    report("estimate_pitch largest LDS image, odd frame length, 8192 frames", fail)
+    A.pitch_shift_chain([tone, tone, tone, sigs[6]], [-9.37, 6.63, -3.37, -1.5], signed=True)
+    report("pitch_shift_chain signed tree", fail)
+
+
 def _partials(stored, parts):
     """(sum, sumsq) of ``parts`` chunks of each sample of a device tensor as fp32 [B][parts][2], placed 24 bytes into a NaN-filled allocation:
     the base is 8-byte but not 16-byte aligned and anything read beyond the buffer is NaN (tests/gn_partials_ref.py:guarded)."""
@@ -368,6 +388,10 @@ def main():
         sweep_ui_images(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
         sys.exit(1 if fail else 0)
+    if "--only-pitch" in sys.argv:
+        sweep_pitch(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
     if "--only-arranger" in sys.argv:
         sweep_arranger(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
@@ -446,6 +470,7 @@ def main():
     sweep_ui_images(fail)
     # 5) the arranger's audio stage
     sweep_arranger(fail)
+    sweep_pitch(fail)
     # 6) GroupNorm from raw partials in every kernel that reduces them, the depthwise families, the chains without ds_gn_finalize
     sweep_gn_partials(fail)
     if fail:
