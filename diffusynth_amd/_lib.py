@@ -61,6 +61,7 @@ PV = _parse_defines(_HEADER_TEXT, "DS_PV_")     # arranger signal table (field i
 MIX_BLOCK = _parse_defines(_HEADER_TEXT, "DS_MIX_")["DS_MIX_BLOCK"]
 YIN = _parse_defines(_HEADER_TEXT, "DS_YIN_")     # pitch signal table (field indices and row width), DS_YIN_MAX_W, DS_YIN_MAX_TAU
 PITCH_MAX_FRAMES = _parse_defines(_HEADER_TEXT, "DS_PITCH_")["DS_PITCH_MAX_FRAMES"]
+RP = _parse_defines(_HEADER_TEXT, "DS_RP_")     # ds_resample_poly signal table (field indices and row width), DS_RP_MAX_TAPS / _SPAN / _BLK
 TAIL = _parse_defines(_HEADER_TEXT, "DS_TAIL_")     # ds_text_tail: op codes
 ConvParams = _STRUCTS["ds_conv_params"]
 PackConvParams = _STRUCTS["ds_pack_conv_params"]
@@ -193,6 +194,7 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_mix_notes": (C.c_int, [_P, C.c_longlong, _P, _I, _P, _P, _I, _P, _I, _P]),
     "ds_yin_frames": (C.c_int, [_P, _P, _I, _I, C.c_longlong, C.c_longlong, _I, _I, _I, _I, _F, _P, _P, _P]),
     "ds_pitch_median": (C.c_int, [_P, _P, _I, _I, C.c_longlong, _P, _P, _P]),
+    "ds_resample_poly": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, _P, _P]),
     "ds_lstm_ws_floats": (_SZ, [_I, _I]),
     "ds_lstm_layer": (C.c_int, [_P, C.c_longlong, C.c_longlong, _P, _I, _I, _I, _P, _P, _P, _P]),
     "ds_timbre_heads": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P]),

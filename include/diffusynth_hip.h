@@ -931,6 +931,44 @@ int ds_yin_frames(const float* x, const int32_t* tab, int n_signals, int max_fra
 int ds_pitch_median(const float* period, const int32_t* tab, int n_signals, int max_frames, long long total_frames, float* median,
                     int32_t* voiced, void* stream);
 
+/* ---------------------------------------------------------------- sample-rate conversion (csrc/resample_poly.hip), fp32
+ * ds_resample_poly: scipy.signal.resample_poly(x, up, down) with its defaults (window ("kaiser", 5.0), padtype "constant") — which is
+ * librosa.resample(res_type="polyphase") and what tools.adjust_audio_length (tools.py:126-151) means in this package — fused with its crop /
+ * zero-pad (librosa.util.fix_length), for a ragged batch whose signals may each have their own rate pair.  With g = gcd(orig_sr, target_sr),
+ * UP = target_sr / g, DOWN = orig_sr / g, HALF = 10 max(UP, DOWN), fc = 1 / max(UP, DOWN), the filter has 2 HALF + 1 taps
+ *   h[k] = UP s[k] w[k] / sum_j s[j] w[j],  s[k] = fc sinc(fc (k - HALF)),  w[k] = I0(5 sqrt(1 - ((k - HALF) / HALF)^2)) / I0(5)
+ * designed by the caller in float64 and rounded to fp32 once, and
+ *   y[m] = sum_n x[n] h[HALF + m DOWN - n UP]  over 0 <= n < LEN with the tap index inside [0, 2 HALF],  0 <= m < NRES = ceil(LEN UP / DOWN).
+ * A signal is row s of tab, a device array [n_signals][DS_RP_NI] int32 (offsets and counts in ELEMENTS):
+ *   XOFF, LEN    its samples in x
+ *   OOFF, OLEN   its output in out: out[m] = y[m] for m < min(OLEN, NRES), 0 for NRES <= m < OLEN (OLEN is the fix_length target)
+ *   NRES         ceil(LEN UP / DOWN), computed by the caller in integers
+ *   UP, DOWN, HALF   its rate pair; any HALF >= 1 with 2 HALF + 1 <= max_taps is legal (the taps are the caller's)
+ *   HOFF         its 2 HALF + 1 taps in filt (rows of one rate pair share them)
+ *   BLK          the outputs one block of the launch owns, 1 <= BLK <= DS_RP_MAX_BLK, chosen by the caller so that the inputs of BLK
+ *                consecutive outputs — at most ((BLK - 1) DOWN + 2 HALF) / UP + 2 samples — number at most `span`
+ * max_blocks = the largest ceil(OLEN / BLK) of the batch, max_taps >= every row's 2 HALF + 1 (<= DS_RP_MAX_TAPS), span <= DS_RP_MAX_SPAN;
+ * the launch uses (max_taps + span) * 4 bytes of LDS per block.  Every element of a row's output is written and nothing outside it; a row that
+ * does not fit the stated totals, max_taps or span reads and writes nothing.  The products m DOWN and n UP are formed in 64 bits.  Per output
+ * the taps are walked in ascending tap index (descending n) as acc = fma(x[n], h[k], acc) from acc = 0: a fixed order, no atomics, so a
+ * signal's output is the same bits whatever else is in the launch, and an impulse returns the fp32 taps themselves. */
+#define DS_RP_XOFF 0
+#define DS_RP_LEN 1
+#define DS_RP_OOFF 2
+#define DS_RP_OLEN 3
+#define DS_RP_NRES 4
+#define DS_RP_UP 5
+#define DS_RP_DOWN 6
+#define DS_RP_HALF 7
+#define DS_RP_HOFF 8
+#define DS_RP_BLK 9
+#define DS_RP_NI 10
+#define DS_RP_MAX_TAPS 16384
+#define DS_RP_MAX_SPAN 20480
+#define DS_RP_MAX_BLK 1024
+int ds_resample_poly(const float* x, const int32_t* tab, const float* filt, int n_signals, int max_blocks, int max_taps, int span,
+                     long long total_in, long long total_out, long long total_filt, float* out, void* stream);
+
 /* ---------------------------------------------------------------- timbre encoder (timbre_encoder_pretrain.py:39,71,81-84), fp32
  * One nn.LSTM layer over a whole sequence, h0 = c0 = 0:  c' = sigmoid(f) c + sigmoid(i) tanh(g),  h' = sigmoid(o) tanh(c')  with
  * [i f g o][b][t] = pre[b][t] + h[b][t-1] w_hh^T.  pre [B][T][4H] = x W_ih^T + b_ih + b_hh comes from the caller (one ds_linear over all B T rows;

@@ -89,6 +89,29 @@ def sweep_pitch(fail):
     report("pitch_shift_chain signed tree", fail)
 
 
+def sweep_ingest(fail):
+    """The ingest path (csrc/resample_poly.hip): one ragged launch of eight rate pairs (a signal shorter than its filter, outputs over several
+    blocks, up = 1, down = 1, the largest filter), fix_length targets on both sides of NRES, a steep decimation whose blocks shrink to fit the
+    span, rows that stay out of the launch, and uploads_to_stft on top."""
+    import numpy as np
+    from diffusynth_amd import ingest as G
+    lengths = (1, 2, 160, 441, 442, 1000, 3001, 7777)
+    origs = (44100, 48000, 8000, 11025, 22050, 16000, 16000, 8000)
+    targets = (16000, 16000, 16000, 16000, 16000, 48000, 44100, 16000)
+    sigs = [synth_input("bs_ing%d" % n, (n,)).cuda() for n in lengths]
+    G.resample_poly(sigs, list(origs), list(targets))
+    G.resample_poly(sigs, list(origs), list(targets), lengths=[5, 1, 200, 1500, 321, 2048, 8272, 20000])
+    report("resample_poly ragged batch of 8 rate pairs, with and without fix_length targets", fail)
+    G.resample_poly([sigs[7], sigs[6], sigs[5]], [96000, 16000, 44100], [8000, 16000, 16000], lengths=[700, 100, 4000])
+    G.resample_poly(torch.stack([sigs[7], sigs[7]]), 44100, 16000, lengths=65280)
+    report("resample_poly 12:1 decimation, an equal-rate row, a (2, L) batch", fail)
+    ups = [(44100, (synth_input("bs_ing_a", (13230,)).numpy() * 3000).astype(np.int16)), (48000, synth_input("bs_ing_b", (48000,)).double()),
+           (16000, synth_input("bs_ing_c", (5000,)))]
+    G.uploads_to_stft(ups, 1, time_resolution=48)
+    G.uploads_to_stft(ups, 3)
+    report("uploads_to_stft 3 uploads at two durations", fail)
+
+
 def _partials(stored, parts):
     """(sum, sumsq) of ``parts`` chunks of each sample of a device tensor as fp32 [B][parts][2], placed 24 bytes into a NaN-filled allocation:
     the base is 8-byte but not 16-byte aligned and anything read beyond the buffer is NaN (tests/gn_partials_ref.py:guarded)."""
@@ -392,6 +415,10 @@ def main():
         sweep_pitch(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
         sys.exit(1 if fail else 0)
+    if "--only-ingest" in sys.argv:
+        sweep_ingest(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
     if "--only-arranger" in sys.argv:
         sweep_arranger(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
@@ -471,6 +498,7 @@ def main():
     # 5) the arranger's audio stage
     sweep_arranger(fail)
     sweep_pitch(fail)
+    sweep_ingest(fail)
     # 6) GroupNorm from raw partials in every kernel that reduces them, the depthwise families, the chains without ds_gn_finalize
     sweep_gn_partials(fail)
     if fail:
