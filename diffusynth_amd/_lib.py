@@ -59,6 +59,7 @@ WM = _parse_defines(_HEADER_TEXT, "DS_WM_")     # ds_window_merge column tables,
 DW_FAMILY ={v: k[6:].lower() for k, v in _parse_defines(_HEADER_TEXT, "DS_DW_").items()}     # ds_dwconv_launch_choice: family code -> name
 PV = _parse_defines(_HEADER_TEXT, "DS_PV_")     # arranger signal table (field indices and row width)
 MIX_BLOCK = _parse_defines(_HEADER_TEXT, "DS_MIX_")["DS_MIX_BLOCK"]
+MX = _parse_defines(_HEADER_TEXT, "DS_MX_")     # ds_mix_notes / ds_mix_notes_shaped event rows (field indices and row widths)
 YIN = _parse_defines(_HEADER_TEXT, "DS_YIN_")     # pitch signal table (field indices and row width), DS_YIN_MAX_W, DS_YIN_MAX_TAU
 PITCH_MAX_FRAMES = _parse_defines(_HEADER_TEXT, "DS_PITCH_")["DS_PITCH_MAX_FRAMES"]
 RP = _parse_defines(_HEADER_TEXT, "DS_RP_")     # ds_resample_poly signal table (field indices and row width), DS_RP_MAX_TAPS / _SPAN / _BLK
@@ -192,6 +193,7 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_peak_normalize_ws_bytes": (_SZ, [_I, _I]),
     "ds_peak_normalize": (C.c_int, [_P, _P, _I, _I, C.c_longlong, _P, _P, _P]),
     "ds_mix_notes": (C.c_int, [_P, C.c_longlong, _P, _I, _P, _P, _I, _P, _I, _P]),
+    "ds_mix_notes_shaped": (C.c_int, [_P, C.c_longlong, _P, _I, _P, _P, _I, _P, _I, _P]),
     "ds_yin_frames": (C.c_int, [_P, _P, _I, _I, C.c_longlong, C.c_longlong, _I, _I, _I, _I, _F, _P, _P, _P]),
     "ds_pitch_median": (C.c_int, [_P, _P, _I, _I, C.c_longlong, _P, _P, _P]),
     "ds_resample_poly": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, _P, _P]),

@@ -9,6 +9,9 @@ ds_resample_sinc sequence over all its nodes, then one ds_mix_notes per track.
 Kept on purpose: the reference's rule for total <= 0 (range(ceil(total / 4)) is empty: notes at or below MIDI 52 are mixed unshifted).
 Opt-in (`tune=`, off by default): shift every note to its event's pitch in BOTH directions, from a stated source pitch or from the one
 pitch.estimate_pitch detects; signed chains through the same tree.
+Opt-in (`pairing="midi"`, `perform=Performance(...)`, off by default): play the file as written — every close paired with the oldest
+open note of its pitch, the tempo map integrated, velocity as level and the reference's own ADSR envelope (tools.adsr_envelope) gated at
+the real note-off, both applied inside the mix (ds_mix_notes_shaped).
 Different on purpose: the resampler.  librosa's default (soxr_hq) is a closed third-party design; the windowed sinc of
 include/diffusynth_hip.h (fc = 0.95 min(1, rate), 32 zero crossings, Kaiser beta 12) is this package's definition.
 
@@ -16,6 +19,8 @@ Everything that is floored or rounded — frame counts, the phase vocoder's time
 int(start_sec * sr) — is computed here on the host in float64 and handed to the kernels as integers and tables.  No CPU fallback.
 """
 import bisect
+import collections
+import dataclasses
 import itertools
 import math
 
@@ -27,6 +32,7 @@ from . import _lib as L
 N_FFT, HOP = 4096, 1024
 _NO_GPU = "diffusynth_amd arranger runs on MI355X only (%s); no CPU fallback"
 _PV = L.PV
+_MX = L.MX
 
 
 def _require_cuda(t, what):
@@ -277,38 +283,194 @@ def mix_lists(starts, lengths, track_len):
     return ptr, np.array([e for p in per for e in p], dtype=np.int32)
 
 
+def _linspace_step(start, stop, n):
+    """numpy.linspace's step in float64; 0 for a segment of 0 or 1 samples (its single element is `start`)."""
+    return (float(stop) - float(start)) / (n - 1) if n > 1 else 0.0
+
+
+def shaped_rows(starts, offsets, note_lengths, gains, envelopes):
+    """The event table of ds_mix_notes_shaped, int32 (n, DS_MX_NI) with the five floats as fp32 bit patterns.  envelopes: one
+    (n_a, n_d, n_s, n_r, sustain) per event, or None for the weight g over the whole note (one sustain segment at level 1).  LEN is the
+    mixed length min(note, n_a + n_d + n_s + n_r); the steps and the gain are float64 here and fp32 in the table."""
+    n = len(starts)
+    gains = [1.0] * n if gains is None else [float(g) for g in _per_signal(gains, n, "mix_notes: gains")]
+    if envelopes is None:
+        envelopes = [(0, 0, ln, 0, 1.0) for ln in note_lengths]
+    if len(envelopes) != n:
+        raise ValueError(f"mix_notes: {len(envelopes)} envelopes for {n} events")
+    ev = np.zeros((n, _MX["DS_MX_NI"]), dtype=np.int32)
+    fv = ev.view(np.float32)
+    for e, (g, (na, nd, ns, nr, sus)) in enumerate(zip(gains, envelopes)):
+        seg = [int(v) for v in (na, nd, ns, nr)]
+        if min(seg) < 0 or seg != [na, nd, ns, nr] or not math.isfinite(sus) or not math.isfinite(g):
+            raise ValueError(f"mix_notes: event {e}: segment lengths must be integers >= 0, gain and sustain finite (got {(g, na, nd, ns, nr, sus)})")
+        if sum(seg) > 2 ** 31 - 1:
+            raise ValueError(f"mix_notes: event {e}: an envelope of {sum(seg)} samples (at most 2^31 - 1)")
+        ev[e, :_MX["DS_MX_NI_PLAIN"]] = (starts[e], offsets[e], min(note_lengths[e], sum(seg)))
+        ev[e, _MX["DS_MX_NA"]:_MX["DS_MX_NR"] + 1] = seg
+        fv[e, _MX["DS_MX_GAIN"]], fv[e, _MX["DS_MX_SUSTAIN"]] = g, sus
+        fv[e, _MX["DS_MX_STEP_A"]] = _linspace_step(0.0, 1.0, seg[0])
+        fv[e, _MX["DS_MX_STEP_D"]] = _linspace_step(1.0, sus, seg[1])
+        fv[e, _MX["DS_MX_STEP_R"]] = _linspace_step(sus, 0.0, seg[3])
+    return ev
+
+
 @torch.no_grad()
-def mix_notes(notes, events, track_len):
+def mix_notes(notes, events, track_len, *, gains=None, envelopes=None):
     """notes: list of 1-D fp32 CUDA tensors; events: (start sample, note index) in mixing order -> the (track_len,) fp32 track, every sample
-    the sum of the notes covering it in event order."""
+    the sum of the notes covering it in event order (ds_mix_notes).
+
+    gains (one float per event) and / or envelopes (one (n_a, n_d, n_s, n_r, sustain) per event: the segment lengths of adsr_envelope in
+    samples) select ds_mix_notes_shaped: every note sample is weighted by fl(g_e env_e(j)) as it is added, nothing per event is
+    materialised.  envelopes=None weights the whole note by g_e.  An event then ends with its envelope (the mixed length
+    min(len(note), n_a + n_d + n_s + n_r)), for the fit check and for the per-block lists alike."""
     sigs, _ = _as_list(notes, "mix_notes")
     lengths = [s.numel() for s in sigs]
     offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-    for start, i in events:
-        if start < 0 or start + lengths[i] > track_len:
-            raise ValueError(f"mix_notes: a note of {lengths[i]} samples at {start} does not fit a track of {track_len} samples")
-    if not events:
+    shaped = gains is not None or envelopes is not None
+    events = list(events)
+    mixed = [lengths[i] for _, i in events]              # the fit check first, on Python integers: nothing is narrowed to int32 before it
+    if envelopes is not None:
+        envelopes = list(envelopes)
+        if len(envelopes) != len(events):
+            raise ValueError(f"mix_notes: {len(envelopes)} envelopes for {len(events)} events")
+        mixed = [min(m, sum(env[:4])) for m, env in zip(mixed, envelopes)]
+    for (start, _), m in zip(events, mixed):
+        if start < 0 or start + m > track_len:
+            raise ValueError(f"mix_notes: a note of {m} samples at {start} does not fit a track of {track_len} samples")
+    if shaped:
+        ev = shaped_rows([s for s, _ in events], [offs[i] for _, i in events], [lengths[i] for _, i in events], gains, envelopes)
+    else:
+        ev = np.array([(s, offs[i], lengths[i]) for s, i in events], dtype=np.int32).reshape(-1, _MX["DS_MX_NI_PLAIN"])
+    if not events or track_len == 0:
         return torch.zeros(track_len, dtype=torch.float32, device=sigs[0].device if sigs else "cuda")
-    ev = np.array([(s, offs[i], lengths[i]) for s, i in events], dtype=np.int32)
-    ptr, lst = mix_lists(ev[:, 0].tolist(), ev[:, 2].tolist(), track_len)
+    ptr, lst = mix_lists(ev[:, _MX["DS_MX_START"]].tolist(), ev[:, _MX["DS_MX_LEN"]].tolist(), track_len)
     flat = sigs[0] if len(sigs) == 1 else torch.cat(sigs)
     host = np.concatenate([ev.reshape(-1), ptr, lst, np.zeros(1, np.int32)])
     tables = torch.from_numpy(host).to(flat.device)
     base = tables.data_ptr()
     track = torch.empty(track_len, dtype=torch.float32, device=flat.device)
-    L.call("ds_mix_notes", flat.data_ptr(), flat.numel(), base, len(ev), base + 4 * ev.size, base + 4 * (ev.size + ptr.size), len(lst), track.data_ptr(),
-           track_len, L.current_stream())
+    L.call("ds_mix_notes_shaped" if shaped else "ds_mix_notes", flat.data_ptr(), flat.numel(), base, len(ev), base + 4 * ev.size,
+           base + 4 * (ev.size + ptr.size), len(lst), track.data_ptr(), track_len, L.current_stream())
     return track
 
 
-def _mix_nodes(have, placed, n):
-    """have {node: tensor}; placed: (node, start sample) per event in mixing order -> the track (every distinct node handed over once)."""
+def _mix_nodes(have, placed, n, shape=None):
+    """have {node: tensor}; placed: (node, start sample) per event in mixing order -> the track (every distinct node handed over once).
+    shape: None or (gains, envelopes) per event for the shaped mix."""
     used, index = [], {}
     for node, _ in placed:
         if node not in index:
             index[node] = len(used)
             used.append(have[node])
-    return mix_notes(used, [(start, index[node]) for node, start in placed], n)
+    events = [(start, index[node]) for node, start in placed]
+    if shape is None:
+        return mix_notes(used, events, n)
+    return mix_notes(used, events, n, gains=shape[0], envelopes=shape[1])
+
+
+def _shape_arg(shape):
+    """The plain mix is called exactly as before the shaped one existed."""
+    return () if shape is None else (shape,)
+
+
+# ---------------------------------------------------------------------------------------------------- performed mode: envelope, velocity
+def adsr_segments(sample_rate, duration, attack_time, decay_time, sustain_level, release_time):
+    """The segment lengths of the reference's tools.adsr_envelope (tools.py:280-288), its int(...) expressions: (n_a, n_d, n_s, n_r); the
+    envelope is n_a + n_d + n_s + int(1.0 * sample_rate) samples long, zero behind the release."""
+    if not release_time <= 1.0:
+        raise ValueError("adsr_envelope: release_time > 1.0")
+    n_a, n_d, n_r = int(attack_time * sample_rate), int(decay_time * sample_rate), int(release_time * sample_rate)
+    return n_a, n_d, max(0, int(duration * sample_rate) - n_a - n_d), n_r
+
+
+@torch.no_grad()
+def adsr_envelope(signals, sample_rate, duration, attack_time, decay_time, sustain_level, release_time):
+    """The reference's tools.adsr_envelope on the device for one 1-D CUDA signal, a (B, L) tensor or a ragged list; duration and the four
+    envelope parameters a number or one per signal.  Per signal the result has n_a + n_d + n_s + int(1.0 * sample_rate) samples: the signal
+    cut or zero-extended to that length, times attack / decay / sustain / release (numpy's linspace per segment) and zero behind the
+    release.  One ds_mix_notes_shaped launch: one event per signal into the concatenated outputs.  fp32 in, fp32 out."""
+    single = isinstance(signals, torch.Tensor) and signals.dim() == 1
+    sigs, was_tensor = _as_list([signals] if single else signals, "adsr_envelope")
+    if not sigs:
+        return signals
+    n = len(sigs)
+    par = [_per_signal(v, n, "adsr_envelope") for v in (duration, attack_time, decay_time, sustain_level, release_time)]
+    envs, outs = [], []
+    for dur, at, dt, sus, rt in zip(*par):
+        seg = adsr_segments(sample_rate, dur, at, dt, sus, rt)
+        envs.append(seg + (float(sus),))
+        outs.append(seg[0] + seg[1] + seg[2] + int(1.0 * sample_rate))
+    if min(s.numel() for s in sigs) < 1 or sum(outs) < 1:
+        raise ValueError("adsr_envelope: an empty signal or an empty result")
+    starts = np.concatenate([[0], np.cumsum(outs)]).tolist()
+    flat = mix_notes(sigs, [(starts[i], i) for i in range(n)], starts[-1], envelopes=envs)
+    if single:
+        return flat
+    if was_tensor and len(set(outs)) == 1:
+        return flat.view(n, outs[0])
+    return [flat[o:o + m] for o, m in zip(starts, outs)]
+
+
+def _finite_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) and math.isfinite(v)
+
+
+@dataclasses.dataclass(frozen=True, kw_only=True)
+class Performance:
+    """How a `pairing="midi"` track is played (Track.render(perform=...)): velocity as level and the reference's ADSR envelope gated at
+    the real note-off.  gain = (velocity / 127) ** velocity_exponent (2: General MIDI's 40 log10(v / 127) dB; 0: every note at full level);
+    the envelope is adsr_envelope's with duration = the held time; a note is sampled for max(held, 0.75) rounded up to a multiple of
+    duration_step seconds (0.0625 s = one latent column at 16 kHz, so notes of one latent width share one sampled note)."""
+    velocity_exponent: float = 2.0
+    attack_time: float = 0.0
+    decay_time: float = 0.0
+    sustain_level: float = 1.0
+    release_time: float = 0.1
+    duration_step: float = 0.0625
+
+    def __post_init__(self):
+        for f in dataclasses.fields(self):
+            if not _finite_number(getattr(self, f.name)):
+                raise ValueError(f"Performance: {f.name} must be a finite number, not {getattr(self, f.name)!r}")
+        if self.velocity_exponent < 0 or self.attack_time < 0 or self.decay_time < 0 or self.release_time < 0:
+            raise ValueError("Performance: velocity_exponent, attack_time, decay_time and release_time must not be negative")
+        if not 0.0 <= self.sustain_level <= 1.0:
+            raise ValueError(f"Performance: sustain_level {self.sustain_level} outside [0, 1]")
+        if self.release_time > 1.0:
+            raise ValueError(f"Performance: release_time {self.release_time} > 1 (the sampled note's tail is 1 s)")
+        if not self.duration_step > 0:
+            raise ValueError(f"Performance: duration_step {self.duration_step} must be positive")
+
+    def gain(self, velocity):
+        return (velocity / 127.0) ** self.velocity_exponent
+
+    def sampled_duration(self, held):
+        """max(held, 0.75) rounded up to a multiple of duration_step; within 1e-9 steps above a multiple counts as that multiple."""
+        return math.ceil(max(held, 0.75) / self.duration_step - 1e-9) * self.duration_step
+
+    def envelope(self, held, sample_rate):
+        """mix_notes' envelope entry of a note held for `held` seconds."""
+        return adsr_segments(sample_rate, held, self.attack_time, self.decay_time, self.sustain_level, self.release_time) + (float(self.sustain_level),)
+
+
+def _check_perform(perform):
+    if perform is None or isinstance(perform, Performance):
+        return perform
+    raise ValueError(f"perform: None or a Performance, not {perform!r}")
+
+
+def tempo_map_of(tracks):
+    """The file's tempo map: the set_tempo messages of ALL tracks as (absolute tick, tempo), ordered by tick (track order, then message
+    order, within a tick: of several entries on one tick the last holds)."""
+    out = []
+    for track in tracks:
+        now = 0
+        for msg in track:
+            now += msg.time
+            if msg.type == "set_tempo":
+                out.append((now, msg.tempo))
+    return sorted(out, key=lambda tt: tt[0])
 
 
 # ---------------------------------------------------------------------------------------------------- tuned mode
@@ -347,15 +509,72 @@ def tick2second(tick, ticks_per_beat, tempo):
 
 
 class Track:
-    """The reference's Track for any iterable of mido-like messages (.type, .time, .is_meta, .note, .velocity, .tempo)."""
+    """The reference's Track for any iterable of mido-like messages (.type, .time, .is_meta, .note, .velocity, .tempo).
 
-    def __init__(self, track, ticks_per_beat, max_notes=100):
+    pairing="reference" (the default) is the reference's reading of the file, bit for bit: a closing note_on closes the LAST opened note,
+    velocities are the closing message's 0, meta deltas are dropped and a start is ticks x the tempo in force at the note.
+    pairing="midi" reads the file as written: every message advances the clock; a note_on with velocity > 0 opens a note of its
+    (channel, note) and a note_off or a note_on with velocity 0 closes the OLDEST open note of the same (channel, note) (an unmatched close is
+    ignored, a note still open at the end closes at the track's last tick); events are ordered by note-on tick, then message order, and
+    carry the opening velocity; seconds are the integral over tempo_map, a list of (absolute tick, tempo) (None: the track's own set_tempo
+    messages; tempo_map_of(tracks) for a file), 500 000 us per beat before its first entry."""
+
+    def __init__(self, track, ticks_per_beat, max_notes=100, *, pairing="reference", tempo_map=None):
+        if pairing not in ("reference", "midi"):
+            raise ValueError(f"Track: pairing \"reference\" or \"midi\", not {pairing!r}")
+        if pairing == "reference" and tempo_map is not None:
+            raise ValueError("Track: tempo_map needs pairing=\"midi\" (the reference pairing keeps the reference's tempo rule)")
         track = list(track)
         self._cum = None
+        self.pairing = pairing
         self.tempo_events = self._parse_tempo_events(track)
-        self.events = self._parse_note_events(track)
         self.ticks_per_beat = ticks_per_beat
         self.max_notes = int(max_notes)
+        if pairing == "midi":
+            self.events = self._parse_midi_events(track)
+            self._set_tempo_map(tempo_map_of([track]) if tempo_map is None else tempo_map)
+        else:
+            self.events = self._parse_note_events(track)
+
+    @staticmethod
+    def _parse_midi_events(track):
+        now, held, done = 0, collections.defaultdict(collections.deque), []
+        for order, msg in enumerate(track):
+            now += msg.time
+            if msg.type not in ("note_on", "note_off"):
+                continue
+            key = (getattr(msg, "channel", 0), msg.note)
+            if msg.type == "note_on" and msg.velocity > 0:
+                held[key].append((now, order, msg.velocity))
+            elif held[key]:
+                on, first, velocity = held[key].popleft()
+                done.append((on, first, NoteEvent(msg.note, velocity, on, now - on)))
+        for (_, note), queue in held.items():
+            done.extend((on, first, NoteEvent(note, velocity, on, now - on)) for on, first, velocity in queue)
+        return [e for _, _, e in sorted(done, key=lambda d: d[:2])]
+
+    def _set_tempo_map(self, tempo_map):
+        """Break points (tick, tempo, seconds at tick): the seconds summed segment by segment in float64."""
+        ticks, tempi = [0], [500000]
+        for tick, tempo in sorted(((int(t), int(u)) for t, u in tempo_map), key=lambda tt: tt[0]):
+            if tick < 0 or tempo <= 0:
+                raise ValueError(f"Track: tempo_map entry {(tick, tempo)}")
+            if tick == ticks[-1]:
+                tempi[-1] = tempo
+            else:
+                ticks.append(tick)
+                tempi.append(tempo)
+        secs = [0.0]
+        for i in range(1, len(ticks)):
+            secs.append(secs[-1] + tick2second(ticks[i] - ticks[i - 1], self.ticks_per_beat, tempi[i - 1]))
+        self.tempo_map = list(zip(ticks, tempi))
+        self._map = (ticks, tempi, secs)
+
+    def seconds(self, tick):
+        """pairing="midi": the time of an absolute tick, the integral of the tempo map."""
+        ticks, tempi, secs = self._map
+        i = bisect.bisect_right(ticks, tick) - 1
+        return secs[i] + tick2second(tick - ticks[i], self.ticks_per_beat, tempi[i])
 
     def _parse_tempo_events(self, track):
         # as written in the reference: a non-meta message re-states the DEFAULT tempo, so a track without set_tempo plays at 500 000 us per beat
@@ -396,22 +615,61 @@ class Track:
             total += e.duration * tick2second(1, self.ticks_per_beat, self._get_tempo_at(e.start_time))
         return total + 10
 
-    def schedule(self, sample_rate=16000):
-        """Host arithmetic of synthesize_track for the first max_notes events: (duration key, duration_sec, start_sample, note - 52) each."""
+    def schedule(self, sample_rate=16000, perform=None):
+        """Host arithmetic of synthesize_track for the first max_notes events: (duration key, duration_sec, start_sample, note - 52) each.
+        pairing="midi": start = int(seconds(on) * sample_rate), duration_sec = max(held, 0.75), with a Performance its sampled_duration."""
+        perform = self._check_perform(perform)
         out = []
+        if self.pairing == "midi":
+            for e, held in zip(self.events, self.held()):
+                dur = max(held, 0.75) if perform is None else perform.sampled_duration(held)
+                out.append((str(dur), dur, int(self.seconds(e.start_time) * sample_rate), e.note - 52))
+            return out
         for e in self.events[:self.max_notes]:
             spt = tick2second(1, self.ticks_per_beat, self._get_tempo_at(e.start_time))
             dur = max(e.duration * spt, 0.75)
             out.append((str(dur), dur, int(e.start_time * spt * sample_rate), e.note - 52))
         return out
 
-    def track_length(self, sample_rate=16000):
+    def _check_perform(self, perform):
+        perform = _check_perform(perform)
+        if perform is not None and self.pairing != "midi":
+            raise ValueError("Track: perform needs pairing=\"midi\" (the reference pairing has no velocities: every one is the closing message's 0)")
+        return perform
+
+    def held(self):
+        """pairing="midi": seconds from note-on to note-off (unfloored) of the first max_notes events."""
+        return [self.seconds(e.start_time + e.duration) - self.seconds(e.start_time) for e in self.events[:self.max_notes]]
+
+    def shape(self, sample_rate=16000, perform=None):
+        """(gains, envelopes) of the played events for mix_notes: velocity as level, the envelope gated at the real note-off."""
+        perform = self._check_perform(perform)
+        if perform is None:
+            return None
+        return ([perform.gain(e.velocity) for e in self.events[:self.max_notes]], [perform.envelope(h, sample_rate) for h in self.held()])
+
+    def mixed_lengths(self, note_lengths, sample_rate=16000, perform=None):
+        """pairing="midi": samples each played event adds to the track: its note's length {duration key: samples}, cut where its envelope ends."""
+        lens = [note_lengths[key] for key, _, _, _ in self.schedule(sample_rate, perform)]
+        shape = self.shape(sample_rate, perform)
+        return lens if shape is None else [min(n, sum(env[:4])) for n, env in zip(lens, shape[1])]
+
+    def track_length(self, sample_rate=16000, note_lengths=None, perform=None):
+        """pairing="reference": the reference's total time.  pairing="midi": the last sounding sample, max(start + mixed length) over the
+        played events; note_lengths {duration key: samples} is needed there."""
+        if self.pairing == "midi":
+            if note_lengths is None:
+                raise ValueError("Track.track_length: pairing=\"midi\" ends with its last sounding sample; give note_lengths {duration key: samples}")
+            ends = [s[2] + m for s, m in zip(self.schedule(sample_rate, perform), self.mixed_lengths(note_lengths, sample_rate, perform))]
+            return max(ends, default=0)
+        if note_lengths is not None or perform is not None:
+            raise ValueError("Track.track_length: note_lengths and perform need pairing=\"midi\"")
         return int(self._get_total_time() * sample_rate)
 
     last_pitches = None        # {duration key: MIDI pitch the note was taken to sit at, nan = unpitched} of the last tuned render
 
     @torch.no_grad()
-    def render(self, note_fn, sample_rate=16000, return_tensor=True, notes=None, *, tune=None):
+    def render(self, note_fn, sample_rate=16000, return_tensor=True, notes=None, *, tune=None, perform=None):
         """synthesize_track on the device.  note_fn(velocity, duration_sec) -> numpy array or tensor on either device, called once per distinct
         duration in event order (the reference's cache); notes: {duration key: tensor} sampled beforehand instead.  One peak normalisation,
         one tree of chains over the distinct (duration, note) pairs, one mix.
@@ -421,42 +679,51 @@ class Track:
         tune="detect": one pitch.estimate_pitch call over the normalised notes; a pitched note of detected pitch p_k is shifted by
         signed_chain(note - p_k), an unpitched one (noise, percussion) follows the reference's rule.  The chains are planned on the host in
         float64, so "detect" costs exactly one extra device -> host copy per render (a period and a count per distinct note).
-        last_pitches holds {duration key: p, p_k or nan} afterwards."""
+        last_pitches holds {duration key: p, p_k or nan} afterwards.
+
+        perform (a Performance; pairing="midi" only) changes the last stage alone: the mix weights every event by its velocity's gain and
+        by adsr_envelope's envelope of its held time (mix_notes(gains=, envelopes=)), and notes are sampled for the performed durations.
+        Normalisation, the chains and tune= are the same and compose with it."""
         tune = _check_tune(tune)
+        perform = self._check_perform(perform)
         if not torch.cuda.is_available():
             raise RuntimeError(_NO_GPU % "Track.render")
-        sched, n, raw = self._collect(note_fn, sample_rate, notes)
+        sched, n, raw, shape = self._collect(note_fn, sample_rate, notes, perform)
         if not sched:
             track = torch.zeros(n, dtype=torch.float32, device="cuda")
             return track if return_tensor else track.cpu().numpy()
         keys = list(raw)
         normed = dict(zip(keys, peak_normalize([raw[k] for k in keys])))
         if tune is None:
-            track = self._mix_reference(sched, n, normed)
+            track = self._mix_reference(sched, n, normed, shape)
         else:
-            track = self._mix_tuned(sched, n, normed, _source_pitches(tune, keys, normed, sample_rate))
+            track = self._mix_tuned(sched, n, normed, _source_pitches(tune, keys, normed, sample_rate), shape)
         return track if return_tensor else track.cpu().numpy()
 
-    def _collect(self, note_fn, sample_rate, notes):
-        """(schedule, track length, {duration key: the raw 1-D fp32 CUDA note}) with the fit check."""
-        sched = self.schedule(sample_rate)
-        n = self.track_length(sample_rate)
+    def _collect(self, note_fn, sample_rate, notes, perform=None):
+        """(schedule, track length, {duration key: the raw 1-D fp32 CUDA note}, mix shape or None).  pairing="reference": with the fit
+        check; pairing="midi": the track ends with its last sounding sample."""
+        sched = self.schedule(sample_rate, perform)
         raw = {}
         for (key, dur, _, _), e in zip(sched, self.events):
             if key not in raw:
                 s = notes[key] if notes is not None else note_fn(e.velocity, dur)
                 s = torch.from_numpy(np.ascontiguousarray(s)) if isinstance(s, np.ndarray) else s
                 raw[key] = s.detach().reshape(-1).float().cuda()
+        if self.pairing == "midi":
+            n = self.track_length(sample_rate, {key: s.numel() for key, s in raw.items()}, perform)
+            return sched, n, raw, self.shape(sample_rate, perform)
+        n = self.track_length(sample_rate)
         for key, _, start, _ in sched:
             if start + raw[key].numel() > n:
                 raise ValueError(f"Track: a note of {raw[key].numel()} samples at sample {start} ends past the track's {n} samples")
-        return sched, n, raw
+        return sched, n, raw, None
 
-    def _mix_reference(self, sched, n, normed):
+    def _mix_reference(self, sched, n, normed, shape=None):
         have = _run_tree(normed, [(key, total) for key, _, _, total in sched if total > 0])
-        return _mix_nodes(have, [((key, max(total, 0)), start) for key, _, start, total in sched], n)
+        return _mix_nodes(have, [((key, max(total, 0)), start) for key, _, start, total in sched], n, *_shape_arg(shape))
 
-    def _mix_tuned(self, sched, n, normed, pitches):
+    def _mix_tuned(self, sched, n, normed, pitches, shape=None):
         """pitches {duration key: MIDI pitch of the normalised note, nan = unpitched}: the signed tree and the mix."""
         self.last_pitches = {key: float(pitches[key]) for key in normed}
         totals = []
@@ -464,7 +731,7 @@ class Track:
             p = self.last_pitches[key]
             totals.append(max(total, 0) if math.isnan(p) else (total + 52) - p)
         have = _run_levels(normed, signed_tree([(key, t) for (key, _, _, _), t in zip(sched, totals)]))
-        return _mix_nodes(have, [((key, t if signed_chain(t) else 0), start) for (key, _, start, _), t in zip(sched, totals)], n)
+        return _mix_nodes(have, [((key, t if signed_chain(t) else 0), start) for (key, _, start, _), t in zip(sched, totals)], n, *_shape_arg(shape))
 
     def synthesize_track(self, diffSynthSampler, sample_rate=16000):
         """The reference's method: float32 numpy array."""
@@ -486,7 +753,7 @@ class DiffSynth:
 
     def __init__(self, instruments_configs, noise_prediction_model, VAE_quantizer, VAE_decoder, text_encoder, CLAP_tokenizer, device,
                  model_sample_rate=16000, timesteps=1000, channels=4, freq_resolution=512, time_resolution=256, VAE_scale=4, squared=False, *,
-                 condition=None, noise_device="philox", seed=None, tune=None):
+                 condition=None, noise_device="philox", seed=None, tune=None, pairing="reference", perform=None):
         self.noise_prediction_model, self.VAE_quantizer, self.VAE_decoder = noise_prediction_model, VAE_quantizer, VAE_decoder
         self.device, self.model_sample_rate, self.timesteps, self.channels = device, model_sample_rate, timesteps, channels
         self.freq_resolution, self.time_resolution, self.VAE_scale, self.squared = freq_resolution, time_resolution, VAE_scale, squared
@@ -495,6 +762,12 @@ class DiffSynth:
         self.instruments_configs = instruments_configs
         self.condition, self.noise_device, self.seed = condition, noise_device, seed
         self.tune = _check_tune(tune)                # Track.render's tune=, for every track of arrange / get_music
+        if pairing not in ("reference", "midi"):
+            raise ValueError(f"DiffSynth: pairing \"reference\" or \"midi\", not {pairing!r}")
+        self.pairing = pairing                       # Track's pairing=, for every track get_music builds (with the file's tempo map for "midi")
+        self.perform = _check_perform(perform)       # Track.render's perform=, for every track of arrange / get_music
+        if self.perform is not None and pairing != "midi":
+            raise ValueError("DiffSynth: perform needs pairing=\"midi\"")
         self.last_batcher = None
         self.last_pitches = None                     # {(instrument name, duration_sec): MIDI pitch or nan} of the last tuned arrange
 
@@ -554,58 +827,72 @@ class DiffSynth:
         return out
 
     @staticmethod
-    def wanted_notes(tracks, instrument_names, sample_rate=16000):
-        """The (instrument name, duration_sec) pair of every event the tracks will mix, in track and event order."""
-        return [(instrument_names[i], dur) for i, t in enumerate(tracks) for _, dur, _, _ in t.schedule(sample_rate)]
+    def wanted_notes(tracks, instrument_names, sample_rate=16000, perform=None):
+        """The (instrument name, duration_sec) pair of every event the tracks will mix, in track and event order (with a Performance: its
+        sampled durations)."""
+        return [(instrument_names[i], dur) for i, t in enumerate(tracks) for _, dur, _, _ in t.schedule(sample_rate, perform)]
 
     @torch.no_grad()
-    def arrange(self, tracks, instrument_names, notes, sample_rate=16000, *, tune=_UNSET):
+    def arrange(self, tracks, instrument_names, notes, sample_rate=16000, *, tune=_UNSET, perform=_UNSET):
         """The audio stage of get_music on sampled notes {(instrument name, duration_sec): signal}: normalise, chains and mix per track,
         then the sum of the zero-padded tracks (track_maker.py:316-322), all on the device.  tune (default: the constructor's) as in
         Track.render; with "detect" the distinct notes of ALL tracks are normalised in one launch and estimated in ONE estimate_pitch call
-        (one extra device -> host copy per call), and each track is then what its own tuned render gives, bit for bit."""
+        (one extra device -> host copy per call), and each track is then what its own tuned render gives, bit for bit.  perform (default:
+        the constructor's) as in Track.render, for tracks built with pairing="midi"; it composes with every form of tune."""
         tune = self.tune if tune is _UNSET else _check_tune(tune)
-        per_track = [{key: notes[(instrument_names[i], dur)] for key, dur, _, _ in t.schedule(sample_rate)} for i, t in enumerate(tracks)]
+        perform = self.perform if perform is _UNSET else _check_perform(perform)
+        per_track = [{key: notes[(instrument_names[i], dur)] for key, dur, _, _ in t.schedule(sample_rate, perform)} for i, t in enumerate(tracks)]
         if tune == "detect":
-            audios = self._arrange_detected(tracks, instrument_names, per_track, sample_rate)
+            audios = self._arrange_detected(tracks, instrument_names, per_track, sample_rate, perform)
         else:
-            audios = [t.render(None, sample_rate, notes=per_track[i], tune=tune) for i, t in enumerate(tracks)]
+            audios = [t.render(None, sample_rate, notes=per_track[i], tune=tune, perform=perform) for i, t in enumerate(tracks)]
             if tune is not None:
-                self.last_pitches = {(instrument_names[i], dur): tune for i, t in enumerate(tracks) for _, dur, _, _ in t.schedule(sample_rate)}
+                self.last_pitches = {(instrument_names[i], dur): tune for i, t in enumerate(tracks) for _, dur, _, _ in t.schedule(sample_rate, perform)}
         full = torch.zeros(max(a.numel() for a in audios), dtype=torch.float32, device=audios[0].device)
         for a in audios:                           # the reference's order: full_audio += pad(audio), track by track
             full[:a.numel()] += a
         return full
 
-    def _arrange_detected(self, tracks, instrument_names, per_track, sample_rate):
+    def _arrange_detected(self, tracks, instrument_names, per_track, sample_rate, perform=None):
         if not torch.cuda.is_available():
             raise RuntimeError(_NO_GPU % "DiffSynth.arrange")
-        parts = [t._collect(None, sample_rate, per_track[i]) for i, t in enumerate(tracks)]
+        parts = [t._collect(None, sample_rate, per_track[i], perform) for i, t in enumerate(tracks)]
         ids, flat = {}, []                                                      # every distinct (instrument, duration) note once
-        for i, (sched, _, raw) in enumerate(parts):
+        for i, (sched, _, raw, _) in enumerate(parts):
             for key, dur, _, _ in sched:
                 if (instrument_names[i], dur) not in ids:
                     ids[(instrument_names[i], dur)] = len(flat)
                     flat.append(raw[key])
-        audios = [torch.zeros(n, dtype=torch.float32, device="cuda") for _, n, _ in parts]
+        audios = [torch.zeros(n, dtype=torch.float32, device="cuda") for _, n, _, _ in parts]
         if not flat:
             self.last_pitches = {}
             return audios
         normed = peak_normalize(flat)
         midi = _source_pitches("detect", list(range(len(flat))), normed, sample_rate)
         self.last_pitches = {name_dur: midi[j] for name_dur, j in ids.items()}
-        for i, (sched, n, raw) in enumerate(parts):
+        for i, (sched, n, raw, shape) in enumerate(parts):
             if sched:
                 own = {key: ids[(instrument_names[i], dur)] for key, dur, _, _ in sched}
-                audios[i] = tracks[i]._mix_tuned(sched, n, {key: normed[j] for key, j in own.items()}, {key: midi[j] for key, j in own.items()})
+                audios[i] = tracks[i]._mix_tuned(sched, n, {key: normed[j] for key, j in own.items()}, {key: midi[j] for key, j in own.items()},
+                                                      *_shape_arg(shape))
         return audios
 
     @torch.no_grad()
-    def get_music(self, mid, instrument_names, sample_rate=16000, max_notes=100, return_tensor=False):
-        tracks = [Track(t, mid.ticks_per_beat, max_notes) for t in mid.tracks]
+    def get_music(self, mid, instrument_names, sample_rate=16000, max_notes=100, return_tensor=False, *, pairing=_UNSET, perform=_UNSET):
+        """The reference's get_music.  pairing / perform (default: the constructor's): with pairing="midi" every track is built with the
+        file's tempo map, tempo_map_of(mid.tracks), and the notes are sampled for the performed durations."""
+        pairing = self.pairing if pairing is _UNSET else pairing
+        perform = self.perform if perform is _UNSET else _check_perform(perform)
+        if perform is not None and pairing != "midi":
+            raise ValueError("DiffSynth.get_music: perform needs pairing=\"midi\"")
+        if pairing == "midi":
+            tempo_map = tempo_map_of(mid.tracks)
+            tracks = [Track(t, mid.ticks_per_beat, max_notes, pairing="midi", tempo_map=tempo_map) for t in mid.tracks]
+        else:
+            tracks = [Track(t, mid.ticks_per_beat, max_notes, pairing=pairing) for t in mid.tracks]
         assert len(tracks) <= len(
             instrument_names), f"len(tracks) = {len(tracks)} > {len(instrument_names)} = len(instrument_names)"
         assert sample_rate == self.model_sample_rate, "sample_rate != model_sample_rate"
-        wanted = self.wanted_notes(tracks, instrument_names, sample_rate)
-        full = self.arrange(tracks, instrument_names, self.sample_notes(wanted) if wanted else {}, sample_rate)
+        wanted = self.wanted_notes(tracks, instrument_names, sample_rate, perform)
+        full = self.arrange(tracks, instrument_names, self.sample_notes(wanted) if wanted else {}, sample_rate, perform=perform)
         return full if return_tensor else full.cpu().numpy()

@@ -25,6 +25,8 @@
 // ds_peak_normalize  max |x| per signal as per-block partials finished by every consumer wave, then x / max (IEEE division).
 // ds_mix_notes   track[s] = sum of the notes covering s in event order: a block walks the host-built list of the events that touch its 1024
 //                samples.  With fp32 notes this is bit for bit numpy's float32 += float64.
+// ds_mix_notes_shaped  the same walk and store with every sample weighted first: w = gain x ADSR envelope in closed form from the row's
+//                segment lengths, rounded to fp32 once, then fl(w x) and the fp32 sum in event order (velocity and gate of the performed mode).
 #include "common.hpp"
 
 namespace {
@@ -311,9 +313,56 @@ __global__ __launch_bounds__(256) void peak_divide_kernel(const float* x, const 
 
 // ------------------------------------------------------------------------------------------------ mix
 // ev [n_ev][3]: start sample in the track, offset of the note in `notes`, length.  Block b walks blk_ev[blk_ptr[b] .. blk_ptr[b + 1]):
-// the events that touch its samples, in event order.
+// the events that touch its samples, in event order.  SHAPED: rows of DS_MX_NI words (the same three first), every sample weighted by
+// w = gain * env(j) before it is added; `length` is then the mixed length min(note, envelope).
+
+// The envelope of one shaped row: segment ends and numpy's linspace per segment (start + k * step, the last element of a segment of more
+// than one sample exactly its stop; the host hands a step of 0 for segments of 0 or 1 samples).
+struct MixShape {
+    int b1, b2, b3, b4, na, nd, nr;
+    float gain, sus, sa, sd, sr, wsus;
+    bool ok;
+};
+__device__ __forceinline__ MixShape mix_shape(const int32_t* r) {
+    MixShape h;
+    h.na = DS_LD(int32_t, r + DS_MX_NA, DS_BX_AUX0);
+    h.nd = DS_LD(int32_t, r + DS_MX_ND, DS_BX_AUX0);
+    const int ns = DS_LD(int32_t, r + DS_MX_NS, DS_BX_AUX0);
+    h.nr = DS_LD(int32_t, r + DS_MX_NR, DS_BX_AUX0);
+    h.gain = DS_LD(float, r + DS_MX_GAIN, DS_BX_AUX0);
+    h.sus = DS_LD(float, r + DS_MX_SUSTAIN, DS_BX_AUX0);
+    h.sa = DS_LD(float, r + DS_MX_STEP_A, DS_BX_AUX0);
+    h.sd = DS_LD(float, r + DS_MX_STEP_D, DS_BX_AUX0);
+    h.sr = DS_LD(float, r + DS_MX_STEP_R, DS_BX_AUX0);
+    const long long end = (long long)h.na + h.nd + ns + h.nr;
+    h.ok = h.na >= 0 && h.nd >= 0 && ns >= 0 && h.nr >= 0 && end <= 0x7fffffffll;
+    h.b1 = h.na;
+    h.b2 = h.b1 + h.nd;
+    h.b3 = h.b2 + ns;
+    h.b4 = h.b3 + h.nr;
+    h.wsus = (float)((double)h.gain * (double)h.sus);
+    return h;
+}
+// gain * env(j), the product formed in fp64 from the fp32 table entries and rounded to fp32 ONCE.  Most of a held note is sustain, and a
+// wave's 64 consecutive samples are mostly all in it: that side is one value per event and whole waves skip the ramps (selects, no
+// further branches; the caller has the note loads in flight meanwhile).
+__device__ __forceinline__ float mix_weight(const MixShape& h, int j) {
+#pragma clang fp contract(off)                           // a + k * st as numpy forms it: a product, then a sum
+    if (j >= h.b2 && j < h.b3) return h.wsus;
+    const bool atk = j < h.b1, dec = !atk && j < h.b2, past = j >= h.b4, rel = !past && j >= h.b3 && !atk && !dec;
+    const int k = atk ? j : dec ? j - h.b1 : rel ? j - h.b3 : 0;
+    const int n = atk ? h.na : dec ? h.nd : rel ? h.nr : 0;                      // sustain and after: env = a + 0 * 0
+    const float a = atk || past ? 0.f : dec ? 1.f : h.sus;
+    const float st = atk ? h.sa : dec ? h.sd : rel ? h.sr : 0.f;
+    const float stop = atk ? 1.f : rel ? 0.f : h.sus;
+    const double env = (n > 1 && k == n - 1) ? (double)stop : (double)a + (double)k * (double)st;
+    return (float)((double)h.gain * env);
+}
+
+template <bool SHAPED>
 __global__ __launch_bounds__(256) void mix_notes_kernel(const float* notes, long long total_samples, const int32_t* ev, int n_ev, const int32_t* blk_ptr,
                                                         const int32_t* blk_ev, int n_blk_ev, float* track, int track_len) {
+    constexpr int NI = SHAPED ? DS_MX_NI : DS_MX_NI_PLAIN;
     const int s0 = blockIdx.x * RS_SPB + threadIdx.x;
     float acc[RS_SPB / 256];
 #pragma unroll
@@ -324,13 +373,35 @@ __global__ __launch_bounds__(256) void mix_notes_kernel(const float* notes, long
     for (int e = e0; e < e1; ++e) {
         const int id = DS_LD(int32_t, blk_ev + e, DS_BX_AUX2);
         if (id < 0 || id >= n_ev) continue;
-        const int start = DS_LD(int32_t, ev + 3 * id, DS_BX_AUX0), off = DS_LD(int32_t, ev + 3 * id + 1, DS_BX_AUX0),
-                  len = DS_LD(int32_t, ev + 3 * id + 2, DS_BX_AUX0);
-        if (!fits(off, len, total_samples)) continue;
+        const int32_t* r = ev + (size_t)NI * id;
+        const int start = DS_LD(int32_t, r + DS_MX_START, DS_BX_AUX0), off = DS_LD(int32_t, r + DS_MX_OFF, DS_BX_AUX0),
+                  len = DS_LD(int32_t, r + DS_MX_LEN, DS_BX_AUX0);
+        if constexpr (SHAPED) {
+            const MixShape h = mix_shape(r);             // the whole row before any test of it: early exits between its loads serialise them
+            if (!fits(off, len, total_samples) || !fits(start, len, track_len) || !h.ok) continue;
+            float x[RS_SPB / 256];
 #pragma unroll
-        for (int q = 0; q < RS_SPB / 256; ++q) {
-            const int j = s0 + q * 256 - start;
-            if (j >= 0 && j < len) acc[q] = __fadd_rn(acc[q], DS_LD(float, notes + off + j, DS_BX_SRC0));
+            for (int q = 0; q < RS_SPB / 256; ++q) {     // the note loads first, all in flight while the weights are formed
+                const int j = s0 + q * 256 - start;
+                x[q] = (j >= 0 && j < len) ? DS_LD(float, notes + off + j, DS_BX_SRC0) : 0.f;
+            }
+#pragma unroll
+            for (int q = 0; q < RS_SPB / 256; ++q) {
+                // HIP contracts by default, and __fmul_rn / __fadd_rn are inline `*` / `+` that carry their header's contraction with
+                // them: plain operators under the pragma, or the pair is one v_fma_f32 and the product is never rounded
+#pragma clang fp contract(off)
+                const int j = s0 + q * 256 - start;
+                const float p = mix_weight(h, j) * x[q];
+                const float sum = acc[q] + p;
+                acc[q] = (j >= 0 && j < len) ? sum : acc[q];
+            }
+        } else {
+            if (!fits(off, len, total_samples)) continue;
+#pragma unroll
+            for (int q = 0; q < RS_SPB / 256; ++q) {
+                const int j = s0 + q * 256 - start;
+                if (j >= 0 && j < len) acc[q] = __fadd_rn(acc[q], DS_LD(float, notes + off + j, DS_BX_SRC0));
+            }
         }
     }
 #pragma unroll
@@ -472,28 +543,40 @@ extern "C" int ds_peak_normalize(const float* x, const int32_t* tab, int n_signa
     return DS_OK;
 }
 
-extern "C" int ds_mix_notes(const float* notes, long long total_samples, const int32_t* ev, int n_events, const int32_t* blk_ptr, const int32_t* blk_ev,
-                            int n_blk_ev, float* track, int track_len, void* stream) {
+template <bool SHAPED>
+static int mix_launch(const char* name, const float* notes, long long total_samples, const int32_t* ev, int n_events, const int32_t* blk_ptr,
+                      const int32_t* blk_ev, int n_blk_ev, float* track, int track_len, void* stream) {
     DS_REQUIRE(notes && ev && blk_ptr && blk_ev && track && total_samples > 0 && n_events > 0 && n_blk_ev >= 0 && track_len > 0,
-               "mix_notes: bad args (total_samples=%lld n_events=%d n_blk_ev=%d track_len=%d)", total_samples, n_events, n_blk_ev, track_len);
-    DS_REQUIRE(total_samples <= MAX_ELEMS && track_len <= MAX_ELEMS - DS_MIX_BLOCK, "mix_notes: at most 2^31 - 1 samples");
-    if (!al4(notes) || !al4(ev) || !al4(blk_ptr) || !al4(blk_ev) || !al4(track)) DS_FAIL(DS_EALIGN, "mix_notes: every pointer must be 4-byte aligned");
+               "%s: bad args (total_samples=%lld n_events=%d n_blk_ev=%d track_len=%d)", name, total_samples, n_events, n_blk_ev, track_len);
+    DS_REQUIRE(total_samples <= MAX_ELEMS && track_len <= MAX_ELEMS - DS_MIX_BLOCK, "%s: at most 2^31 - 1 samples", name);
+    DS_REQUIRE(!SHAPED || n_events <= MAX_ELEMS / DS_MX_NI, "%s: at most %lld events", name, MAX_ELEMS / DS_MX_NI);
+    if (!al4(notes) || !al4(ev) || !al4(blk_ptr) || !al4(blk_ev) || !al4(track)) DS_FAIL(DS_EALIGN, "%s: every pointer must be 4-byte aligned", name);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nblk = (track_len + RS_SPB - 1) / RS_SPB;
 #if DS_BOUNDS
     {
-        DsBxHost h(DS_K_MIX_NOTES);
+        DsBxHost h(SHAPED ? DS_K_MIX_NOTES_SHAPED : DS_K_MIX_NOTES);
         h.set(DS_BX_SRC0, notes, total_samples * 4);
-        h.set(DS_BX_AUX0, ev, (long long)n_events * 12);
+        h.set(DS_BX_AUX0, ev, (long long)n_events * (SHAPED ? DS_MX_NI : DS_MX_NI_PLAIN) * 4);
         h.set(DS_BX_AUX1, blk_ptr, (long long)(nblk + 1) * 4);
         h.set(DS_BX_AUX2, blk_ev, (long long)(n_blk_ev > 0 ? n_blk_ev : 1) * 4);
         h.set(DS_BX_OUT, track, (long long)track_len * 4);
         h.publish(st);
     }
 #endif
-    hipLaunchKernelGGL(mix_notes_kernel, dim3(nblk), dim3(256), 0, st, notes, total_samples, ev, n_events, blk_ptr, blk_ev, n_blk_ev, track, track_len);
-    DS_CHECK_LAUNCH("mix_notes");
+    hipLaunchKernelGGL(mix_notes_kernel<SHAPED>, dim3(nblk), dim3(256), 0, st, notes, total_samples, ev, n_events, blk_ptr, blk_ev, n_blk_ev, track, track_len);
+    DS_CHECK_LAUNCH(name);
     return DS_OK;
+}
+
+extern "C" int ds_mix_notes(const float* notes, long long total_samples, const int32_t* ev, int n_events, const int32_t* blk_ptr, const int32_t* blk_ev,
+                            int n_blk_ev, float* track, int track_len, void* stream) {
+    return mix_launch<false>("mix_notes", notes, total_samples, ev, n_events, blk_ptr, blk_ev, n_blk_ev, track, track_len, stream);
+}
+
+extern "C" int ds_mix_notes_shaped(const float* notes, long long total_samples, const int32_t* ev, int n_events, const int32_t* blk_ptr,
+                                   const int32_t* blk_ev, int n_blk_ev, float* track, int track_len, void* stream) {
+    return mix_launch<true>("mix_notes_shaped", notes, total_samples, ev, n_events, blk_ptr, blk_ev, n_blk_ev, track, track_len, stream);
 }
 
 #if DS_BOUNDS

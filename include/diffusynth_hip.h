@@ -902,6 +902,37 @@ int ds_peak_normalize(const float* x, const int32_t* tab, int n_signals, int max
 #define DS_MIX_BLOCK 1024
 int ds_mix_notes(const float* notes, long long total_samples, const int32_t* ev, int n_events, const int32_t* blk_ptr, const int32_t* blk_ev,
                  int n_blk_ev, float* track, int track_len, void* stream);
+/* The shaped mix: track[s] = sum, in event order, of fl(w x) with x = the event's note sample j = s - START and w = fl(GAIN env(j)), one fp32
+ * weight per sample (the product is formed in fp64 from the fp32 row entries and rounded once); fl(w x) and the running sum are fp32
+ * roundings.  ev [n_events][DS_MX_NI] 32-bit words, the first three as ds_mix_notes' (DS_MX_NI_PLAIN), then four int32 segment lengths and
+ * five fp32 values.  env is an ADSR envelope in closed form:
+ *   attack   j in [0, NA)               linspace(0, 1, NA)[j]             = 0 + j STEP_A
+ *   decay    the next ND samples        linspace(1, SUSTAIN, ND)[k]       = 1 + k STEP_D
+ *   sustain  the next NS samples        SUSTAIN
+ *   release  the next NR samples        linspace(SUSTAIN, 0, NR)[k]       = SUSTAIN + k STEP_R
+ *   after                               0
+ * linspace is numpy's: start + k step with step = (stop - start) / (n - 1), the last element exactly stop when n > 1, the single element
+ * start when n = 1.  The steps (0 for n <= 1) and GAIN are the host's, computed in float64 and rounded to fp32.  LEN is the MIXED length
+ * min(note length, NA + ND + NS + NR): the host builds blk_ptr / blk_ev from it, so a block that only a note's silent remainder would touch
+ * does not walk the event.  A row with a negative segment length, whose note range [OFF, OFF + LEN) does not fit total_samples or whose
+ * track range [START, START + LEN) does not fit track_len reads and writes nothing.
+ * Block ownership, event order, no atomics and the same bits whatever else is in the launch: as ds_mix_notes. */
+#define DS_MX_START 0
+#define DS_MX_OFF 1
+#define DS_MX_LEN 2
+#define DS_MX_NI_PLAIN 3
+#define DS_MX_NA 3
+#define DS_MX_ND 4
+#define DS_MX_NS 5
+#define DS_MX_NR 6
+#define DS_MX_GAIN 7
+#define DS_MX_SUSTAIN 8
+#define DS_MX_STEP_A 9
+#define DS_MX_STEP_D 10
+#define DS_MX_STEP_R 11
+#define DS_MX_NI 12
+int ds_mix_notes_shaped(const float* notes, long long total_samples, const int32_t* ev, int n_events, const int32_t* blk_ptr,
+                        const int32_t* blk_ev, int n_blk_ev, float* track, int track_len, void* stream);
 
 /* ---------------------------------------------------------------- pitch detection (csrc/pitch.hip): YIN (de Cheveigne & Kawahara 2002), fp32
  * ds_yin_frames: period and aperiodicity of every frame of a ragged batch.  A signal is row s of tab, a device array

@@ -12,9 +12,15 @@ after one untimed warm-up pass, each figure the median of --repeat (>= 5) runs, 
   host_s       (--what host) the float64 RESTATEMENT of the same stage (tests/arranger_ref.py; not librosa, which is not installed) on the same
                notes, the nodes of a level spread over 16 processes: one run
 
+  mix          (--what mix, a run of its own) the performed mix next to the plain mix of the SAME schedule: Canon in D track 0 read with
+               pairing="midi", first 100 notes, the default Performance's sampled durations and starts, synthetic notes; ds_mix_notes over
+               the whole notes against ds_mix_notes_shaped with velocity gains and gated envelopes, alternating in one process, device
+               events around --mix-reps launches on tables already on the device, the median of --repeat windows each -> "mix" in the JSON;
+               --parent-lib OTHER.so times ds_mix_notes of another build of the library (the parent commit's) in the same alternation
+
 Prints one JSON line (-> profiles/arranger_bench.json).  --what audio --presets NAME is the run to put under a kernel trace.
 
-    python tools/arranger_bench.py [--what notes,audio,host] [--presets A,B] [--repeat 5]
+    python tools/arranger_bench.py [--what notes,audio,host,mix] [--presets A,B] [--repeat 5]
 """
 import argparse
 import json
@@ -36,7 +42,7 @@ from diffusynth_amd import arranger as A  # noqa: E402
 from diffusynth_amd.synth import synth_input, synth_state_dict  # noqa: E402
 
 PRESETS = ("Ode_to_Joy_Easy_variation", "Air_on_the_G_String", "Canon_in_D", "Arhbo", "Rrharil")
-KERNELS = {"ds_pv_stft": 1, "ds_pv_vocode": 1, "ds_pv_istft": 2, "ds_resample_sinc": 1, "ds_peak_normalize": 2, "ds_mix_notes": 1}
+KERNELS = {"ds_pv_stft": 1, "ds_pv_vocode": 1, "ds_pv_istft": 2, "ds_resample_sinc": 1, "ds_peak_normalize": 2, "ds_mix_notes": 1, "ds_mix_notes_shaped": 1}
 NAMES = ["organ", "string"]
 
 
@@ -81,14 +87,94 @@ def host_stage(tracks, notes, pool):
     return time.perf_counter() - t0, full
 
 
+def mix_bench(g, repeat, reps, parent_lib=None):
+    """us per launch of the plain and of the performed mix of one schedule, through the C entry points on tables built once."""
+    name = "Canon_in_D"
+    t = A.Track(R.messages(g[name + ".t0.msgs"]), int(g[name + ".tpb"]), 100, pairing="midi")
+    perform = A.Performance()
+    sched = t.schedule(perform=perform)
+    keys = list(dict.fromkeys(s[0] for s in sched))
+    dur = {s[0]: s[1] for s in sched}
+    notes = A.peak_normalize([torch.from_numpy(R.synthetic_note(dur[k])).cuda() for k in keys])
+    events = [(s[2], keys.index(s[0])) for s in sched]
+    n = max(start + notes[i].numel() for start, i in events)
+    gains, envs = t.shape(perform=perform)
+    out = {"preset": name, "events": len(events), "distinct_notes": len(keys), "track_samples": n, "launches_per_window": reps,
+           "plain": {"us": []}, "performed": {"us": []}}
+    # the tables of both launches, built once from the package's public pieces and kept on the device
+    lengths = [x.numel() for x in notes]
+    offs = np.concatenate([[0], np.cumsum(lengths)]).tolist()
+    starts, note_off, note_len = [s for s, _ in events], [offs[i] for _, i in events], [lengths[i] for _, i in events]
+    flat, st = torch.cat(notes), L.current_stream()
+    tracks, launches = {}, {}
+    for kind, fn, ev in (("plain", "ds_mix_notes", np.array(list(zip(starts, note_off, note_len)), dtype=np.int32)),
+                         ("performed", "ds_mix_notes_shaped", A.shaped_rows(starts, note_off, note_len, gains, envs))):
+        ptr, lst = A.mix_lists(ev[:, L.MX["DS_MX_START"]].tolist(), ev[:, L.MX["DS_MX_LEN"]].tolist(), n)
+        tables = torch.from_numpy(np.concatenate([ev.reshape(-1), ptr, lst, np.zeros(1, np.int32)])).cuda()
+        tracks[kind] = torch.empty(n, dtype=torch.float32, device="cuda")
+        base = tables.data_ptr()
+        launches[kind] = (tables, (fn, flat.data_ptr(), flat.numel(), base, len(ev), base + 4 * ev.size, base + 4 * (ev.size + ptr.size), len(lst),
+                                   tracks[kind].data_ptr(), n, st))
+        out[kind]["entry"], out[kind]["block_list_entries"] = fn, len(lst)
+        L.call(*launches[kind][1])                       # warm-up
+    kinds, run = ["plain", "performed"], {"plain": L.call, "performed": L.call}
+    if parent_lib:                                       # ds_mix_notes of ANOTHER build of the library (the parent commit's) on the plain tables
+        import ctypes
+        other = ctypes.CDLL(os.path.abspath(parent_lib))
+        other.ds_mix_notes.restype, other.ds_mix_notes.argtypes = L._PROTOS["ds_mix_notes"]
+        tracks["plain_parent"] = torch.empty(n, dtype=torch.float32, device="cuda")
+        args = list(launches["plain"][1])
+        args[8] = tracks["plain_parent"].data_ptr()
+        launches["plain_parent"] = (launches["plain"][0], tuple(args))
+
+        def call_other(fn, *a):
+            assert getattr(other, fn)(*a) == 0, fn
+        kinds, run["plain_parent"] = ["plain_parent"] + kinds, call_other
+        out["plain_parent"] = {"us": [], "entry": "ds_mix_notes", "library": os.path.basename(parent_lib), "block_list_entries": out["plain"]["block_list_entries"]}
+        call_other(*launches["plain_parent"][1])
+    for _ in range(repeat):                              # alternating
+        for kind in kinds:
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(reps):
+                run[kind](*launches[kind][1])
+            t1.record()
+            t1.synchronize()
+            out[kind]["us"].append(t0.elapsed_time(t1) * 1e3 / reps)
+    plain, shaped = tracks["plain"], tracks["performed"]
+    assert torch.equal(plain, A.mix_notes(notes, events, n)) and torch.equal(shaped, A.mix_notes(notes, events, n, gains=gains, envelopes=envs))
+    if parent_lib:
+        torch.cuda.synchronize()
+        out["plain_equals_parent_bit_for_bit"] = bool(torch.equal(tracks["plain_parent"], plain))
+    for row in [out[k] for k in kinds]:
+        row["us_median"], row["us_min"], row["us_max"] = round(statistics.median(row["us"]), 3), round(min(row["us"]), 3), round(max(row["us"]), 3)
+        del row["us"]
+    mixed = t.mixed_lengths({k: x.numel() for k, x in zip(keys, notes)}, perform=perform)
+    out["plain"]["note_samples_read"] = sum(notes[i].numel() for _, i in events)
+    out["performed"]["note_samples_read"] = sum(mixed)
+    out["performed_over_plain"] = round(out["performed"]["us_median"] / out["plain"]["us_median"], 4)
+    if parent_lib:
+        out["performed_over_plain_parent"] = round(out["performed"]["us_median"] / out["plain_parent"]["us_median"], 4)
+        out["plain_over_plain_parent"] = round(out["plain"]["us_median"] / out["plain_parent"]["us_median"], 4)
+    out["finite"] = bool(torch.isfinite(plain).all() and torch.isfinite(shaped).all())
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mix-reps", type=int, default=200)
+    ap.add_argument("--parent-lib", default=None, help="--what mix: another build of the library (the parent commit's) whose ds_mix_notes is timed beside")
     ap.add_argument("--what", default="notes,audio")
     ap.add_argument("--presets", default=",".join(PRESETS))
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     a = ap.parse_args()
     what = set(a.what.split(","))
+    if what == {"mix"}:
+        g = np.load(os.path.join(ROOT, "tests", "golden", "arranger.npz"), allow_pickle=False)
+        print(json.dumps({"tool": "tools/arranger_bench.py", "device": torch.cuda.get_device_name(0), "repeat": a.repeat,
+                          "mix": mix_bench(g, a.repeat, a.mix_reps, a.parent_lib)}), flush=True)
+        return
     pool = None
     if "host" in what:
         import multiprocessing as mp

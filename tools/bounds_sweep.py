@@ -69,6 +69,32 @@ def sweep_arranger(fail):
     report("mix_notes 9 events over 98 blocks + a 5-sample track", fail)
 
 
+def sweep_perform(fail):
+    """The performed mode (ds_mix_notes_shaped in csrc/arranger.hip): events from sample 0 to the last sample, an event with every segment
+    of 0 or 1 samples, envelopes longer and shorter than their notes, a 5-sample track, adsr_envelope on a ragged batch, and a performed
+    render on top."""
+    from diffusynth_amd import arranger as A
+    sigs = [synth_input("bs_prf%d" % n, (n,)).cuda() for n in (28416, 5000, 2048, 1, 77568)]
+    n = 100000
+    events = [(0, 0), (n - 5000, 1), (1023, 3), (n - 1, 3), (500, 2), (500, 2), (n - 77568, 4), (60000, 0), (0, 4), (3000, 1), (70000, 2)]
+    envs = [(1024, 1023, 1026, 4000, 0.6), (100, 200, 9000, 1600, 0.5), (1, 0, 0, 0, 1.0), (0, 1, 0, 0, 0.5), (1, 1, 1, 1, 0.25), (0, 0, 0, 0, 1.0),
+            (3000, 5000, 60000, 9568, 0.4), (0, 0, 28416, 0, 1.0), (0, 0, 100, 16000, 1.0), (10, 20, 500, 300, 0.7), (0, 1, 0, 1, 0.0)]
+    A.mix_notes(sigs, events, n, gains=[0.1 * (e + 1) for e in range(len(events))], envelopes=envs)
+    A.mix_notes(sigs, events, n, gains=[1.0] * len(events))
+    A.mix_notes(sigs[3:4], [(3, 0)], 5, gains=[0.5])
+    A.mix_notes(sigs[1:2], [(0, 0)], 5, envelopes=[(1, 1, 2, 1, 0.5)])
+    report("mix_notes shaped: 11 events over 98 blocks, whole-note gains, two 5-sample tracks", fail)
+    A.adsr_envelope(sigs, 16000, [0.5, 1.0, 0.001, 0.0, 6.0], [0.01, 0.0, 0.0, 0.0, 1.5], [0.05, 0.0, 0.0005, 0.0, 0.25], [0.7, 1.0, 0.5, 0.0, 0.3],
+                    [0.1, 0.0, 1.0, 0.5, 0.2])
+    A.adsr_envelope(sigs[3], 7, 0.0, 0.0, 0.0, 1.0, 0.0)
+    report("adsr_envelope ragged batch of 5 + a one-sample signal at 7 Hz", fail)
+    rows = [(0, 0, 60, 100, 0, 0), (0, 0, 64, 50, 0, 0), (0, 120, 64, 0, 0, 0), (1, 360, 60, 0, 0, 0), (0, 0, 45, 127, 0, 0), (0, 2400, 45, 0, 0, 0)]
+    import arranger_ref as R
+    t = A.Track(R.messages(rows), 480, pairing="midi")
+    t.render(lambda v, d: synth_input("bs_prf_note", (256 * (4 * int(16 * (d + 1)) - 1),)), perform=A.Performance(attack_time=0.01, release_time=0.3), tune=52.0)
+    report("Track.render pairing=midi, performed and tuned", fail)
+
+
 def sweep_pitch(fail):
     """Pitch detection (csrc/pitch.hip): a ragged batch with frameless signals at both ends and one sample either side of a frame, the
     largest LDS image (frame_length 2048, tau_max 1024, tau_min 2) with an odd hop, an odd frame length, the median at its frame limit, and
@@ -419,6 +445,10 @@ def main():
         sweep_ingest(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
         sys.exit(1 if fail else 0)
+    if "--only-perform" in sys.argv:
+        sweep_perform(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
     if "--only-arranger" in sys.argv:
         sweep_arranger(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
@@ -497,6 +527,7 @@ def main():
     sweep_ui_images(fail)
     # 5) the arranger's audio stage
     sweep_arranger(fail)
+    sweep_perform(fail)
     sweep_pitch(fail)
     sweep_ingest(fail)
     # 6) GroupNorm from raw partials in every kernel that reduces them, the depthwise families, the chains without ds_gn_finalize
