@@ -64,7 +64,9 @@ int ds_abi_version(void);
 /* ds_conv_params.flags (DS_CONV_TILE_HALO3_256x96): the split-precision tier runs a 3x3 convolution of fp32 tensors on bf16 matrix
  * cores as x*w ~ x_hi*w_hi + x_lo*w_hi + x_hi*w_lo (fp32 accumulate; x = x_hi + x_lo to 2^-17).
  *   SPLIT_IN : src0 = 2C bf16 channels per pixel (the hi plane, then the lo plane, of a C-channel fp32 tensor), C0 = 2C; wpk holds
- *              [W_hi | W_hi | W_lo] as 3C input channels (chunk-major, wk_order = 1; GroupNorm gain folded before the split)
+ *              3C input channels (chunk-major, wk_order = 1; GroupNorm gain folded before the split): per 32-channel source chunk c the
+ *              three virtual chunks [W_hi_c | W_lo_c | W_hi_c], the first two for the hi plane's chunk c, the third for the lo plane's
+ *              (diffusynth_amd/engine.py:split3_weight).  DS_CONV_TILE_QUAD_HALO3 takes [W_hi | W_hi | W_lo] over 3C input channels.
  *   OUT_SPLIT: the result is stored as hi / lo bf16 planes (out_C = 2 * Cout bf16 channels): the SPLIT_IN format of the next layer
  *   OUT_F32  : the result (+ an fp32 residual `res`) is stored as fp32 (out_C counts fp32 elements) */
 #define DS_CONV_F_SPLIT_IN 1

@@ -1,4 +1,5 @@
-"""Plain CPU helpers for the bit-exact tests (tests/test_hip_exact.py, tests/test_exact_ref_cpu.py).
+"""Plain CPU helpers for the bit-exact tests (tests/test_hip_exact.py, tests/test_exact_ref_cpu.py; the split-precision tier:
+tests/test_hip_exact_x3.py, tests/test_exact_ref_x3_cpu.py).
 
 The idea: when x, w, bias, residual and the GroupNorm numbers are small integers (or integers times a power of two) and
 sum |x| |w| stays below 2^24 units, every bf16 x bf16 product is exact in fp32 and every partial sum is exact IN ANY ORDER (MFMA
@@ -190,6 +191,124 @@ def gn_on_load(x, a, mean, gamma, beta, act, groups):
 
 def gelu64(x):
     return 0.5 * x.double() * (1.0 + torch.special.erf(x.double() * math.sqrt(0.5)))
+
+
+# ------------------------------------------------------------------------------------------------- split precision (tier bf16x3)
+# The split kernels compute x w as x_hi w_hi + x_lo w_hi + x_hi w_lo with hi = bf16(v), lo = bf16(v - hi) (include/diffusynth_hip.h).  On
+# integer operands (or integers times a power of two) hi and lo are such numbers too, each of the three bf16 x bf16 products is exact in
+# fp32, and with the sum of their magnitudes below 2^24 units every partial sum is exact in any order: the expected tensor is the float64
+# value of that documented algebra, WITHOUT the x_lo w_lo term, bit for bit.
+def split_hi_lo(v):
+    """(hi, lo) of an fp32-exact float64 tensor, both float64: hi = rne_bf16(v), lo = rne_bf16(v - hi) (v - hi is exact in fp32)."""
+    assert is_f32(v), "the value to split must be representable in fp32"
+    hi = rne_bf16(v).double()
+    return hi, rne_bf16(v.double() - hi).double()
+
+
+def trunc_split(v):
+    """A defective split: the lo plane truncated toward zero instead of rounded."""
+    hi = rne_bf16(v).double()
+    return hi, trunc_bf16(v.double() - hi).double()
+
+
+def store_split(v):
+    """The OUT_SPLIT store of the exact value v: the two bf16 planes (hi, lo)."""
+    hi, lo = split_hi_lo(v)
+    return hi.float().bfloat16(), lo.float().bfloat16()
+
+
+def split_profile(v):
+    """(share of elements with lo != 0, share with v != hi + lo: a third part is dropped, the lo plane really rounds, number of exact ties in
+    the rounding of hi, number of exact ties in the rounding of lo) of a float64 tensor of fp32-exact values."""
+    hi, lo = split_hi_lo(v)
+    tie = lambda t: int(((t.double().float().view(torch.int32) & 0xFFFF) == 0x8000).sum())
+    return (lo != 0).double().mean().item(), (v.double() != hi + lo).double().mean().item(), tie(v), tie(v.double() - hi)
+
+
+def check_lo_share(v, least, what):
+    share = split_profile(v)[0]
+    assert share >= least, "%s: only %.3f of the elements have lo != 0 (at least %.2f asked)" % (what, share, least)
+
+
+def check_out_split(v):
+    """An OUT_SPLIT case: at least 50 % of the expected v have lo != 0, at least 1 % drop a third part, with an exact tie in the lo rounding."""
+    s_lo, s_drop, _, ties = split_profile(v)
+    assert s_lo >= 0.5 and s_drop >= 0.01 and ties > 0, "split store: lo != 0 on %.3f, v != hi + lo on %.4f, %d ties: widen the operands" % (s_lo, s_drop, ties)
+
+
+def check_wide3(x):
+    """A 'wide3' operand: at least 5 % of the elements drop a third part, with exact ties among the lo roundings."""
+    _, s_drop, _, ties = split_profile(x)
+    assert s_drop >= 0.05 and ties > 0, "wide3: x != hi + lo on %.4f of the elements, %d ties" % (s_drop, ties)
+
+
+def _conv(x, w, stride, pad, transposed):
+    if transposed:
+        return F.conv_transpose2d(x.double(), w.double(), None, stride=stride, padding=pad)
+    return F.conv2d(x.double(), w.double(), None, stride=stride, padding=pad)
+
+
+def _fold_gain(w, gamma, transposed):
+    if gamma is None:
+        return w.double()
+    return w.double() * (gamma.view(-1, 1, 1, 1) if transposed else gamma.view(1, -1, 1, 1))
+
+
+def conv_x3_ref(x, w, stride=1, pad=0, transposed=False, x1=None, off=(0, 0), gamma=None, split=split_hi_lo):
+    """The three convolutions of the split parts, x_hi w_hi + x_lo w_hi + x_hi w_lo, over pad_and_concat(x, x1) (the zeros of the pad region
+    split into hi = lo = 0), the GroupNorm gain folded into w BEFORE the split (split3_weight, pack_x3_1x1, the header).  No bias."""
+    xin = pad_concat(x, x1, off, x.shape[2], x.shape[3])
+    xh, xl = split(xin)
+    wh, wl = split_hi_lo(_fold_gain(w, gamma, transposed))
+    return _conv(xh, wh, stride, pad, transposed) + _conv(xl, wh, stride, pad, transposed) + _conv(xh, wl, stride, pad, transposed)
+
+
+def x3_margin(x, w, *adds, stride=1, pad=0, transposed=False, x1=None, off=(0, 0), gamma=None, scale=1.0, scale_min=1.0, unit=1.0):
+    """exactness_margin over the three magnitude convolutions, sum |x_hi||w_hi| + |x_lo||w_hi| + |x_hi||w_lo|, times `scale`, plus the largest
+    |.| of every added term, in multiples of `unit`: the power of two of which every product of two operand parts, times the smallest factor
+    `scale_min` the sum is multiplied by, is a multiple (asserted), as every added term must be."""
+    xin = pad_concat(x, x1, off, x.shape[2], x.shape[3])
+    xh, xl = split_hi_lo(xin)
+    wh, wl = split_hi_lo(_fold_gain(w, gamma, transposed))
+    for a in (xh, xl):
+        for b in (wh, wl):
+            p = a.abs().max().item() and b.abs().max().item() and unit_of(a) * unit_of(b)
+            assert not p or p * scale_min >= unit, "a product of operand parts is a multiple of %g only, not of the unit %g" % (p * scale_min, unit)
+    m = _conv(xh.abs() + xl.abs(), wh.abs(), stride, pad, transposed) + _conv(xh.abs(), wl.abs(), stride, pad, transposed)
+    tot = scale * m.max().item()
+    for t in adds:
+        if t is not None:
+            tot += float(torch.as_tensor(t).abs().max())
+    return tot / unit
+
+
+def conv_x3_fold_ref(x, w, bias, gamma, beta, a, mean, pad=1, split=split_hi_lo):
+    """conv(GroupNorm(1, C)(x)) in the split kernels' algebra: a * acc + (t1[cls] - a*mean * t2[cls]) with acc = conv_x3_ref(x, w * gamma) and
+    the tables of conv_fold_ref, built from the UNSPLIT fp32 w, gamma and beta (ds_conv_fold_tables gets the same inputs).  a, mean: [B]."""
+    B, _, H, W = x.shape
+    acc = conv_x3_ref(x, w, pad=pad, gamma=gamma, split=split)
+    t1 = border_maps(w, beta, H, W, pad)
+    if bias is not None:
+        t1 = t1 + bias.view(-1, 1, 1)
+    t2 = border_maps(w, gamma, H, W, pad)
+    a4, m4 = a.view(B, 1, 1, 1), mean.view(B, 1, 1, 1)
+    return a4 * acc + (t1[None] - a4 * m4 * t2[None])
+
+
+def conv_x3_fold_margin(x, w, bias, gamma, beta, a, mean, res=None, pad=1, unit=0.25):
+    """The largest of the three sums that must stay below 2^24 for conv_x3_fold_ref to be exact in fp32, each in its own unit:
+      the epilogue  a * (three magnitude convolutions) + |t1| + |a mean t2| (+ |res|) in units of `unit`: x3_margin with the largest
+                    entries of the tables as added terms (the accumulator's partial sums are a part of it);
+      the tables    ds_conv_fold_tables sums w beta (+ bias) and w gamma in fp32, in an order of its own: sum |w||beta| + |bias| in units
+                    of 1 and sum |w||gamma| in units of 1/2 (gamma in {0.5, 1, 2})."""
+    _, _, H, W = x.shape
+    t1 = border_maps(w, beta, H, W, pad) + (bias.view(-1, 1, 1) if bias is not None else 0.0)
+    t2 = border_maps(w, gamma, H, W, pad) * (a * mean).abs().max()
+    epi = x3_margin(x, w, t1, t2, res, pad=pad, gamma=gamma, scale=a.max().item(), scale_min=a.min().item(), unit=unit)
+    assert unit_of(torch.cat([w.flatten(), beta, bias if bias is not None else beta[:0]])) == 1.0 and unit_of(gamma) >= 0.5
+    tab1 = border_maps(w.abs(), beta.abs(), H, W, pad).max().item() + (bias.abs().max().item() if bias is not None else 0.0)
+    tab2 = border_maps(w.abs(), gamma.abs(), H, W, pad).max().item() / 0.5
+    return max(epi, tab1, tab2)
 
 
 # ------------------------------------------------------------------------------------------------- the checker
