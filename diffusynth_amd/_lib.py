@@ -63,6 +63,7 @@ MX = _parse_defines(_HEADER_TEXT, "DS_MX_")     # ds_mix_notes / ds_mix_notes_sh
 YIN = _parse_defines(_HEADER_TEXT, "DS_YIN_")     # pitch signal table (field indices and row width), DS_YIN_MAX_W, DS_YIN_MAX_TAU
 PITCH_MAX_FRAMES = _parse_defines(_HEADER_TEXT, "DS_PITCH_")["DS_PITCH_MAX_FRAMES"]
 RP = _parse_defines(_HEADER_TEXT, "DS_RP_")     # ds_resample_poly signal table (field indices and row width), DS_RP_MAX_TAPS / _SPAN / _BLK
+IM = _parse_defines(_HEADER_TEXT, "DS_IM_")     # inpaint mask table (field indices and row width), DS_IM_RUN_IN
 TAIL = _parse_defines(_HEADER_TEXT, "DS_TAIL_")     # ds_text_tail: op codes
 ConvParams = _STRUCTS["ds_conv_params"]
 PackConvParams = _STRUCTS["ds_pack_conv_params"]
@@ -203,6 +204,10 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_text_embed": (C.c_int, [_P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _F, _P, _P]),
     "ds_text_attention": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "ds_text_tail": (C.c_int, [_P, _I, _I, _I, _F, _P, _P]),
+    "ds_mask_layers": (C.c_int, [_P, _P, _I, _I, C.c_longlong, C.c_longlong, _P, _P]),
+    "ds_mask_ws_bytes": (_SZ, [C.c_longlong]),
+    "ds_mask_prefilter": (C.c_int, [_P, _P, _I, _I, _I, C.c_longlong, _P, _P]),
+    "ds_mask_zoom": (C.c_int, [_P, _P, _I, _I, C.c_longlong, C.c_longlong, _P, _P, _P]),
     "ds_bounds_report": (C.c_int, [C.c_char_p, _I, _I]),
 }
 _UNCHECKED = {"ds_conv3x3_f32_n4_weight_floats", "ds_bounds_report", "ds_abi_version", "ds_conv_stats_parts", "ds_conv1x1_x3_stats_parts", "ds_conv_tile_bn", "ds_dwconv_stats_parts", "ds_attn_fused_stats_parts", "ds_attn_fused_generations", "ds_attn_fused_segments", "ds_attn_fused_segments_gen", "ds_attn_x3_stats_parts", "ds_attn_x3_segments", "ds_vq_attn_segments", "ds_conv3x3_c80_stats_slots", "ds_convt4x4_c80_stats_slots"}

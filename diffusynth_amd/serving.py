@@ -92,3 +92,86 @@ def sample_mixed_widths(model, requests, steps, *, timesteps=1000, height=128, c
             imgs, _ = h.result()
             out[i] = [im[0] for im in imgs] if return_trajectory else imgs[-1][0]
     return out
+
+
+@torch.no_grad()
+def inpaint_with_text(model, requests, steps, *, timesteps=1000, height=128, channels=4, sampler="ddim", cfg_scale=1.0,
+                      unconditional_condition=None, device="cuda", noise_device=None, noise_strategy="repeat", train_width=64,
+                      max_width=256, VAE_scale=4, time_resolution=256, guidance_rescale=0.0):
+    """The Inpaint tab for a list of requests (webUI/natural_language_guided_4/inpaint_with_text.py:193-267): each request's drawing
+    becomes its latent mask on the device (diffusynth_amd.inpaint_mask: all masks of the list in one pass of the three kernels) and its
+    ``inpaint_sample`` call is submitted to one SamplingBatcher with the one-channel plane as the mask.  requests: list of dicts
+
+        ``{"guide": (1, channels, height, W) latent (what InputBatch2Encode_STFT returned), "layers": the ImageEditor's layers``
+        ``(list of (H, W, 4) uint8) or "mask": the merged 2-D 0/1 array, "time_range": (begin, end) or None, "freq_range": (begin, end)``
+        ``or None, "inpaint_area": "masked" / "unmasked" (default), "condition": (label_dim,) tensor, "seed": int,``
+        ``"noising_strength": float in (0, 1], "batchsize": int (default 1), "width": int (default: the guide's)}``
+
+    The guide is what the sampler's noise strategy takes as one: ``train_width`` columns under "repeat", which the sampler repeats or
+    crops to the call's ``width`` as it does the noise (the arranger's notes: track_maker.py:245-269), ``max_width`` under
+    "non_repeat"; both are handed to the samplers built here.  The reference's tab has ``width = guide.shape[-1]`` (:249), the default here; the drawing is ``VAE_scale * width`` wide.
+
+    Returns a list (request order) of final latents ``(batchsize, channels, height, width)``.  A request is the reference's call: the guide
+    repeated ``batchsize`` times, the condition likewise, a sampler respaced to ``int(steps / noising_strength)`` steps (:244-246),
+    ``inpaint_sample(shape, seed=, noising_strength=, guide_img=, mask=, condition=, sampler=)`` on a ``DiffSynthSampler(timesteps,
+    height=, channels=, noise_strategy=)``.  The rules of ``sample_mixed_widths`` hold: the deterministic samplers only, every request is
+    checked before any device work (the drawings too: ``ValueError`` as ``latent_mask_from_layers`` raises it), requests of one width
+    share their U-Net steps."""
+    if sampler not in ("ddim", "dpmpp_2m"):
+        raise NotImplementedError("inpaint_with_text serves the deterministic samplers ('ddim', 'dpmpp_2m') only: per-step noise of a "
+                                  "shared bucket would make a request's result depend on its bucket mates (got %r)" % (sampler,))
+    if cfg_scale != 1.0 and unconditional_condition is None:
+        raise ValueError("cfg_scale != 1 needs an unconditional_condition (the negative-prompt embedding)")
+    from . import inpaint_mask as M
+    from .batching import SamplingBatcher
+    requests = list(requests)
+    if not requests:
+        return []
+    guide_width = int(train_width if noise_strategy == "repeat" else max_width)
+    shapes, counts = [], []
+    for i, r in enumerate(requests):
+        if ("layers" in r) == ("mask" in r):
+            raise ValueError("request %d carries either 'layers' or 'mask' (got %s)" % (i, "both" if "layers" in r else "neither"))
+        g, B = r["guide"], int(r.get("batchsize", 1))
+        if g.dim() != 4 or tuple(g.shape) != (1, channels, height, guide_width):
+            raise ValueError("request %d: the guide must be (1, %d, %d, %d) for noise_strategy %r, got %r"
+                             % (i, channels, height, guide_width, noise_strategy, tuple(g.shape)))
+        width = int(r.get("width", g.shape[3]))
+        if width < 1:
+            raise ValueError("request %d: width must be >= 1 (got %r)" % (i, r.get("width")))
+        if B < 1:
+            raise ValueError("request %d: batchsize must be >= 1 (got %r)" % (i, r.get("batchsize")))
+        ns = float(r["noising_strength"])
+        if not 0.0 < ns <= 1.0 or not 1 <= int(steps / ns) <= timesteps:
+            raise ValueError("request %d: noising_strength %r with %r steps gives %r sampler steps" % (i, r["noising_strength"], steps, ns and int(steps / ns)))
+        c = r.get("condition")
+        if c is None and cfg_scale != 1.0:
+            raise ValueError("request %d: classifier-free guidance (cfg_scale != 1) needs a condition" % i)
+        if c is not None and (not isinstance(c, torch.Tensor) or c.dim() != 1 or not c.is_floating_point()):
+            raise ValueError("request %d: the condition must be a (label_dim,) float tensor, got %r"
+                             % (i, tuple(c.shape) if isinstance(c, torch.Tensor) else type(c).__name__))
+        seed = r.get("seed")
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)):
+            raise ValueError("request %d: seed must be an int (got %r)" % (i, seed))
+        shapes.append((B, channels, height, width))
+        counts.append(int(steps / ns))
+    specs = M.plan_masks([r["layers"] if "layers" in r else r["mask"] for r in requests], shapes, VAE_scale, time_resolution,
+                         [r.get("time_range") for r in requests], [r.get("freq_range") for r in requests],
+                         [r.get("inpaint_area", "unmasked") for r in requests])
+    planes, _ = M.run_masks(specs, device)
+    rps = getattr(model, "rows_per_sample", lambda width: 1)
+    need = [s[0] * (2 if cfg_scale != 1.0 else 1) * int(rps(s[3])) for s in shapes]
+    b = SamplingBatcher(model, max_rows=max(128, max(need)))      # (the batcher's default, or what the largest request alone takes)
+    handles = []
+    for r, shape, n, plane in zip(requests, shapes, counts, planes):
+        s = DiffSynthSampler(timesteps, mute=True, device=device, height=height, channels=channels, noise_strategy=noise_strategy,
+                             train_width=train_width, max_width=max_width, max_batchsize=max(16, shape[0]), noise_device=noise_device)
+        s.respace(list(np.linspace(0, timesteps - 1, n, dtype=np.int32)))
+        if cfg_scale != 1.0 or guidance_rescale != 0.0:
+            s.activate_classifier_free_guidance(cfg_scale, unconditional_condition, guidance_rescale)
+        c = None if r.get("condition") is None else r["condition"].to(device).float()[None].repeat(shape[0], 1)
+        guide = r["guide"].to(device).float().repeat(shape[0], 1, 1, 1)
+        handles.append(b.submit(s, "inpaint_sample", shape, float(r["noising_strength"]), guide, plane, return_tensor=True, condition=c,
+                                sampler=sampler, seed=int(r["seed"])))
+    b.run()
+    return [h.result()[0][-1] for h in handles]

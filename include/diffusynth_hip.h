@@ -1040,6 +1040,62 @@ int ds_text_attention(const float* qkv, const void* mask, int mask_bytes, int B,
 #define DS_TAIL_L2NORM 2
 int ds_text_tail(const float* x, int B, int D, int op, float eps, float* out, void* stream);
 
+/* ---------------------------------------------------------------- the Inpaint tab's latent mask (csrc/inpaint_mask.hip)
+ * What webUI/natural_language_guided_4/inpaint_with_text.py:204-233 does on the host with numpy and scipy.ndimage.zoom: the drawn layers to
+ * the mask DiffSynthSampler.inpaint_sample takes, for a ragged batch of masks, one launch per stage.  A mask is row s of tab, a device array
+ * [n_masks][DS_IM_NI] int32 (offsets and counts in ELEMENTS):
+ *   LOFF, NL     its NL layers [H][W][4] uint8, back to back from PIXEL LOFF of layers (ds_mask_layers; NL = 0: the caller has put its
+ *                plane in place and ds_mask_layers leaves it alone)
+ *   POFF, H, W   its binary plane [H][W] uint8 in planes and its float64 coefficients in both halves of ws;  H, W >= 2
+ *   OOFF, HO, WO its latent plane [HO][WO] in out (and pre);  HO = round(H / VAE_scale), WO = round(W / VAE_scale) with Python's round
+ *                (half to even), computed by the caller;  HO, WO >= 2
+ *   R0, R1, C0, C1   the rectangle set to 1, rows [R0, R1) and columns [C0, C1) of the UNFLIPPED plane: the caller resolves
+ *                mask[int(fb):int(fe), int(tb tr / (4 VAE_scale)):int(te tr / (4 VAE_scale))] with slice(a, b).indices(n)
+ *   INV          1: the area is "masked", the plane is 1 - mask
+ * A row that does not fit the stated totals, or has H, W, HO or WO below 2, reads and writes nothing.
+ *
+ * ds_mask_layers (:205-206, :214): plane = any layer's alpha > 0 (for uint8 what mean(layers)[:, :, -1] > 0 is) as 0 / 1.  16-byte loads of
+ * four pixels where LOFF, POFF and H W are multiples of 4, single pixels otherwise.  max_px = the largest H W of the batch.
+ *
+ * ds_mask_prefilter (:218, the first half of zoom): scipy.ndimage's cubic B-spline prefilter of the plane, float64, along axis 0 and then
+ * along axis 1, whole-sample mirror boundary, pole z = sqrt(3) - 2, gain 6 per axis — spline_filter1d(x, 3, mode="mirror").  A line is
+ * cut into independent segments of 16 samples: c+[j] = 6 e[j] + z c+[j-1] from zero over the mirror-extended line e, from DS_IM_RUN_IN
+ * samples in front of the segment to DS_IM_RUN_IN behind it; c[s1] = -sum_k z^(k+1) c+[s1 + k] over the samples behind; downwards
+ * c[j] = z (c[j+1] - c+[j]).  What the missing history contributes is below |z|^DS_IM_RUN_IN = 1.3e-23 of the data.
+ * ws: ds_mask_ws_bytes(total_px) bytes = [2][total_px] float64; the coefficients are its second half.
+ *
+ * ds_mask_zoom (:218-233, the second half of zoom onwards): output (i, j) of the unflipped plane reads the coefficients at
+ * x = i ((H - 1) / (HO - 1)), y = j ((W - 1) / (WO - 1)) (the ratio formed first, as scipy forms it): 4 x 4 taps at floor - 1 ... floor + 2,
+ * cubic B-spline weights 2/3 - t^2 + |t|^3 / 2 (|t| < 1), (2 - |t|)^3 / 6 (1 <= |t| < 2), tap indices mirrored (-1 -> 1, n -> n - 2), all in
+ * float64.  scipy's mode "constant": an output whose coordinate is outside the input, x < 0 or x > H - 1 (y likewise), is cval = 0 — for
+ * about one size in ten (30, 63, 120, 252, 416 ...) the LAST output's product (HO - 1) ((H - 1) / (HO - 1)) rounds an ulp above H - 1, and
+ * the whole last row (or column) of the zoomed mask is 0.  The reference zooms the INT64 mask, so scipy rounds the value half away from zero (v > 0 ? floor(v + 0.5) : ceil(v - 0.5)) to
+ * -1 ... 2 and np.clip makes it 0 / 1: the mask is binary.  Then the rectangle, 1 - m if INV, and the flip:
+ * out[OOFF + (HO - 1 - i) WO + j] as fp32 — one (1, 1, HO, WO) plane per mask, which the sampler broadcasts over batch and channels.
+ * pre (NULL: not wanted) receives the float64 value before rounding at [OOFF + i WO + j].  max_out_px = the largest HO WO of the batch. */
+#define DS_IM_LOFF 0
+#define DS_IM_NL 1
+#define DS_IM_POFF 2
+#define DS_IM_H 3
+#define DS_IM_W 4
+#define DS_IM_OOFF 5
+#define DS_IM_HO 6
+#define DS_IM_WO 7
+#define DS_IM_R0 8
+#define DS_IM_R1 9
+#define DS_IM_C0 10
+#define DS_IM_C1 11
+#define DS_IM_INV 12
+#define DS_IM_NI 13
+#define DS_IM_RUN_IN 40
+int ds_mask_layers(const uint8_t* layers, const int32_t* tab, int n_masks, int max_px, long long total_layer_px, long long total_px,
+                   uint8_t* planes, void* stream);
+size_t ds_mask_ws_bytes(long long total_px);
+int ds_mask_prefilter(const uint8_t* planes, const int32_t* tab, int n_masks, int max_h, int max_w, long long total_px, double* ws,
+                      void* stream);
+int ds_mask_zoom(const double* ws, const int32_t* tab, int n_masks, int max_out_px, long long total_px, long long total_out, float* out,
+                 double* pre, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
