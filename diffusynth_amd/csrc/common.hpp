@@ -270,6 +270,8 @@ __device__ __forceinline__ float gelu_fast(float v) {
     const float e = __builtin_amdgcn_exp2f(v * v * (-0.5f * 1.44269504088896340736f));   // exp(-v^2 / 2)
     return fmaf(-0.5f * av, poly * t * e, fmaxf(v, 0.0f));
 }
+// v sigmoid(v) on v_exp_f32 / v_rcp_f32 (the decoder's swish on the way into a convolution; act_apply's SiLU below is the expf / true-division one)
+__device__ __forceinline__ float silu_fast(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * v)); }
 __device__ __forceinline__ float act_apply(float v, int act) {
     switch (act) {
         case DS_ACT_GELU: return gelu_fast(v);

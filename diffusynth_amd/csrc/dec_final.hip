@@ -32,8 +32,6 @@ struct ds_dec_final_params {
     float* out;
 };
 
-__device__ __forceinline__ float swish_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * v)); }
-
 // r04 (the first form: 1.2 - 1.35 ms at 64 x 512 x 256 x 80, VALU-bound in its staging pass):
 //   * staging walks the REAL halo pixels and the REAL 16-byte channel pieces: thread = (pixel of the iteration, piece), NT / NPC pixels per
 //     iteration, the piece fixed per thread (its 8 scales / shifts in registers) — 14 iterations of 8 values at C = 80 against 6 x 3 chunks
@@ -131,7 +129,7 @@ __global__ __launch_bounds__(NT, DS_MINBLK) void dec_final_kernel(const ds_dec_f
             for (int e = 0; e < 4; ++e) {
                 const float x0 = __uint_as_float(raw[it][e] << 16), x1 = __uint_as_float(raw[it][e] & 0xffff0000u);
                 const float v0 = fmaf(x0, sc[2 * e], sh[2 * e]), v1 = fmaf(x1, sc[2 * e + 1], sh[2 * e + 1]);
-                const ds_f32x2 s2 = {swish_f(v0), swish_f(v1)};
+                const ds_f32x2 s2 = {silu_fast(v0), silu_fast(v1)};
                 // zero padding applies to the convolution's INPUT (after the activation): pixels outside the image and pieces beyond C are zeros
                 o4[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(s2, ds_bf16x2)) & msk[it];
             }

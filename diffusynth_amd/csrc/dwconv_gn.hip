@@ -981,7 +981,7 @@ __global__ __launch_bounds__(256) void gn_apply_table_kernel(const ds_gn_apply_p
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             float y = fmaf(x[v], sc[v], sh[v]);
-            if (ACT == DS_ACT_SILU) y = y * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * y));
+            if (ACT == DS_ACT_SILU) y = silu_fast(y);
             else if (ACT == DS_ACT_RELU) y = fmaxf(y, 0.f);
             else if (ACT == DS_ACT_GELU) y = gelu_fast(y);
             y += cb[v];

@@ -128,13 +128,27 @@ def test_dec_final_kernel_matches_torch():
         assert err < 6e-3                      # swish(GroupNorm(x)) is rounded to bf16 before the 3x3 (as in the unfused bf16 path)
 
 
-@pytest.mark.parametrize("hw,cin", [((8, 32), 80), ((19, 45), 80), ((64, 64), 80), ((4, 32), 160), ((19, 45), 160), ((32, 64), 160)])
+# A block of the two 80-channel decoder kernels works through one RUN of a sample's tiles (4 rows x 32 columns each).  A sample has
+# tps = ceil(H / 4) * ceil(W / 32) tiles and rps = min(N // B, tps) runs (N = 256 for the 3x3, 128 / 64 for the 80 / 160 -> 80 upsample) of
+# per = ceil(tps / rps) tiles: run li = tiles [min(tps, li * per), min(tps, (li + 1) * per)).  At B = 3 every shape below has rps = tps: one
+# tile per run.  At 9 x 70 (tps = 3 x 3 = 9; the last row tile has 1 row, the last column tile 6 columns) and N // B = 6: per = 2, the runs
+# are [0, 2) [2, 4) [4, 6) [6, 8) [8, 9) [9, 9) = 2, 2, 2, 2, 1 and 0 tiles — the prefetching multi-tile pipeline, a single-tile run and an
+# empty run, which must still zero its statistics slots.
+C80_SIX_RUNS_HW = (9, 70)
+C80_SIX_RUNS_B = {"conv3x3": 40, 80: 20, 160: 10}
+
+
+@pytest.mark.parametrize("hw,cin", [((8, 32), 80), ((19, 45), 80), ((64, 64), 80), ((4, 32), 160), ((19, 45), 160), ((32, 64), 160),
+                                    (C80_SIX_RUNS_HW, 80), (C80_SIX_RUNS_HW, 160)])
 def test_convt4x4_c80_matches_torch(hw, cin):
     """ds_convt4x4_c80 (the decoder's last Upsample on its own kernel) == F.conv_transpose2d(x, w, b, stride 2, padding 1) on the bf16-rounded
-    operands: the four output phases, ragged tiles and image borders (zeros from the buffer range check), several tiles per block."""
+    operands: the four output phases, ragged tiles and image borders (zeros from the buffer range check); at 9 x 70 several tiles per block
+    and an empty run (see C80_SIX_RUNS_B)."""
     import hip_helpers as h
     from diffusynth_amd import _lib as L
-    B, (Hh, Ww) = 3, hw
+    B, (Hh, Ww) = (C80_SIX_RUNS_B[cin] if hw == C80_SIX_RUNS_HW else 3), hw
+    if hw == C80_SIX_RUNS_HW:
+        assert L.load().ds_convt4x4_c80_stats_slots(B, Hh, Ww, cin) == 6 * 16          # six runs per sample x (4 phases x 4 waves)
     x = synth_input("t_u8_x%s%d" % (hw, cin), (B, cin, Hh, Ww))
     w = synth_input("t_u8_w%d" % cin, (cin, 80, 4, 4), 0.05)
     b = synth_input("t_u8_b", (80,))
@@ -177,13 +191,17 @@ def test_convt4x4_c80_matches_torch(hw, cin):
     assert (ab2[:, :, 1].cpu().double() - rstd * gr.mean(dim=2)).abs().max() < 2e-2
 
 
-@pytest.mark.parametrize("hw,act", [((4, 32), "silu"), ((19, 45), "silu"), ((64, 64), "relu"), ((9, 70), None)])
+@pytest.mark.parametrize("hw,act", [((4, 32), "silu"), ((19, 45), "silu"), ((64, 64), "relu"), ((9, 70), None), (C80_SIX_RUNS_HW, "silu")])
 def test_conv3x3_c80_matches_torch(hw, act):
     """ds_conv3x3_c80 == x + conv3x3(act(GroupNorm(16, 80)(x))) + bias on the bf16-rounded operands (act None: plain convolution without the
-    norm and the residual): ragged tiles, borders (zero padding AFTER the activation), several tiles per block, sample changes inside a run."""
+    norm and the residual): ragged tiles, borders (zero padding AFTER the activation); 9 x 70 with the norm: several tiles per block and an
+    empty run (see C80_SIX_RUNS_B), in the fused form and as ds_gn_apply + ds_conv3x3_c80_res."""
     import hip_helpers as h
     from diffusynth_amd import _lib as L
-    B, (Hh, Ww), G = 3, hw, 16
+    six = hw == C80_SIX_RUNS_HW and act is not None
+    B, (Hh, Ww), G = (C80_SIX_RUNS_B["conv3x3"] if six else 3), hw, 16
+    if six:
+        assert L.load().ds_conv3x3_c80_stats_slots(B, Hh, Ww) == 6 * 4                 # six runs per sample x 4 waves
     x = synth_input("t_c8_x%s" % (hw,), (B, 80, Hh, Ww)) * 1.5 + 0.2
     w = synth_input("t_c8_w", (80, 80, 3, 3), 0.04)
     b = synth_input("t_c8_b", (80,))

@@ -12,6 +12,7 @@
 #           attn   attn_microbench.py over the four attention levels (-a e.g. "--batch 128 --iters 20")
 #           small  the small-batch workloads: BASELINE configs[1] (batch 16) and batch 1 (bench.py --workload config2 / config1)
 #           rows   row_kernels_bench.py: device time per launch of the sampler-step, window and STFT-blend kernels (-a e.g. "--reps 100")
+#           c80    c80_microbench.py: the decoder's 80-channel 3x3 (both forms) and its two upsamples at batch 64, 1500 launches per window (-a e.g. "--iters 3000")
 # Rounds are interleaved (A B A B), so drift of the box shows up as disagreement between rounds.
 # The first command that exits non-zero (a fault, a time limit, a result line that does not parse) ends the script with ITS status (the
 # first failing stage of the pipeline: 124 / 134 / 139 of the measured program, not the 1 of the parser that then got no line):
@@ -58,6 +59,8 @@ for r in $(seq 1 $R); do
         run_variant "$v" timeout -k 10 120 python tools/attn_microbench.py --c $c --n $n --batch 128 --iters 20 $EXTRA 2>&1 | tail -1; fail "$v" "${PIPESTATUS[@]}"; done; done;;
     rows)
       for v in "$@"; do run_variant "$v" timeout -k 10 120 python tools/row_kernels_bench.py $EXTRA 2>&1 | grep "^rows " | sed "s|^rows|$(printf '%-44s' "$v")|"; fail "$v" "${PIPESTATUS[@]}"; done;;
+    c80)
+      for v in "$@"; do run_variant "$v" timeout -k 10 180 python tools/c80_microbench.py --batch 64 --iters 1500 $EXTRA 2>&1 | grep "_c80 B=" | sed "s|^|$(printf '%-36s' "$v")|"; fail "$v" "${PIPESTATUS[@]}"; done;;
     *) echo "unknown mode $MODE"; exit 2;;
   esac
 done

@@ -12,12 +12,16 @@ sys.path.insert(0, ROOT)
 from diffusynth_amd import _lib as L  # noqa: E402
 
 
-def main():
+def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--h", type=int, default=256)
     ap.add_argument("--w", type=int, default=128)
-    a = ap.parse_args()
+    ap.add_argument("--iters", type=int, default=10, help="launches per timed window (an A/B wants windows of half a second: about 1500)")
+    return ap.parse_args()
+
+
+def main(a):
     B, H, W, G = a.batch, a.h, a.w, 16
     torch.manual_seed(0)
     x = torch.randn(B, H, W, 80, device="cuda").to(torch.bfloat16)
@@ -37,14 +41,14 @@ def main():
             L.call("ds_conv3x3_c80", x.data_ptr(), B, H, W, wp.data_ptr(), bias.data_ptr(), out.data_ptr(), *args, st)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        for _ in range(10):
+        for _ in range(a.iters):
             L.call("ds_conv3x3_c80", x.data_ptr(), B, H, W, wp.data_ptr(), bias.data_ptr(), out.data_ptr(), *args, st)
         e1.record()
         torch.cuda.synchronize()
-        print(f"conv3x3_c80 B={B} {H}x{W} {name}: {e0.elapsed_time(e1) * 100:.1f} us")
+        print(f"conv3x3_c80 B={B} {H}x{W} {name}: {e0.elapsed_time(e1) * 1000 / a.iters:.1f} us")
 
 
-def convt(B, H, W, cin):
+def convt(B, H, W, cin, iters=10):
     """ds_convt4x4_c80 (ConvTranspose2d(cin, 80, 4, 2, 1)) with GroupNorm + ReLU on load vs plain."""
     G = 16
     x = torch.randn(B, H, W, cin, device="cuda").to(torch.bfloat16)
@@ -62,14 +66,15 @@ def convt(B, H, W, cin):
             L.call("ds_convt4x4_c80", x.data_ptr(), B, H, W, cin, wp.data_ptr(), bias.data_ptr(), out.data_ptr(), *args, st)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        for _ in range(10):
+        for _ in range(iters):
             L.call("ds_convt4x4_c80", x.data_ptr(), B, H, W, cin, wp.data_ptr(), bias.data_ptr(), out.data_ptr(), *args, st)
         e1.record()
         torch.cuda.synchronize()
-        print(f"convt4x4_c80 B={B} {H}x{W} {cin}->80 {name}: {e0.elapsed_time(e1) * 100:.1f} us")
+        print(f"convt4x4_c80 B={B} {H}x{W} {cin}->80 {name}: {e0.elapsed_time(e1) * 1000 / iters:.1f} us")
 
 
 if __name__ == "__main__":
-    main()
-    convt(64, 256, 128, 80)
-    convt(64, 128, 64, 160)
+    args = parse()
+    main(args)
+    convt(args.batch, 256, 128, 80, args.iters)
+    convt(args.batch, 128, 64, 160, args.iters)

@@ -325,7 +325,71 @@ def row_kernels_cases():
         keep.clear()
 
 
-FAMILIES = {"attn_bf16": attn_bf16_cases, "row_kernels": row_kernels_cases}
+def conv_c80_cases():
+    """Every entry point of conv3x3_c80.hip and convt4x4_c80.hip: one tile per run (B = 1, 3), ragged tiles, and the batches at which a
+    9 x 70 sample is cut into runs of 2, 2, 2, 2, 1 and 0 tiles.  Outputs and statistics slots start from a fixed pattern, so an unwritten
+    pixel or slot shows in the digest."""
+    import torch
+    from diffusynth_amd import _lib as L
+    lib, st, G = L.load(), L.current_stream(), 16
+
+    def pat(dtype, *shape):
+        n = 1
+        for d in shape:
+            n *= d
+        return ((torch.arange(n, dtype=torch.float32, device="cuda") % 97) * 0.5 - 7.0).reshape(shape).to(dtype)
+
+    def gn_ab(x, B, HW, cin):
+        ab = torch.empty(B, G, 2, device="cuda")
+        L.call("ds_gn_stats", x.data_ptr(), L.DS_BF16, B, HW, cin, G, 1e-6, ab.data_ptr(), st)
+        return ab
+
+    g = torch.Generator().manual_seed(80)
+    w3 = (_rand(g, 80, 80, 3, 3) * 0.04).contiguous().cuda()
+    wp3 = pat(torch.bfloat16, lib.ds_conv3x3_c80_weight_elems())
+    L.call("ds_pack_conv3x3_c80", w3.data_ptr(), 80, 80, wp3.data_ptr(), st)
+    yield "pack_conv3x3_c80", dict(wpk=wp3)
+    wpt = {}
+    for cin in (80, 160):
+        wt = (_rand(g, cin, 80, 4, 4) * 0.05).contiguous().cuda()
+        wpt[cin] = pat(torch.bfloat16, lib.ds_convt4x4_c80_weight_elems(cin))
+        L.call("ds_pack_convt4x4_c80", wt.data_ptr(), cin, 80, wpt[cin].data_ptr(), st)
+        yield "pack_convt4x4_c80 cin=%d" % cin, dict(wpk=wpt[cin])
+    bias = _rand(g, 80).cuda()
+
+    for B, H, W in ((1, 3, 5), (3, 4, 32), (3, 19, 45), (40, 9, 70)):
+        x = (_rand(g, B, H, W, 80) * 1.5 + 0.2).bfloat16().cuda()
+        gamma, beta, ab = (_rand(g, 80) * 0.3 + 1.0).cuda(), (_rand(g, 80) * 0.5).cuda(), gn_ab(x, B, H * W, 80)
+        slots = lib.ds_conv3x3_c80_stats_slots(B, H, W)
+        norm = (ab.data_ptr(), G, gamma.data_ptr(), beta.data_ptr())
+        for form, args, stats in (("plain", (None, 0, None, None, L.ACT_NONE, 0), False), ("gn+silu+x+stats", norm + (L.ACT_SILU, 1), True),
+                                  ("gn+relu", norm + (L.ACT_RELU, 0), False)):
+            for b in (bias, None):
+                out, ws = pat(torch.bfloat16, B, H, W, 80), pat(torch.float32, B, slots, 80, 2)
+                L.call("ds_conv3x3_c80", x.data_ptr(), B, H, W, wp3.data_ptr(), b.data_ptr() if b is not None else None, out.data_ptr(), *args,
+                       ws.data_ptr() if stats else None, st)
+                yield "conv3x3_c80 B=%d HxW=%dx%d %s bias=%d" % (B, H, W, form, b is not None), dict(out=out, stats_ws=ws)
+        for b in (bias, None):
+            res = (_rand(g, B, H, W, 80) * 1.5).bfloat16().cuda()
+            out, ws = pat(torch.bfloat16, B, H, W, 80), pat(torch.float32, B, slots, 80, 2)
+            L.call("ds_conv3x3_c80_res", x.data_ptr(), res.data_ptr(), B, H, W, wp3.data_ptr(), b.data_ptr() if b is not None else None, out.data_ptr(),
+                   ws.data_ptr(), st)
+            yield "conv3x3_c80_res B=%d HxW=%dx%d bias=%d" % (B, H, W, b is not None), dict(out=out, stats_ws=ws)
+
+    for cin, shapes in ((80, ((3, 8, 32), (3, 19, 45), (20, 9, 70))), (160, ((3, 4, 32), (3, 19, 45), (10, 9, 70)))):
+        for B, H, W in shapes:
+            x = (_rand(g, B, H, W, cin) * 1.5 + 0.2).bfloat16().cuda()
+            gamma, beta, ab = (_rand(g, cin) * 0.3 + 1.0).cuda(), (_rand(g, cin) * 0.5).cuda(), gn_ab(x, B, H * W, cin)
+            slots = lib.ds_convt4x4_c80_stats_slots(B, H, W, cin)
+            for form, args, stats in (("plain", (None, 0, None, None), False), ("gn+stats", (ab.data_ptr(), G, gamma.data_ptr(), beta.data_ptr()), True)):
+                for b in (bias, None):
+                    out, ws = pat(torch.bfloat16, B, 2 * H, 2 * W, 80), pat(torch.float32, B, slots, 80, 2)
+                    L.call("ds_convt4x4_c80", x.data_ptr(), B, H, W, cin, wpt[cin].data_ptr(), b.data_ptr() if b is not None else None, out.data_ptr(),
+                           *args, ws.data_ptr() if stats else None, st)
+                    yield "convt4x4_c80 cin=%d B=%d HxW=%dx%d %s bias=%d" % (cin, B, H, W, form, b is not None), dict(out=out, stats_ws=ws)
+
+
+FAMILIES = {"attn_bf16": attn_bf16_cases, "row_kernels": row_kernels_cases, "conv_c80": conv_c80_cases}
 
 
 def child(family):
