@@ -12,6 +12,8 @@ pitch.estimate_pitch detects; signed chains through the same tree.
 Opt-in (`pairing="midi"`, `perform=Performance(...)`, off by default): play the file as written — every close paired with the oldest
 open note of its pitch, the tempo map integrated, velocity as level and the reference's own ADSR envelope (tools.adsr_envelope) gated at
 the real note-off, both applied inside the mix (ds_mix_notes_shaped).
+Opt-in (`master=Mastering(...)`, off by default): an RMS gain and a peak-hold look-ahead limiter behind the mix (ds_master_gain,
+ds_master_limit; include/diffusynth_hip.h has the arithmetic), once per render, in arrange / get_music once on the sum of the tracks.
 Different on purpose: the resampler.  librosa's default (soxr_hq) is a closed third-party design; the windowed sinc of
 include/diffusynth_hip.h (fc = 0.95 min(1, rate), 32 zero crossings, Kaiser beta 12) is this package's definition.
 
@@ -33,6 +35,7 @@ N_FFT, HOP = 4096, 1024
 _NO_GPU = "diffusynth_amd arranger runs on MI355X only (%s); no CPU fallback"
 _PV = L.PV
 _MX = L.MX
+_MS = L.MS
 
 
 def _require_cuda(t, what):
@@ -473,6 +476,119 @@ def tempo_map_of(tracks):
     return sorted(out, key=lambda tt: tt[0])
 
 
+# ---------------------------------------------------------------------------------------------------- mastering: RMS gain, limiter
+@dataclasses.dataclass(frozen=True, kw_only=True)
+class Mastering:
+    """The stage behind a mix (master(), Track.render(master=...), DiffSynth(master=...)): a gain that takes the signal to target_rms (at
+    most max_gain; None: no gain), then a limiter that keeps |y| <= ceiling: the gain a sample needs is held for `hold` seconds behind it,
+    reached `lookahead` seconds ahead of it and smoothed by a moving average of 2 lookahead + 1 samples, so it never exceeds what any sample
+    needs (include/diffusynth_hip.h).  Times are floored to samples as int(t * sample_rate).  The defaults are choices, not
+    measurements: the reference's tools.rms_normalize default, 20 dB, -1 dBFS, 5 ms and 50 ms."""
+    target_rms: float = 0.1
+    max_gain: float = 10.0
+    ceiling: float = 10 ** (-1 / 20)
+    lookahead: float = 0.005
+    hold: float = 0.05
+
+    def __post_init__(self):
+        for f in dataclasses.fields(self):
+            v = getattr(self, f.name)
+            if not (_finite_number(v) or (f.name == "target_rms" and v is None)):
+                raise ValueError(f"Mastering: {f.name} must be a finite number, not {v!r}")
+        for name in ("target_rms", "max_gain"):                 # (the kernels take them as fp32)
+            v = getattr(self, name)
+            if v is not None and not (v > 0 and 0 < float(np.float32(v)) < math.inf):
+                raise ValueError(f"Mastering: {name} must be positive (and a finite, non-zero fp32 value), not {v!r}")
+        if not (0.0 < self.ceiling <= 1.0 and float(np.float32(self.ceiling)) > 0):
+            raise ValueError(f"Mastering: ceiling {self.ceiling} outside (0, 1]")
+        if self.lookahead < 0:
+            raise ValueError(f"Mastering: lookahead {self.lookahead} must not be negative")
+        if self.hold < self.lookahead:
+            raise ValueError(f"Mastering: hold {self.hold} < lookahead {self.lookahead} (the hold covers the look-ahead: that is why the gain never exceeds what a sample needs)")
+
+    def samples(self, sample_rate):
+        """(A, R): lookahead and hold in samples, floored; ValueError above the kernels' caps."""
+        if not isinstance(sample_rate, (int, np.integer)) or isinstance(sample_rate, (bool, np.bool_)) or sample_rate <= 0:
+            raise ValueError(f"master: sample_rate must be a positive int, not {sample_rate!r}")
+        a, r = int(self.lookahead * int(sample_rate)), int(self.hold * int(sample_rate))
+        if a > _MS["DS_MS_MAX_LOOKAHEAD"]:
+            raise ValueError(f"master: lookahead {self.lookahead} s is {a} samples at {sample_rate} Hz (at most {_MS['DS_MS_MAX_LOOKAHEAD']})")
+        if r > _MS["DS_MS_MAX_HOLD"]:
+            raise ValueError(f"master: hold {self.hold} s is {r} samples at {sample_rate} Hz (at most {_MS['DS_MS_MAX_HOLD']})")
+        return a, r
+
+
+class MasterStats(collections.namedtuple("MasterStats", "gain rms peak min_gain limited")):
+    """Per signal, as device tensors (reading them is the caller's copy): the gain applied, the input's RMS and peak (fp32), the smallest
+    limiter gain and the number of samples whose limiter gain is below 1 (int32)."""
+    __slots__ = ()
+
+
+def _check_master(master):
+    if master is None or isinstance(master, Mastering):
+        return master
+    raise ValueError(f"master: None or a Mastering, not {master!r}")
+
+
+@torch.no_grad()
+def master(signals, mastering=Mastering(), *, sample_rate=16000, pcm16=False, return_stats=False):
+    """Gain and limiter (Mastering) for one 1-D CUDA tensor, a (B, L) tensor or a list of 1-D tensors of different lengths, each signal by
+    itself -> the same container, fp32, or int16 = rint(y * 32767) with pcm16=True; with return_stats=True (result, MasterStats).
+    One table upload, ds_master_gain and ds_master_limit, no device -> host copy.  A signal's result is the same bits alone and in a batch."""
+    if not isinstance(mastering, Mastering):
+        raise ValueError(f"master: mastering must be a Mastering, not {mastering!r}")
+    a, r = mastering.samples(sample_rate)
+    single = isinstance(signals, torch.Tensor) and signals.dim() == 1
+    was_tensor = isinstance(signals, torch.Tensor) and not single
+    if was_tensor and signals.dim() != 2:
+        raise ValueError("master: signals: expected a 1-D tensor, a (B, L) tensor or a list of 1-D tensors")
+    sigs = [signals] if single else list(signals)
+    if not sigs:
+        raise ValueError("master: signals: no signals")
+    for s in sigs:
+        if not isinstance(s, torch.Tensor) or s.dim() != 1:
+            raise ValueError("master: signals: expected a 1-D tensor, a (B, L) tensor or a list of 1-D tensors")
+        if s.numel() < 1:
+            raise ValueError("master: signals: an empty signal")
+        if s.numel() > _MS["DS_MS_MAX_LEN"]:
+            raise ValueError(f"master: signals: a signal of {s.numel()} samples (at most 2^24 = {_MS['DS_MS_MAX_LEN']})")
+    for s in sigs:
+        _require_cuda(s, "master")
+    sigs = [s.detach().float().contiguous() for s in sigs]
+    lengths = [s.numel() for s in sigs]
+    n, max_len = len(sigs), max(lengths)
+    tab = _flat_table(lengths)
+    x = sigs[0] if n == 1 else torch.cat(sigs)
+    dev = x.device
+    dtab = torch.from_numpy(tab.reshape(-1)).to(dev)
+    ws = torch.empty(L.load().ds_master_ws_bytes(n, max_len) // 4, dtype=torch.float32, device=dev)      # (the allocator aligns far beyond 8 bytes)
+    stats = torch.empty((n, _MS["DS_MS_NS"]), dtype=torch.float32, device=dev)
+    limited = torch.empty(n, dtype=torch.int32, device=dev)
+    out = torch.empty(x.numel(), dtype=torch.float32, device=dev)
+    pcm = torch.empty(x.numel(), dtype=torch.int16, device=dev) if pcm16 else None
+    target = 0.0 if mastering.target_rms is None else float(np.float32(mastering.target_rms))
+    st = L.current_stream()
+    L.call("ds_master_gain", x.data_ptr(), dtab.data_ptr(), n, max_len, x.numel(), target, float(np.float32(mastering.max_gain)), ws.data_ptr(),
+           stats.data_ptr(), limited.data_ptr(), st)
+    L.call("ds_master_limit", x.data_ptr(), dtab.data_ptr(), n, max_len, x.numel(), float(np.float32(mastering.ceiling)), a, r, stats.data_ptr(),
+           limited.data_ptr(), out.data_ptr(), L.ptr(pcm), st)
+    res = pcm if pcm16 else out
+    if was_tensor:
+        res = res.view(n, lengths[0])
+    elif not single:
+        res = [res[o:o + m] for o, m in zip(tab[:, _PV["DS_PV_XOFF"]].tolist(), lengths)]
+    if not return_stats:
+        return res
+    return res, MasterStats(*(stats[:, _MS[k]] for k in ("DS_MS_GAIN", "DS_MS_RMS", "DS_MS_PEAK", "DS_MS_MIN_GAIN")), limited)
+
+
+def _mastered(track, mastering, sample_rate, pcm16=False):
+    """(track or its mastered form, MasterStats or None); an empty track has nothing to master."""
+    if mastering is None or track.numel() == 0:
+        return (track.to(torch.int16) if pcm16 else track), None
+    return master(track, mastering, sample_rate=sample_rate, pcm16=pcm16, return_stats=True)
+
+
 # ---------------------------------------------------------------------------------------------------- tuned mode
 def _check_tune(tune):
     """None, "detect" or a finite real number (returned as float); anything else is a ValueError, before any other work."""
@@ -668,8 +784,10 @@ class Track:
 
     last_pitches = None        # {duration key: MIDI pitch the note was taken to sit at, nan = unpitched} of the last tuned render
 
+    last_master = None         # MasterStats of the last mastered render
+
     @torch.no_grad()
-    def render(self, note_fn, sample_rate=16000, return_tensor=True, notes=None, *, tune=None, perform=None):
+    def render(self, note_fn, sample_rate=16000, return_tensor=True, notes=None, *, tune=None, perform=None, master=None):
         """synthesize_track on the device.  note_fn(velocity, duration_sec) -> numpy array or tensor on either device, called once per distinct
         duration in event order (the reference's cache); notes: {duration key: tensor} sampled beforehand instead.  One peak normalisation,
         one tree of chains over the distinct (duration, note) pairs, one mix.
@@ -683,21 +801,29 @@ class Track:
 
         perform (a Performance; pairing="midi" only) changes the last stage alone: the mix weights every event by its velocity's gain and
         by adsr_envelope's envelope of its held time (mix_notes(gains=, envelopes=)), and notes are sampled for the performed durations.
-        Normalisation, the chains and tune= are the same and compose with it."""
+        Normalisation, the chains and tune= are the same and compose with it.
+
+        master (a Mastering) adds one stage behind the mix: master(track, mastering, sample_rate=sample_rate), bit for bit; last_master
+        holds its MasterStats.  None (the default) is the render without it."""
         tune = _check_tune(tune)
         perform = self._check_perform(perform)
+        master = _check_master(master)
+        if master is not None:
+            master.samples(sample_rate)            # its refusals come before any device work
         if not torch.cuda.is_available():
             raise RuntimeError(_NO_GPU % "Track.render")
         sched, n, raw, shape = self._collect(note_fn, sample_rate, notes, perform)
         if not sched:
             track = torch.zeros(n, dtype=torch.float32, device="cuda")
-            return track if return_tensor else track.cpu().numpy()
-        keys = list(raw)
-        normed = dict(zip(keys, peak_normalize([raw[k] for k in keys])))
-        if tune is None:
-            track = self._mix_reference(sched, n, normed, shape)
         else:
-            track = self._mix_tuned(sched, n, normed, _source_pitches(tune, keys, normed, sample_rate), shape)
+            keys = list(raw)
+            normed = dict(zip(keys, peak_normalize([raw[k] for k in keys])))
+            if tune is None:
+                track = self._mix_reference(sched, n, normed, shape)
+            else:
+                track = self._mix_tuned(sched, n, normed, _source_pitches(tune, keys, normed, sample_rate), shape)
+        if master is not None:
+            track, self.last_master = _mastered(track, master, sample_rate)
         return track if return_tensor else track.cpu().numpy()
 
     def _collect(self, note_fn, sample_rate, notes, perform=None):
@@ -753,7 +879,7 @@ class DiffSynth:
 
     def __init__(self, instruments_configs, noise_prediction_model, VAE_quantizer, VAE_decoder, text_encoder, CLAP_tokenizer, device,
                  model_sample_rate=16000, timesteps=1000, channels=4, freq_resolution=512, time_resolution=256, VAE_scale=4, squared=False, *,
-                 condition=None, noise_device="philox", seed=None, tune=None, pairing="reference", perform=None):
+                 condition=None, noise_device="philox", seed=None, tune=None, pairing="reference", perform=None, master=None):
         self.noise_prediction_model, self.VAE_quantizer, self.VAE_decoder = noise_prediction_model, VAE_quantizer, VAE_decoder
         self.device, self.model_sample_rate, self.timesteps, self.channels = device, model_sample_rate, timesteps, channels
         self.freq_resolution, self.time_resolution, self.VAE_scale, self.squared = freq_resolution, time_resolution, VAE_scale, squared
@@ -768,6 +894,8 @@ class DiffSynth:
         self.perform = _check_perform(perform)       # Track.render's perform=, for every track of arrange / get_music
         if self.perform is not None and pairing != "midi":
             raise ValueError("DiffSynth: perform needs pairing=\"midi\"")
+        self.master = _check_master(master)          # master()'s stage behind the sum of the tracks of arrange / get_music
+        self.last_master = None                      # MasterStats of the last mastered arrange (None: it was not mastered)
         self.last_batcher = None
         self.last_pitches = None                     # {(instrument name, duration_sec): MIDI pitch or nan} of the last tuned arrange
 
@@ -833,14 +961,22 @@ class DiffSynth:
         return [(instrument_names[i], dur) for i, t in enumerate(tracks) for _, dur, _, _ in t.schedule(sample_rate, perform)]
 
     @torch.no_grad()
-    def arrange(self, tracks, instrument_names, notes, sample_rate=16000, *, tune=_UNSET, perform=_UNSET):
+    def arrange(self, tracks, instrument_names, notes, sample_rate=16000, *, tune=_UNSET, perform=_UNSET, master=_UNSET, pcm16=False):
         """The audio stage of get_music on sampled notes {(instrument name, duration_sec): signal}: normalise, chains and mix per track,
         then the sum of the zero-padded tracks (track_maker.py:316-322), all on the device.  tune (default: the constructor's) as in
         Track.render; with "detect" the distinct notes of ALL tracks are normalised in one launch and estimated in ONE estimate_pitch call
         (one extra device -> host copy per call), and each track is then what its own tuned render gives, bit for bit.  perform (default:
-        the constructor's) as in Track.render, for tracks built with pairing="midi"; it composes with every form of tune."""
+        the constructor's) as in Track.render, for tracks built with pairing="midi"; it composes with every form of tune.
+        master (default: the constructor's; None: off) runs master()'s stage ONCE, on the sum of the tracks, which is then
+        master(plain sum, mastering, sample_rate=sample_rate) bit for bit; pcm16=True returns its int16 form (it needs a master: the raw sum
+        has no bound); last_master holds the MasterStats, or None."""
         tune = self.tune if tune is _UNSET else _check_tune(tune)
         perform = self.perform if perform is _UNSET else _check_perform(perform)
+        master = self.master if master is _UNSET else _check_master(master)
+        if master is None and pcm16:
+            raise ValueError("DiffSynth: pcm16=True needs a master (the sum of the tracks has no bound: a 16-bit rounding of it would clip)")
+        if master is not None:
+            master.samples(sample_rate)            # its refusals come before any device work
         per_track = [{key: notes[(instrument_names[i], dur)] for key, dur, _, _ in t.schedule(sample_rate, perform)} for i, t in enumerate(tracks)]
         if tune == "detect":
             audios = self._arrange_detected(tracks, instrument_names, per_track, sample_rate, perform)
@@ -851,6 +987,7 @@ class DiffSynth:
         full = torch.zeros(max(a.numel() for a in audios), dtype=torch.float32, device=audios[0].device)
         for a in audios:                           # the reference's order: full_audio += pad(audio), track by track
             full[:a.numel()] += a
+        full, self.last_master = _mastered(full, master, sample_rate, pcm16)
         return full
 
     def _arrange_detected(self, tracks, instrument_names, per_track, sample_rate, perform=None):
@@ -878,11 +1015,16 @@ class DiffSynth:
         return audios
 
     @torch.no_grad()
-    def get_music(self, mid, instrument_names, sample_rate=16000, max_notes=100, return_tensor=False, *, pairing=_UNSET, perform=_UNSET):
+    def get_music(self, mid, instrument_names, sample_rate=16000, max_notes=100, return_tensor=False, *, pairing=_UNSET, perform=_UNSET,
+                  master=_UNSET, pcm16=False):
         """The reference's get_music.  pairing / perform (default: the constructor's): with pairing="midi" every track is built with the
-        file's tempo map, tempo_map_of(mid.tracks), and the notes are sampled for the performed durations."""
+        file's tempo map, tempo_map_of(mid.tracks), and the notes are sampled for the performed durations.  master / pcm16 as in arrange:
+        the music is mastered on the device and still leaves it in one copy, of int16 samples (half the bytes) with pcm16=True."""
         pairing = self.pairing if pairing is _UNSET else pairing
         perform = self.perform if perform is _UNSET else _check_perform(perform)
+        master = self.master if master is _UNSET else _check_master(master)
+        if master is None and pcm16:
+            raise ValueError("DiffSynth.get_music: pcm16=True needs a master (the sum of the tracks has no bound: a 16-bit rounding of it would clip)")
         if perform is not None and pairing != "midi":
             raise ValueError("DiffSynth.get_music: perform needs pairing=\"midi\"")
         if pairing == "midi":
@@ -894,5 +1036,5 @@ class DiffSynth:
             instrument_names), f"len(tracks) = {len(tracks)} > {len(instrument_names)} = len(instrument_names)"
         assert sample_rate == self.model_sample_rate, "sample_rate != model_sample_rate"
         wanted = self.wanted_notes(tracks, instrument_names, sample_rate, perform)
-        full = self.arrange(tracks, instrument_names, self.sample_notes(wanted) if wanted else {}, sample_rate, perform=perform)
+        full = self.arrange(tracks, instrument_names, self.sample_notes(wanted) if wanted else {}, sample_rate, perform=perform, master=master, pcm16=pcm16)
         return full if return_tensor else full.cpu().numpy()

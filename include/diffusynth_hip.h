@@ -1096,6 +1096,58 @@ int ds_mask_prefilter(const uint8_t* planes, const int32_t* tab, int n_masks, in
 int ds_mask_zoom(const double* ws, const int32_t* tab, int n_masks, int max_out_px, long long total_px, long long total_out, float* out,
                  double* pre, void* stream);
 
+/* ---------------------------------------------------------------- mastering: RMS gain and peak-hold limiter (csrc/master.hip), fp32
+ * The stage behind the sum of the arranger's tracks, for a ragged batch: a signal is row s of tab, the arranger's [n_signals][DS_PV_NI]
+ * int32 table, of which XOFF and LEN are read (its samples in x, and in out / pcm).  1 <= LEN <= DS_MS_MAX_LEN.  Per signal x[0..N), with
+ * the scalars target_rms, max_gain and the ceiling c computed by the caller in float64 and rounded to fp32 once, A = lookahead and
+ * R = hold in SAMPLES (floored by the caller), 0 <= A <= R:
+ *   1 gain      rms = sqrt(sum x^2 / N), squares and sum in float64 (a square of an fp32 value is exact there);
+ *               gL = fp32(min(target_rms / rms, max_gain)), 1.0 exactly for target_rms <= 0 (none); silence: rms = 0, gL = max_gain;
+ *               peak = max |x|.
+ *   2 required  u[n] = fl(gL x[n]);  r[n] = fl(c / |u[n]|) where |u[n]| > c, else 1 (IEEE fp32 division);  r = 1 outside [0, N).
+ *   3 hold      m[j] = min r[k] over j - R <= k <= j + A, for -A <= j <= N - 1 + A.
+ *   4 smooth    g[n] = fp32((sum of m[j], n - A <= j <= n + A, in float64) / (2 A + 1)), the division in float64.  Every window of step 3
+ *               that the sum reads contains n (R >= A), so every m[j] <= r[n] and g[n] <= r[n].  With |u| <= 2^18 c and A <= 1024 every
+ *               partial sum is exact in float64 (12 + 18 + 23 = 53 bits): the order of the sum changes no bit.  Where nothing within reach
+ *               is over the ceiling the sum is 2 A + 1 ones and g = 1 exactly.
+ *   5 apply     y[n] = fl(g[n] u[n]), then y > c -> c, y < -c -> -c (comparisons: a NaN stays a NaN).  fl(c / |u|) |u| can exceed c by
+ *               one ulp; the clamp moves a sample by no more than that.  No product is contracted into an FMA.
+ *   6 pcm       pcm[n] = int16(rint(fl(y[n] 32767))), half to even; c <= 1, so nothing overflows.
+ *   7 stats     stats [n_signals][DS_MS_NS] fp32: GAIN = gL, RMS = fp32(rms), PEAK, MIN_GAIN = min g[n] (1 where nothing was limited);
+ *               limited [n_signals] int32 = #{n : g[n] < 1}.  The last two go through integer atomics only (the bit pattern of a
+ *               non-negative float, an int add): deterministic.
+ * Non-finite samples are not checked (their effect on the values is unspecified); nothing is read or written out of bounds.
+ *
+ * ds_master_gain: steps 1 and the initial MIN_GAIN = 1, limited = 0.  Signal s is reduced by nb = clamp(ceil(N / DS_MS_CHUNK), 1,
+ * DS_MS_MAX_PARTS) blocks of 256 threads (thread t of block b: samples b 256 + t, + nb 256, ... in that order), the partials (float64 sum,
+ * fp32 max) go to ws and one block per signal adds them in a fixed order: the order depends on N alone, so gL is the same bits for a signal
+ * alone and inside any batch.  ws: ds_master_ws_bytes(n_signals, max_len) bytes, 8-byte aligned, need not be initialised.
+ *
+ * ds_master_limit: steps 2-7 in one launch, grid (tiles of DS_MS_TILE output samples, signal); a block beyond its signal's last tile exits.
+ * A block of tile [t0, t0 + T) stages r over [t0 - A - R, t0 + T - 1 + 2 A] in LDS (computed from x and GAIN as it loads), turns it in
+ * place into minima over 2^k samples by doubling, stages m over [t0 - A, t0 + T - 1 + A] as the minimum of two of them, then forms g by
+ * the direct 2 A + 1-term sum, applies it and stores.  LDS: 4 (T + R + 3 A) + 4 (T + 2 A) bytes, 86 016 at the caps.  pcm may be NULL.
+ * out may not alias x (a tile reads its neighbours' inputs).  lookahead <= DS_MS_MAX_LOOKAHEAD, lookahead <= hold <= DS_MS_MAX_HOLD,
+ * 0 < ceiling <= 1, else DS_EINVAL.
+ * Both: every element of a fitting signal's output (and its stats row) is written and nothing outside it; a row that does not fit
+ * total_samples or has LEN outside [1, DS_MS_MAX_LEN] reads and writes nothing. */
+#define DS_MS_GAIN 0
+#define DS_MS_RMS 1
+#define DS_MS_PEAK 2
+#define DS_MS_MIN_GAIN 3
+#define DS_MS_NS 4
+#define DS_MS_TILE 4096
+#define DS_MS_MAX_LOOKAHEAD 1024
+#define DS_MS_MAX_HOLD 8192
+#define DS_MS_MAX_LEN 16777216
+#define DS_MS_CHUNK 2048
+#define DS_MS_MAX_PARTS 512
+size_t ds_master_ws_bytes(int n_signals, int max_len);
+int ds_master_gain(const float* x, const int32_t* tab, int n_signals, int max_len, long long total_samples, float target_rms, float max_gain,
+                   void* ws, float* stats, int32_t* limited, void* stream);
+int ds_master_limit(const float* x, const int32_t* tab, int n_signals, int max_len, long long total_samples, float ceiling, int lookahead,
+                    int hold, float* stats, int32_t* limited, float* out, int16_t* pcm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,21 @@ def sweep_ingest(fail):
     report("uploads_to_stft 3 uploads at two durations", fail)
 
 
+def sweep_master(fail):
+    """The mastering stage (csrc/master.hip): ragged batches on both sides of a tile at no look-ahead, the defaults and the caps (the largest
+    LDS image), with and without the int16 output, a (B, L) batch, and more chunks than the reduction has partials."""
+    from diffusynth_amd import arranger as A
+    sigs = [3.0 * synth_input("bs_ms%d" % n, (n,)).cuda() for n in (1, 2, 161, 4095, 4096, 4097, 20001)]
+    for look, hold in ((0.0, 0.0), (0.005, 0.05), (1024.5 / 16000, 8192.5 / 16000)):
+        m = A.Mastering(lookahead=look, hold=hold)
+        A.master(sigs, m, return_stats=True)
+        A.master(sigs[::-1], m, pcm16=True)
+    report("master ragged batch of 7 at three (lookahead, hold) pairs, fp32 and int16", fail)
+    A.master(torch.stack([sigs[6], -sigs[6]]), A.Mastering(target_rms=None))
+    A.master(synth_input("bs_ms_long", (2 ** 20 + 4099,)).cuda(), pcm16=True)
+    report("master (2, L) batch, 2^20 + 4099 samples", fail)
+
+
 def _partials(stored, parts):
     """(sum, sumsq) of ``parts`` chunks of each sample of a device tensor as fp32 [B][parts][2], placed 24 bytes into a NaN-filled allocation:
     the base is 8-byte but not 16-byte aligned and anything read beyond the buffer is NaN (tests/gn_partials_ref.py:guarded)."""
@@ -445,6 +460,10 @@ def main():
         sweep_ingest(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
         sys.exit(1 if fail else 0)
+    if "--only-master" in sys.argv:
+        sweep_master(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
     if "--only-perform" in sys.argv:
         sweep_perform(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
@@ -530,6 +549,7 @@ def main():
     sweep_perform(fail)
     sweep_pitch(fail)
     sweep_ingest(fail)
+    sweep_master(fail)
     # 6) GroupNorm from raw partials in every kernel that reduces them, the depthwise families, the chains without ds_gn_finalize
     sweep_gn_partials(fail)
     if fail:
