@@ -189,6 +189,7 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_latent_image": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "ds_pv_stft": (C.c_int, [_P, _P, _I, _I, C.c_longlong, C.c_longlong, _P, _P]),
     "ds_pv_vocode": (C.c_int, [_P, _P, _P, _P, _I, C.c_longlong, C.c_longlong, _P, _P]),
+    "ds_pv_formant": (C.c_int, [_P, _P, _P, _P, _F, _I, _I, C.c_longlong, _P]),
     "ds_pv_istft_ws_bytes": (_SZ, [C.c_longlong]),
     "ds_pv_istft": (C.c_int, [_P, _P, _I, _I, _I, C.c_longlong, C.c_longlong, _P, _P, _P]),
     "ds_resample_sinc": (C.c_int, [_P, _P, _P, _I, _I, C.c_longlong, C.c_longlong, _P, _P]),

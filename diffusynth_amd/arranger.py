@@ -14,6 +14,9 @@ open note of its pitch, the tempo map integrated, velocity as level and the refe
 the real note-off, both applied inside the mix (ds_mix_notes_shaped).
 Opt-in (`master=Mastering(...)`, off by default): an RMS gain and a peak-hold look-ahead limiter behind the mix (ds_master_gain,
 ds_master_limit; include/diffusynth_hip.h has the arithmetic), once per render, in arrange / get_music once on the sum of the tracks.
+Opt-in (`formant=Formant(...)`, off by default): every link of a chain keeps the note's spectral envelope where the source had it
+(ds_pv_formant between ds_pv_vocode and ds_pv_istft: cepstral envelope, warped ratio, one more launch per level), so a note shifted two
+octaves up is still the same instrument.  Beyond the reference; defined in include/diffusynth_hip.h.
 Different on purpose: the resampler.  librosa's default (soxr_hq) is a closed third-party design; the windowed sinc of
 include/diffusynth_hip.h (fc = 0.95 min(1, rate), 32 zero crossings, Kaiser beta 12) is this package's definition.
 
@@ -63,10 +66,57 @@ def signed_chain(total, step_size=4, deadband=0.05):
 
 
 # ---------------------------------------------------------------------------------------------------- one batched pitch_shift
-class _Plan:
-    """Host side of one batched pitch_shift: the signal table and the time-step tables (float64), packed for ONE upload."""
+def _finite_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) and math.isfinite(v)
 
-    def __init__(self, lengths, n_steps):
+
+@dataclasses.dataclass(frozen=True, kw_only=True)
+class Formant:
+    """Formant-preserving pitch shifts (pitch_shift(formant=...), Track.render(formant=...), DiffSynth(formant=...)): every synthesis frame
+    of the phase vocoder is multiplied, bin by bin, by the ratio of its own smoothed spectral envelope at the place the resampler will move
+    the bin to and at the bin itself (ds_pv_formant; include/diffusynth_hip.h has the arithmetic), so the envelope stays where the source
+    had it while the partials move.
+
+    order: the lifter's cut-off in QUEFRENCY SAMPLES: the envelope keeps the cepstral coefficients up to it.  It must stay below the source's
+    pitch period sample_rate / f0 (97 samples at MIDI 52 and 16 kHz), or the envelope follows the partials themselves; 1 .. DS_PV_ORDER_MAX.
+    max_gain_db: the correction of a bin is held inside +- max_gain_db (0 < max_gain_db <= 60).
+    track_pitch: a link of a chain entered at cumulative shift `lo` semitones gets max(4, floor(order min(1, 2^(-lo / 12)))): the period of
+    its input has already shrunk by the shifts in front of it (a downward chain keeps `order`).  False: every link gets `order`."""
+    order: int = 30
+    max_gain_db: float = 24.0
+    track_pitch: bool = True
+
+    def __post_init__(self):
+        if not isinstance(self.order, (int, np.integer)) or isinstance(self.order, (bool, np.bool_)) or not 1 <= self.order <= _PV["DS_PV_ORDER_MAX"]:
+            raise ValueError(f"Formant: order must be an int in [1, {_PV['DS_PV_ORDER_MAX']}] (quefrency samples), not {self.order!r}")
+        if not _finite_number(self.max_gain_db) or not 0 < self.max_gain_db <= _PV["DS_PV_GAIN_DB_MAX"]:
+            raise ValueError(f"Formant: max_gain_db must be a number in (0, {_PV['DS_PV_GAIN_DB_MAX']}], not {self.max_gain_db!r}")
+        if not isinstance(self.track_pitch, (bool, np.bool_)):
+            raise ValueError(f"Formant: track_pitch must be a bool, not {self.track_pitch!r}")
+
+    @property
+    def limit(self):
+        """max_gain_db in nepers, ln 10 / 20 per dB, as the fp32 value the kernel takes."""
+        return float(np.float32(float(self.max_gain_db) * math.log(10.0) / 20.0))
+
+    def node_order(self, lo):
+        """The order of a link whose input sits `lo` semitones from the source."""
+        if not self.track_pitch:
+            return int(self.order)
+        return max(4, int(math.floor(int(self.order) * min(1.0, 2.0 ** (-float(lo) / 12.0)))))
+
+
+def _check_formant(formant):
+    if formant is None or isinstance(formant, Formant):
+        return formant
+    raise ValueError(f"formant: None or a Formant, not {formant!r}")
+
+
+class _Plan:
+    """Host side of one batched pitch_shift: the signal table and the time-step tables (float64), packed for ONE upload.  orders (one per
+    signal; only with a Formant) appends ds_pv_formant's order and warp = fl32(1 / rate) arrays; without it the buffer is what it always was."""
+
+    def __init__(self, lengths, n_steps, orders=None):
         n = len(lengths)
         tab = np.zeros((n, _PV["DS_PV_NI"]), dtype=np.int32)
         rates = np.zeros(n, dtype=np.float64)
@@ -91,11 +141,20 @@ class _Plan:
         # [rates (8-byte aligned) | tab | step_idx | step_alpha] as one int32 buffer
         self.host = np.concatenate([rates.view(np.int32), tab.reshape(-1), np.concatenate(idx), np.concatenate(alpha).view(np.int32)])
         self.o_tab, self.o_idx, self.o_alpha = 2 * n, 2 * n + tab.size, 2 * n + tab.size + toff
+        if orders is not None:
+            if len(orders) != n:
+                raise ValueError(f"pitch_shift: {len(orders)} orders for {n} signals")
+            self.o_order, self.o_warp = self.host.size, self.host.size + n
+            warp = (1.0 / rates).astype(np.float32)              # the float64 quotient rounded once: the fp32 factor of q = fl32(k) * warp
+            self.host = np.concatenate([self.host, np.asarray(orders, dtype=np.int32), warp.view(np.int32)])
 
 
-def _shift_flat(x, lengths, n_steps):
-    """x: the signals back to back (fp32, CUDA) -> (the shifted signals back to back, their offsets).  Four entry points, six launches."""
-    p = _Plan(lengths, n_steps)
+def _shift_flat(x, lengths, n_steps, formant=None, orders=None):
+    """x: the signals back to back (fp32, CUDA) -> (the shifted signals back to back, their offsets).  Four entry points, six launches; with
+    a Formant (orders: one per signal, default its order) ds_pv_formant between vocode and iSTFT: five and seven."""
+    if formant is not None and orders is None:
+        orders = [formant.order] * len(lengths)
+    p = _Plan(lengths, n_steps, orders if formant is not None else None)
     dev = x.device
     tables = torch.from_numpy(p.host).to(dev)
     base = tables.data_ptr()
@@ -108,6 +167,8 @@ def _shift_flat(x, lengths, n_steps):
     st = L.current_stream()
     L.call("ds_pv_stft", x.data_ptr(), tab, p.n, p.max_frames, p.total_samples, p.total_frames, spec.data_ptr(), st)
     L.call("ds_pv_vocode", spec.data_ptr(), tab, idx, alpha, p.n, p.total_frames, p.total_out, voc.data_ptr(), st)
+    if formant is not None:
+        L.call("ds_pv_formant", voc.data_ptr(), tab, base + 4 * p.o_order, base + 4 * p.o_warp, formant.limit, p.n, p.max_out, p.total_out, st)
     L.call("ds_pv_istft", voc.data_ptr(), tab, p.n, p.max_out, p.max_stretched, p.total_out, p.total_stretched, ws.data_ptr(), ys.data_ptr(), st)
     L.call("ds_resample_sinc", ys.data_ptr(), tab, rates, p.n, p.max_len, p.total_stretched, p.total_samples, out.data_ptr(), st)
     return out, p.offsets
@@ -138,10 +199,12 @@ def _per_signal(v, n, what):
 
 
 @torch.no_grad()
-def pitch_shift(signals, n_steps, sample_rate=16000, n_fft=4096, hop_length=None):
+def pitch_shift(signals, n_steps, sample_rate=16000, n_fft=4096, hop_length=None, *, formant=None):
     """librosa.effects.pitch_shift(y, sr, n_steps, n_fft=4096, hop_length=1024) for a batch: a (B, L) CUDA tensor or a list of 1-D CUDA
     tensors of different lengths, n_steps a number or one per signal (any real value of either sign) -> the same shapes, fp32.
-    sample_rate does not enter the arithmetic (as in librosa: only the ratio does)."""
+    sample_rate does not enter the arithmetic (as in librosa: only the ratio does).  formant (a Formant; None: librosa's shift, today's
+    bits) keeps every signal's spectral envelope in place, with the Formant's order for this one link."""
+    formant = _check_formant(formant)
     if n_fft != N_FFT or (hop_length is not None and hop_length != HOP):
         raise ValueError(f"pitch_shift: n_fft {N_FFT} / hop_length {HOP} only (the reference's call)")
     sigs, was_tensor = _as_list(signals, "pitch_shift")
@@ -149,7 +212,7 @@ def pitch_shift(signals, n_steps, sample_rate=16000, n_fft=4096, hop_length=None
         return signals
     steps = _per_signal(n_steps, len(sigs), "pitch_shift")
     lengths = [s.numel() for s in sigs]
-    out, offs = _shift_flat(sigs[0] if len(sigs) == 1 else torch.cat(sigs), lengths, steps)
+    out, offs = _shift_flat(sigs[0] if len(sigs) == 1 else torch.cat(sigs), lengths, steps, formant)
     if was_tensor:
         return out.view(len(sigs), lengths[0])
     return [out[o:o + n] for o, n in zip(offs, lengths)]
@@ -194,30 +257,46 @@ def signed_tree(requests, step_size=4, deadband=0.05):
     return levels
 
 
-def _run_tree(sources, requests, step_size=4):
+def _tree_arg(formant, *lead):
+    """Trailing arguments of Track's calls of _run_tree / _run_levels: none without a Formant, so that the plain render calls the two
+    exactly as it did before the mode existed (tests/test_pitch_cpu.py replaces them by two-argument stand-ins).  ONLY for those two
+    internal calls: everything else, the public calls above all, hands `formant` on as it is — an explicit None must stay a None."""
+    return () if formant is None else lead + (formant,)
+
+
+def node_orders(nodes, formant):
+    """The lifter order of every node of a level: Formant.node_order of the cumulative shift the node is entered at."""
+    return [formant.node_order(lo) for _, lo, _, _ in nodes]
+
+
+def _run_tree(sources, requests, step_size=4, formant=None):
     """sources {key: 1-D fp32 CUDA tensor}; -> {(key, cumulative): tensor} with (key, 0) = the source itself.  One batched launch sequence
     per level."""
-    return _run_levels(sources, shift_tree(requests, step_size))
+    return _run_levels(sources, shift_tree(requests, step_size), formant)
 
 
-def _run_levels(sources, levels):
-    """_run_tree on built levels (shift_tree's or signed_tree's)."""
+def _run_levels(sources, levels, formant=None):
+    """_run_tree on built levels (shift_tree's or signed_tree's).  With a Formant every node carries its own order; (key, cumulative) still
+    names a node uniquely (its order follows from the cumulative of its parent), so the sharing is the same."""
     have = {(k, 0): v for k, v in sources.items()}
     for nodes in levels:
         parents = [have[(k, lo)] for k, lo, _, _ in nodes]
         lengths = [p.numel() for p in parents]
-        out, offs = _shift_flat(parents[0] if len(parents) == 1 else torch.cat(parents), lengths, [st for _, _, _, st in nodes])
+        out, offs = _shift_flat(parents[0] if len(parents) == 1 else torch.cat(parents), lengths, [st for _, _, _, st in nodes],
+                                formant, None if formant is None else node_orders(nodes, formant))
         for (k, _, cum, _), o, n in zip(nodes, offs, lengths):
             have[(k, cum)] = out[o:o + n]
     return have
 
 
 @torch.no_grad()
-def pitch_shift_chain(signals, totals, step_size=4, *, signed=False):
+def pitch_shift_chain(signals, totals, step_size=4, *, signed=False, formant=None):
     """The reference's pitch_shift_librosa (track_maker.py:12-47) for a batch: ceil(total / step_size) chained shifts of at most step_size
     semitones; total <= 0 returns the input unchanged (the reference's loop is empty).  Signals that are the same tensor share the common
     prefix of their chains; the result is bit for bit what the chains run one by one give.  signed=True: real totals of either sign through
-    signed_chain (a total inside its deadband returns the input)."""
+    signed_chain (a total inside its deadband returns the input).  formant (a Formant) keeps the envelope in place
+    in every link, each with the order of the cumulative shift it is entered at."""
+    formant = _check_formant(formant)
     if isinstance(signals, torch.Tensor) and signals.dim() == 2:
         _require_cuda(signals, "pitch_shift_chain")
         rows = list(signals)
@@ -233,22 +312,23 @@ def pitch_shift_chain(signals, totals, step_size=4, *, signed=False):
         if key not in sources:
             sources[key] = s.detach().float().contiguous()
     if signed:
-        have = _run_levels(sources, signed_tree(list(zip(keys, tot)), step_size))
+        have = _run_levels(sources, signed_tree(list(zip(keys, tot)), step_size), formant)
         out = [have[(k, t)] if signed_chain(t, step_size) else s for s, k, t in zip(rows, keys, tot)]
     else:
-        have = _run_tree(sources, [(k, t) for k, t in zip(keys, tot) if t > 0], step_size)
+        have = _run_tree(sources, [(k, t) for k, t in zip(keys, tot) if t > 0], step_size, formant)
         out = [s if t <= 0 else have[(k, t)] for s, k, t in zip(rows, keys, tot)]
     if isinstance(signals, torch.Tensor):
         return torch.stack([o.float() for o in out])
     return out
 
 
-def pitch_shift_librosa(waveform, sample_rate, total_steps, step_size=4, n_fft=4096, hop_length=None):
-    """Drop-in for track_maker.pitch_shift_librosa on one CUDA waveform."""
+def pitch_shift_librosa(waveform, sample_rate, total_steps, step_size=4, n_fft=4096, hop_length=None, *, formant=None):
+    """Drop-in for track_maker.pitch_shift_librosa on one CUDA waveform (formant: as in pitch_shift_chain)."""
+    formant = _check_formant(formant)
     if n_fft != N_FFT or (hop_length is not None and hop_length != HOP):
         raise ValueError(f"pitch_shift_librosa: n_fft {N_FFT} / hop_length {HOP} only")
     _require_cuda(waveform, "pitch_shift_librosa")
-    return pitch_shift_chain([waveform], [total_steps], step_size)[0]
+    return pitch_shift_chain([waveform], [total_steps], step_size, formant=formant)[0]
 
 
 # ---------------------------------------------------------------------------------------------------- peak normalisation, mix
@@ -413,10 +493,6 @@ def adsr_envelope(signals, sample_rate, duration, attack_time, decay_time, susta
     if was_tensor and len(set(outs)) == 1:
         return flat.view(n, outs[0])
     return [flat[o:o + m] for o, m in zip(starts, outs)]
-
-
-def _finite_number(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) and math.isfinite(v)
 
 
 @dataclasses.dataclass(frozen=True, kw_only=True)
@@ -787,7 +863,7 @@ class Track:
     last_master = None         # MasterStats of the last mastered render
 
     @torch.no_grad()
-    def render(self, note_fn, sample_rate=16000, return_tensor=True, notes=None, *, tune=None, perform=None, master=None):
+    def render(self, note_fn, sample_rate=16000, return_tensor=True, notes=None, *, tune=None, perform=None, master=None, formant=None):
         """synthesize_track on the device.  note_fn(velocity, duration_sec) -> numpy array or tensor on either device, called once per distinct
         duration in event order (the reference's cache); notes: {duration key: tensor} sampled beforehand instead.  One peak normalisation,
         one tree of chains over the distinct (duration, note) pairs, one mix.
@@ -804,7 +880,11 @@ class Track:
         Normalisation, the chains and tune= are the same and compose with it.
 
         master (a Mastering) adds one stage behind the mix: master(track, mastering, sample_rate=sample_rate), bit for bit; last_master
-        holds its MasterStats.  None (the default) is the render without it."""
+        holds its MasterStats.  None (the default) is the render without it.
+
+        formant (a Formant) changes the chains alone: every link keeps the note's spectral envelope in place (pitch_shift_chain(formant=)).
+        It composes with tune, perform and master; None (the default) is the render without it."""
+        formant = _check_formant(formant)
         tune = _check_tune(tune)
         perform = self._check_perform(perform)
         master = _check_master(master)
@@ -819,9 +899,9 @@ class Track:
             keys = list(raw)
             normed = dict(zip(keys, peak_normalize([raw[k] for k in keys])))
             if tune is None:
-                track = self._mix_reference(sched, n, normed, shape)
+                track = self._mix_reference(sched, n, normed, shape, formant)
             else:
-                track = self._mix_tuned(sched, n, normed, _source_pitches(tune, keys, normed, sample_rate), shape)
+                track = self._mix_tuned(sched, n, normed, _source_pitches(tune, keys, normed, sample_rate), shape, formant)
         if master is not None:
             track, self.last_master = _mastered(track, master, sample_rate)
         return track if return_tensor else track.cpu().numpy()
@@ -845,18 +925,18 @@ class Track:
                 raise ValueError(f"Track: a note of {raw[key].numel()} samples at sample {start} ends past the track's {n} samples")
         return sched, n, raw, None
 
-    def _mix_reference(self, sched, n, normed, shape=None):
-        have = _run_tree(normed, [(key, total) for key, _, _, total in sched if total > 0])
+    def _mix_reference(self, sched, n, normed, shape=None, formant=None):
+        have = _run_tree(normed, [(key, total) for key, _, _, total in sched if total > 0], *_tree_arg(formant, 4))
         return _mix_nodes(have, [((key, max(total, 0)), start) for key, _, start, total in sched], n, *_shape_arg(shape))
 
-    def _mix_tuned(self, sched, n, normed, pitches, shape=None):
+    def _mix_tuned(self, sched, n, normed, pitches, shape=None, formant=None):
         """pitches {duration key: MIDI pitch of the normalised note, nan = unpitched}: the signed tree and the mix."""
         self.last_pitches = {key: float(pitches[key]) for key in normed}
         totals = []
         for key, _, _, total in sched:                                         # total = note - 52
             p = self.last_pitches[key]
             totals.append(max(total, 0) if math.isnan(p) else (total + 52) - p)
-        have = _run_levels(normed, signed_tree([(key, t) for (key, _, _, _), t in zip(sched, totals)]))
+        have = _run_levels(normed, signed_tree([(key, t) for (key, _, _, _), t in zip(sched, totals)]), *_tree_arg(formant))
         return _mix_nodes(have, [((key, t if signed_chain(t) else 0), start) for (key, _, start, _), t in zip(sched, totals)], n, *_shape_arg(shape))
 
     def synthesize_track(self, diffSynthSampler, sample_rate=16000):
@@ -879,7 +959,7 @@ class DiffSynth:
 
     def __init__(self, instruments_configs, noise_prediction_model, VAE_quantizer, VAE_decoder, text_encoder, CLAP_tokenizer, device,
                  model_sample_rate=16000, timesteps=1000, channels=4, freq_resolution=512, time_resolution=256, VAE_scale=4, squared=False, *,
-                 condition=None, noise_device="philox", seed=None, tune=None, pairing="reference", perform=None, master=None):
+                 condition=None, noise_device="philox", seed=None, tune=None, pairing="reference", perform=None, master=None, formant=None):
         self.noise_prediction_model, self.VAE_quantizer, self.VAE_decoder = noise_prediction_model, VAE_quantizer, VAE_decoder
         self.device, self.model_sample_rate, self.timesteps, self.channels = device, model_sample_rate, timesteps, channels
         self.freq_resolution, self.time_resolution, self.VAE_scale, self.squared = freq_resolution, time_resolution, VAE_scale, squared
@@ -895,6 +975,7 @@ class DiffSynth:
         if self.perform is not None and pairing != "midi":
             raise ValueError("DiffSynth: perform needs pairing=\"midi\"")
         self.master = _check_master(master)          # master()'s stage behind the sum of the tracks of arrange / get_music
+        self.formant = _check_formant(formant)       # Track.render's formant=, for every track of arrange / get_music
         self.last_master = None                      # MasterStats of the last mastered arrange (None: it was not mastered)
         self.last_batcher = None
         self.last_pitches = None                     # {(instrument name, duration_sec): MIDI pitch or nan} of the last tuned arrange
@@ -961,7 +1042,7 @@ class DiffSynth:
         return [(instrument_names[i], dur) for i, t in enumerate(tracks) for _, dur, _, _ in t.schedule(sample_rate, perform)]
 
     @torch.no_grad()
-    def arrange(self, tracks, instrument_names, notes, sample_rate=16000, *, tune=_UNSET, perform=_UNSET, master=_UNSET, pcm16=False):
+    def arrange(self, tracks, instrument_names, notes, sample_rate=16000, *, tune=_UNSET, perform=_UNSET, master=_UNSET, pcm16=False, formant=_UNSET):
         """The audio stage of get_music on sampled notes {(instrument name, duration_sec): signal}: normalise, chains and mix per track,
         then the sum of the zero-padded tracks (track_maker.py:316-322), all on the device.  tune (default: the constructor's) as in
         Track.render; with "detect" the distinct notes of ALL tracks are normalised in one launch and estimated in ONE estimate_pitch call
@@ -969,7 +1050,9 @@ class DiffSynth:
         the constructor's) as in Track.render, for tracks built with pairing="midi"; it composes with every form of tune.
         master (default: the constructor's; None: off) runs master()'s stage ONCE, on the sum of the tracks, which is then
         master(plain sum, mastering, sample_rate=sample_rate) bit for bit; pcm16=True returns its int16 form (it needs a master: the raw sum
-        has no bound); last_master holds the MasterStats, or None."""
+        has no bound); last_master holds the MasterStats, or None.  formant (default: the constructor's; None: off) as in Track.render, for
+        the chains of every track."""
+        formant = self.formant if formant is _UNSET else _check_formant(formant)
         tune = self.tune if tune is _UNSET else _check_tune(tune)
         perform = self.perform if perform is _UNSET else _check_perform(perform)
         master = self.master if master is _UNSET else _check_master(master)
@@ -979,9 +1062,9 @@ class DiffSynth:
             master.samples(sample_rate)            # its refusals come before any device work
         per_track = [{key: notes[(instrument_names[i], dur)] for key, dur, _, _ in t.schedule(sample_rate, perform)} for i, t in enumerate(tracks)]
         if tune == "detect":
-            audios = self._arrange_detected(tracks, instrument_names, per_track, sample_rate, perform)
+            audios = self._arrange_detected(tracks, instrument_names, per_track, sample_rate, perform, formant)
         else:
-            audios = [t.render(None, sample_rate, notes=per_track[i], tune=tune, perform=perform) for i, t in enumerate(tracks)]
+            audios = [t.render(None, sample_rate, notes=per_track[i], tune=tune, perform=perform, formant=formant) for i, t in enumerate(tracks)]
             if tune is not None:
                 self.last_pitches = {(instrument_names[i], dur): tune for i, t in enumerate(tracks) for _, dur, _, _ in t.schedule(sample_rate, perform)}
         full = torch.zeros(max(a.numel() for a in audios), dtype=torch.float32, device=audios[0].device)
@@ -990,7 +1073,7 @@ class DiffSynth:
         full, self.last_master = _mastered(full, master, sample_rate, pcm16)
         return full
 
-    def _arrange_detected(self, tracks, instrument_names, per_track, sample_rate, perform=None):
+    def _arrange_detected(self, tracks, instrument_names, per_track, sample_rate, perform=None, formant=None):
         if not torch.cuda.is_available():
             raise RuntimeError(_NO_GPU % "DiffSynth.arrange")
         parts = [t._collect(None, sample_rate, per_track[i], perform) for i, t in enumerate(tracks)]
@@ -1011,15 +1094,16 @@ class DiffSynth:
             if sched:
                 own = {key: ids[(instrument_names[i], dur)] for key, dur, _, _ in sched}
                 audios[i] = tracks[i]._mix_tuned(sched, n, {key: normed[j] for key, j in own.items()}, {key: midi[j] for key, j in own.items()},
-                                                      *_shape_arg(shape))
+                                                      shape, formant)
         return audios
 
     @torch.no_grad()
     def get_music(self, mid, instrument_names, sample_rate=16000, max_notes=100, return_tensor=False, *, pairing=_UNSET, perform=_UNSET,
-                  master=_UNSET, pcm16=False):
+                  master=_UNSET, pcm16=False, formant=_UNSET):
         """The reference's get_music.  pairing / perform (default: the constructor's): with pairing="midi" every track is built with the
         file's tempo map, tempo_map_of(mid.tracks), and the notes are sampled for the performed durations.  master / pcm16 as in arrange:
-        the music is mastered on the device and still leaves it in one copy, of int16 samples (half the bytes) with pcm16=True."""
+        the music is mastered on the device and still leaves it in one copy, of int16 samples (half the bytes) with pcm16=True.  formant as in arrange."""
+        formant = self.formant if formant is _UNSET else _check_formant(formant)
         pairing = self.pairing if pairing is _UNSET else pairing
         perform = self.perform if perform is _UNSET else _check_perform(perform)
         master = self.master if master is _UNSET else _check_master(master)
@@ -1036,5 +1120,6 @@ class DiffSynth:
             instrument_names), f"len(tracks) = {len(tracks)} > {len(instrument_names)} = len(instrument_names)"
         assert sample_rate == self.model_sample_rate, "sample_rate != model_sample_rate"
         wanted = self.wanted_notes(tracks, instrument_names, sample_rate, perform)
-        full = self.arrange(tracks, instrument_names, self.sample_notes(wanted) if wanted else {}, sample_rate, perform=perform, master=master, pcm16=pcm16)
+        full = self.arrange(tracks, instrument_names, self.sample_notes(wanted) if wanted else {}, sample_rate, perform=perform, master=master, pcm16=pcm16,
+                            formant=formant)
         return full if return_tensor else full.cpu().numpy()

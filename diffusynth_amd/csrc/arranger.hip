@@ -15,6 +15,9 @@
 //                accumulator phi + wrap(angle R - angle L - phi) is angle R - angle L modulo 2 pi, so the phase is kept as the running
 //                product of u(R) conj(u(L)), u(z) = z / |z| (1 for z = 0, as np.angle(0) = 0), renormalised every frame: no angle ever
 //                reaches the 10^5 rad an fp32 accumulator would lose 1e-4 on, and no atan2f / sinf / cosf is evaluated.
+// ds_pv_formant  (opt-in, in place on the synthesis frames) two frames per block once more: the log magnitudes of frames t and t + 1 as the real
+//                and imaginary part of one forward transform (both real and even: no separation), lifter, one inverse transform, then
+//                V[k] *= exp(clamp(S(k / rate) - S(k))): the envelope the resampler is about to move is put where it will land.
 // ds_pv_istft    two frames per block again (Z = A + i B with both Hermitian extensions; the real part of the inverse transform is frame t,
 //                the imaginary part frame t + 1), window, frames to the workspace; then overlap-add as a gather: an output sample sums its
 //                <= 4 frames in frame order and divides by its window-sum-square.
@@ -177,6 +180,76 @@ __global__ __launch_bounds__(256) void pv_vocode_kernel(const float2* spec, cons
             acc = cmul(acc, cmul(ur, float2{ul.x, -ul.y}));
             const float n = sqrtf(acc.x * acc.x + acc.y * acc.y);
             acc = float2{acc.x / n, acc.y / n};
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ formant correction
+// V[k] *= exp(clamp(S(k warp) - S(k), +- limit)), S = the cepstrally smoothed log magnitude of the frame (include/diffusynth_hip.h).
+// L_t and L_{t+1} are real and even, so are their transforms: Re FFT(L_t + i L_{t+1}) is frame t's cepstrum and Im frame t + 1's, the
+// lifter is a real mask, and the inverse transform's real / imaginary parts are S_t / S_{t+1} — two frames per transform pair and no
+// separation step.  The frames stay in registers between the load and the store: one read and one write of voc.
+constexpr int FM_PER = (NBINS + 255) / 256;           // bins per thread (the last round holds bin 2048 alone)
+constexpr float FM_FLOOR = 1e-6f;
+__device__ __forceinline__ float log_mag(float2 v) {
+    float m;
+    (void)unit_mag(v, m);
+    return logf(fmaxf(m, FM_FLOOR));
+}
+__device__ __forceinline__ float formant_gain(float sk, float lo, float hi, float f, float limit) {
+    const float sq = (1.0f - f) * lo + f * hi;
+    return expf(fminf(fmaxf(sq - sk, -limit), limit));
+}
+
+__global__ __launch_bounds__(256) void pv_formant_kernel(float2* voc, const int32_t* tab, const int32_t* order, const float* warp, float limit,
+                                                         long long total_out) {
+    extern __shared__ __attribute__((aligned(16))) float2 sm[];
+    float2 *b0 = sm, *b1 = sm + N_FFT, *tw = sm + 2 * N_FFT;
+    const int tid = threadIdx.x, t0 = 2 * blockIdx.x;
+    const PvRow r = pv_row(tab, blockIdx.y);
+    if (t0 >= r.nout || !fits(r.toff, r.nout, total_out)) return;
+    const int ord = DS_LD(int32_t, order + blockIdx.y, DS_BX_AUX1);
+    if (ord < 1 || ord > DS_PV_ORDER_MAX) return;
+    const float wp = DS_LD(float, warp + blockIdx.y, DS_BX_AUX2);
+    const bool two = t0 + 1 < r.nout;
+    fill_twiddles<false>(tw, tid);
+    float2* v = voc + ((size_t)r.toff + t0) * NBINS;
+    float2 va[FM_PER], vb[FM_PER];
+#pragma unroll
+    for (int j = 0; j < FM_PER; ++j) {
+        const int k = tid + 256 * j;
+        if (k >= NBINS) continue;
+        va[j] = DS_LD(float2, v + k, DS_BX_OUT);
+        vb[j] = two ? DS_LD(float2, v + NBINS + k, DS_BX_OUT) : float2{0.f, 0.f};      // an odd last frame: the lane stays at ln(floor)
+        const float2 l = {log_mag(va[j]), log_mag(vb[j])};
+        b0[k] = l;
+        if (k != 0 && k != N_FFT / 2) b0[N_FFT - k] = l;                                 // the even extension
+    }
+    __syncthreads();
+    fft4096<false>(b0, b1, tw, tid);
+    for (int n = tid; n < N_FFT; n += 256) {                                             // lifter and 1 / N, each element by its own thread
+        const int m = n < N_FFT - n ? n : N_FFT - n;
+        const float2 c = b0[n];
+        b0[n] = m <= ord ? float2{c.x * (1.0f / N_FFT), c.y * (1.0f / N_FFT)} : float2{0.f, 0.f};
+    }
+    for (int m = tid; m < 1024; m += 256) tw[m].y = -tw[m].y;                            // the inverse transform's twiddles: the conjugates
+    __syncthreads();
+    fft4096<true>(b0, b1, tw, tid);
+#pragma unroll
+    for (int j = 0; j < FM_PER; ++j) {
+        const int k = tid + 256 * j;
+        if (k >= NBINS) continue;
+        const float q = fminf((float)k * wp, (float)(N_FFT / 2));
+        int i = (int)floorf(q);
+        i = i < N_FFT / 2 - 1 ? i : N_FFT / 2 - 1;
+        i = i > 0 ? i : 0;                                                               // (a NaN or negative warp stays inside the buffer)
+        const float f = q - (float)i;
+        const float2 sk = b0[k], lo = b0[i], hi = b0[i + 1];
+        const float ga = formant_gain(sk.x, lo.x, hi.x, f, limit);
+        DS_ST(float2, v + k, DS_BX_OUT, (float2{va[j].x * ga, va[j].y * ga}));
+        if (two) {
+            const float gb = formant_gain(sk.y, lo.y, hi.y, f, limit);
+            DS_ST(float2, v + NBINS + k, DS_BX_OUT, (float2{vb[j].x * gb, vb[j].y * gb}));
         }
     }
 }
@@ -459,6 +532,33 @@ extern "C" int ds_pv_vocode(const float* spec, const int32_t* tab, const int32_t
     hipLaunchKernelGGL(pv_vocode_kernel, dim3((NBINS + 255) / 256, n_signals), dim3(256), 0, st, reinterpret_cast<const float2*>(spec), tab, step_idx,
                        step_alpha, total_frames, total_out, reinterpret_cast<float2*>(voc));
     DS_CHECK_LAUNCH("pv_vocode");
+    return DS_OK;
+}
+
+extern "C" int ds_pv_formant(float* voc, const int32_t* tab, const int32_t* order, const float* warp, float limit, int n_signals, int max_out,
+                             long long total_out, void* stream) {
+    DS_REQUIRE(voc && tab && order && warp && n_signals > 0 && max_out > 0 && total_out > 0, "pv_formant: bad args (n_signals=%d max_out=%d total_out=%lld)",
+               n_signals, max_out, total_out);
+    DS_REQUIRE(n_signals <= 65535 && total_out * NBINS <= MAX_ELEMS, "pv_formant: at most 65535 signals and 2^31 - 1 elements per buffer");
+    // (0, DS_PV_GAIN_DB_MAX dB] in nepers; the slack is an fp32 rounding of the caller's product
+    DS_REQUIRE(limit > 0.f && (double)limit <= DS_PV_GAIN_DB_MAX * (2.302585092994046 / 20.0) * (1.0 + 1e-6),
+               "pv_formant: the limit must be inside (0, %d dB] in nepers, dB ln 10 / 20 (limit=%g)", DS_PV_GAIN_DB_MAX, (double)limit);
+    if (!al8(voc) || !al4(tab) || !al4(order) || !al4(warp)) DS_FAIL(DS_EALIGN, "pv_formant: voc must be 8-byte, tab / order / warp 4-byte aligned");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#if DS_BOUNDS
+    {
+        DsBxHost h(DS_K_PV_FORMANT);
+        h.set(DS_BX_AUX0, tab, (long long)n_signals * DS_PV_NI * 4);
+        h.set(DS_BX_AUX1, order, (long long)n_signals * 4);
+        h.set(DS_BX_AUX2, warp, (long long)n_signals * 4);
+        h.set(DS_BX_OUT, voc, total_out * NBINS * 8);
+        h.publish(st);
+    }
+#endif
+    DS_SET_MAX_LDS(pv_formant_kernel, FFT_LDS, "pv_formant");
+    hipLaunchKernelGGL(pv_formant_kernel, dim3((max_out + 1) / 2, n_signals), dim3(256), FFT_LDS, st, reinterpret_cast<float2*>(voc), tab, order, warp, limit,
+                       total_out);
+    DS_CHECK_LAUNCH("pv_formant");
     return DS_OK;
 }
 

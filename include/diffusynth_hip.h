@@ -889,6 +889,27 @@ int ds_pv_stft(const float* x, const int32_t* tab, int n_signals, int max_frames
                void* stream);
 int ds_pv_vocode(const float* spec, const int32_t* tab, const int32_t* step_idx, const float* step_alpha, int n_signals, long long total_frames,
                  long long total_out, float* voc, void* stream);
+/* Formant correction (opt-in, between ds_pv_vocode and ds_pv_istft; in place on voc): a shift followed by the resampler moves the content of
+ * bin k to k / rate and the spectral envelope with it; this gives bin k beforehand the source's envelope AT k / rate, so the envelope stays
+ * where it was.  Per synthesis frame V[k], k = 0 .. 2048, of row s, with order[s] (quefrency samples) and warp[s] = fl32(1 / rate):
+ *   L[k]  = ln(max(|V[k]|, 1e-6))                          extended evenly to 4096 points
+ *   c     = FFT4096(L) / 4096                              the real cepstrum
+ *   c'[n] = c[n] where min(n, 4096 - n) <= order, else 0   rectangular lifter
+ *   S     = inverse FFT4096 of c' (unnormalised)           the smoothed log envelope
+ *   q     = min(fl32(k) * warp, 2048)                      ONE fp32 product
+ *   Sq    = (1 - f) S[i] + f S[i + 1],  i = min(floor(q), 2047),  f = q - i
+ *   d     = clamp(Sq - S[k], -limit, +limit)               limit = max_gain_db ln 10 / 20, 0 < max_gain_db <= DS_PV_GAIN_DB_MAX
+ *   V'[k] = V[k] exp(d)
+ * in fp32 with logf / expf, |V| by the scaled form ds_pv_vocode uses.  A row with warp == 1 has d == 0: its frames keep their bits.
+ * order, warp: device arrays of n_signals entries.  Grid (ceil(max_out / 2), n_signals): a block takes two consecutive frames of one signal
+ * through ONE transform pair (L_t in the real part, L_{t+1} in the imaginary part: both are real and even, so are their transforms).
+ * A row whose (TOFF, NOUT) does not fit total_out reads (beyond its table row) and writes nothing; a row whose order is outside
+ * [1, DS_PV_ORDER_MAX] reads that order and nothing else, and writes nothing.  No atomics, no workspace; a frame's result depends on nothing
+ * outside the frame. */
+#define DS_PV_ORDER_MAX 512
+#define DS_PV_GAIN_DB_MAX 60
+int ds_pv_formant(float* voc, const int32_t* tab, const int32_t* order, const float* warp, float limit, int n_signals, int max_out,
+                  long long total_out, void* stream);
 size_t ds_pv_istft_ws_bytes(long long total_out);
 int ds_pv_istft(const float* voc, const int32_t* tab, int n_signals, int max_out, int max_stretched, long long total_out, long long total_stretched,
                 float* ws, float* y, void* stream);

@@ -61,6 +61,9 @@ def sweep_arranger(fail):
     report("pitch_shift 2 ragged batches of 7 + a (2, L) batch", fail)
     A.pitch_shift_chain([sigs[0], sigs[0], sigs[2], sigs[4]], [31, 5, 9, 2])
     report("pitch_shift_chain tree (8 levels)", fail)
+    A.pitch_shift(sigs[:7], [-12, 12, 0, -4, 7, 4, -1], formant=A.Formant(order=512, max_gain_db=60))
+    A.pitch_shift_chain([sigs[0], sigs[0], sigs[2], sigs[4]], [31, 5, 9, 2], formant=A.Formant())
+    report("pitch_shift with a Formant (ds_pv_formant): a ragged batch of 7 at the caps + the chain tree with per-node orders", fail)
     normed = A.peak_normalize(sigs)
     report("peak_normalize 8 signals (1 .. 77568 samples)", fail)
     n = 100000
