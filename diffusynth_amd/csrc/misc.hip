@@ -358,6 +358,12 @@ __global__ __launch_bounds__(256) void dup_batch_kernel(const u32x4* src, u32x4*
 
 extern "C" int ds_dup_batch(const void* src, void* dst, size_t nbytes, void* stream) {
     DS_REQUIRE(src && dst && nbytes > 0, "dup_batch: bad args");
+    {
+        // src == dst (in place), or the source and the two halves of dst apart: a partial overlap would read what the call has already written
+        const uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
+        DS_REQUIRE(s == d || (s >= d ? s - d >= 2 * (uintptr_t)nbytes : d - s >= (uintptr_t)nbytes),
+                   "dup_batch: src [%p, +%zu) overlaps dst [%p, +%zu) partially (src == dst, or disjoint)", src, nbytes, dst, 2 * nbytes);
+    }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (nbytes % 16 == 0 && ds_aligned16(src) && ds_aligned16(dst)) {
         const size_t nvec = nbytes / 16;

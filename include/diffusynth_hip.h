@@ -417,7 +417,10 @@ int ds_conv1x1_in_nchw(const float* x_nchw, int B, int Cin, int HW, const float*
 /* dst[0, nbytes) = dst[nbytes, 2 nbytes) = src[0, nbytes): the two halves of a classifier-free-guidance batch (DiffSynthSampler.py:311-320 evaluates
  * model(cat([x, x]), cat([t, t]), cat([uncond, cond]))) are identical up to the first operator that reads the condition — the plan computes
  * that prefix once at half the batch and duplicates its result (engine.py, `paired`).  dst == src: the first half is in place already,
- * only dst[nbytes, 2 nbytes) is written (r05: the plan computes the prefix into the first half of the full-batch tensor). */
+ * only dst[nbytes, 2 nbytes) is written (r05: the plan computes the prefix into the first half of the full-batch tensor).
+ * Either src == dst, or [src, src + nbytes) and [dst, dst + 2 nbytes) are disjoint: any other overlap is refused on the host with
+ * DS_EINVAL and nothing is launched (the copy would read bytes it has already overwritten).  Any nbytes and alignment: 16-byte aligned
+ * pointers with nbytes % 16 == 0 take the vector kernel, everything else two device-to-device copies (one when src == dst). */
 int ds_dup_batch(const void* src, void* dst, size_t nbytes, void* stream);
 int ds_nhwc_to_nchw(const void* x, int dtype, int B, int C, int C_stride, int H, int W, float* out, void* stream);
 
