@@ -23,8 +23,14 @@ __device__ __forceinline__ float2 stft_plus_decode(float c0, float c1, float c2)
 
 // tools.encode_stft of one bin; a zero spectrum has phase 0: (0, 1, 0)
 __device__ __forceinline__ void stft_plus_encode(float xr, float xi, float& c0, float& c1, float& c2) {
-    const float mag = sqrtf(xr * xr + xi * xi);
-    c0 = log1pf(mag);
-    c1 = mag > 0.f ? xr / mag : 1.f;
-    c2 = mag > 0.f ? xi / mag : 0.f;
+    // (as in the decode, the pair is first scaled by an exact power of two so that max(|xr|, |xi|) lies in [0.5, 1): the squares of a bin
+    // below 1e-19 are denormal or zero, and its (cos, sin) used to come out far off unit length or as (1, 0); those of a bin above 1e19
+    // overflow.  Scaling by a power of two commutes with every rounding below, so a bin in the normal range keeps its bits.)
+    const float pm = fmaxf(fabsf(xr), fabsf(xi));
+    const int pe = pm > 0.f && pm < 3.0e38f ? __builtin_amdgcn_frexp_expf(pm) : 0;
+    const float pa = ldexpf(xr, -pe), pb = ldexpf(xi, -pe);
+    const float n = sqrtf(pa * pa + pb * pb);
+    c0 = log1pf(ldexpf(n, pe));
+    c1 = n > 0.f ? pa / n : 1.f;
+    c2 = n > 0.f ? pb / n : 0.f;
 }

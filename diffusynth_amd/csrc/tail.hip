@@ -482,7 +482,14 @@ __global__ __launch_bounds__(1024) void vq_stats_finish_kernel(const unsigned* c
         out2[0] = mse;
         out2[1] = expf((float)(-ht));
         // the module's loss (VQGAN.py:64-66 / :133-134): commitment_cost * e_latent_loss (EMA) or q_latent_loss + commitment_cost * e_latent_loss
-        out2[2] = ema ? __fmul_rn(cc, mse) : __fadd_rn(mse, __fmul_rn(cc, mse));
+        // (two torch ops, two roundings.  __fmul_rn / __fadd_rn are inline `*` / `+` that carry their header's contraction with them: the
+        // pair used to be one v_fma_f32 whose product was never rounded, an ulp off the module's loss now and then.  Plain operators under
+        // the pragma, as in arranger.hip.)
+        {
+#pragma clang fp contract(off)
+            const float commit = cc * mse;
+            out2[2] = ema ? commit : mse + commit;
+        }
     }
 }
 }  // namespace

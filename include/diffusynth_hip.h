@@ -765,7 +765,8 @@ int ds_vq_nearest(const float* z_nchw, const float* codebook, const float* code_
                   int ncodes, float* q_nchw, int64_t* idx, void* stream);
 /* The quantiser's scalars from its outputs (VQGAN.py:62-73 / :131-144): out3[0] = mean((q - z)^2), out3[1] = perplexity =
  * exp(-sum_j p_j log(p_j + 1e-10)) (p = usage frequencies of the codes), out3[2] = the module's loss: commitment_cost * out3[0] (ema != 0:
- * VectorQuantizerEMA) or out3[0] + commitment_cost * out3[0] (VectorQuantizer).  ws: ds_vq_stats_ws_bytes. */
+ * VectorQuantizerEMA) or out3[0] + commitment_cost * out3[0] (VectorQuantizer), the product and the sum each rounded to fp32 on its own as
+ * the module's two torch ops are.  Indices outside [0, ncodes) count for no code.  ws: ds_vq_stats_ws_bytes. */
 size_t ds_vq_stats_ws_bytes(int ncodes);
 int ds_vq_stats(const float* z_nchw, const float* q_nchw, const int64_t* idx, int B, int D, int HW, int ncodes, float commitment_cost, int ema,
                 float* out3, void* ws, void* stream);
@@ -837,7 +838,9 @@ int ds_istft_plus_loop(const float* enc, int B, int F, int T, int hop, float* fr
  * (call sites load_presets.py:68, sound2sound_with_text.py:85, inpaint_with_text.py:97) + tools.pad_STFT
  * (tools.py:170-182: drop the DC row, zero-pad time to T_out) + tools.encode_stft (tools.py:320-331), fused:
  * audio [B][L] fp32 -> enc [B][3][512][T_out] fp32, T_out >= 1 + L/hop.  reflect_pad: 0 = zero padding of the
- * centred frames (librosa >= 0.10 default), 1 = reflect (older librosa). */
+ * centred frames (librosa >= 0.10 default), 1 = reflect (older librosa).  The (cos, sin) pair of a bin is of unit length to 6 x 2^-24
+ * whatever the bin's magnitude (1e-30 as well as 1e30: the pair is scaled by a power of two before it is squared); a bin of exactly 0
+ * and every column past the signal's frames is (0, 1, 0). */
 int ds_stft_plus(const float* audio, int B, int L, int hop, int reflect_pad, int T_out, float* enc, void* stream);
 /* The spectrogram and phase images the reference's UI shows for an STFT+ tensor (csrc/ui_images.hip; per clip tools.decode_stft +
  * tools.depad_STFT + np.abs / np.angle + spectrogram_to_Gradio_image / phase_to_Gradio_image: webUI/natural_language_guided_4/utils.py:8-86
