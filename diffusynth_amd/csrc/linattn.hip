@@ -337,7 +337,13 @@ extern "C" int ds_linattn_output(const ds_attn_params* p, void* stream) {
     linattn_publish_bounds(p, st);
 #endif
     if (p->dtype == DS_BF16) hipLaunchKernelGGL(attn_out_kernel<bf16>, grid, dim3(256), lds, st, *p);
-    else hipLaunchKernelGGL(attn_out_kernel<float>, grid, dim3(256), lds, st, *p);
+    else {
+        // 7 and 8 heads ask for 66 432 and 70 656 bytes: above the 64 KB a kernel gets without asking.  The limit is set once per device, so to the
+        // largest request check() admits (8 heads), not to this call's
+        constexpr int MAX_LDS_F32 = (8 * 1024 + 8 * 32 + 4 * 64 * 36) * (int)sizeof(float);
+        DS_SET_MAX_LDS(attn_out_kernel<float>, MAX_LDS_F32, "attn_out");
+        hipLaunchKernelGGL(attn_out_kernel<float>, grid, dim3(256), lds, st, *p);
+    }
     DS_CHECK_LAUNCH("attn_out");
     return DS_OK;
 }

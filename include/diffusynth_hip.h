@@ -245,7 +245,11 @@ int ds_gn_apply(const ds_gn_apply_params* p, void* stream);
  * VQGAN LinearAttention (VQGAN.py:261-272) on a precomputed qkv tensor [B][N][3*heads*32]:
  *   pass 1: per (sample, head, segment) softmax_n(k) . v^T partial context (max, sum, 32x32)
  *   combine: merges segments (+ the optional extra key/value token of linear_cat)
- *   pass 2: q~ = softmax_d(q + label_q) * scale;  out[n][h*32+e] = sum_d ctx[d][e] q~[d]      */
+ *   pass 2: q~ = softmax_d(q + label_q) * scale;  out[n][h*32+e] = sum_d ctx[d][e] q~[d]
+ * Limits (refused with an error code otherwise): heads <= 8 (pass 2 keeps every head's context in LDS: (heads * 1056 + 9216) * 4
+ * bytes in fp32, 70 656 at 8 heads) and 1 <= nseg <= N.  With nseg < N a segment can still be empty (per = ceil(N / nseg) pixels
+ * each, e.g. N = 10, nseg = 7: segments 5 and 6): it contributes (max = -inf, sum = 0, context = 0), which the combine weighs with
+ * exp(-inf) = 0.  The label strides are counted in floats and may exceed heads * 32.                   */
 typedef struct {
     const void* qkv;             /* [B][N][3*heads*32]: q | k | v, each (head, d)                      */
     int32_t B, N, heads, dtype;

@@ -156,6 +156,33 @@ def sweep_master(fail):
     report("master (2, L) batch, 2^20 + 4099 samples", fail)
 
 
+def sweep_linattn_paths(fail):
+    """The plain linear-attention files at eight exact cases of tests/linattn_ref.py, through the C ABI (this build compiles attn_out_kernel<float>
+    without its row-transposition path, and nothing else here calls ds_vq_attn_* directly): empty segments (N = 10 in 7), ragged N, 7 and 8 heads,
+    strided labels, both dtypes; both C of the vq kernels with an empty block (nseg = 16 over five groups, nseg = 8 at N = 33), one block over six
+    ragged groups, stats_ws NULL.  The results are compared bit for bit as in tests/test_hip_linattn_paths.py."""
+    import linattn_ref as R
+    import test_hip_linattn_paths as T
+    lin = [dict(bf16=False, B=3, N=10, heads=4, nseg=7), dict(bf16=True, B=1, N=10, heads=1, nseg=7, token=True, pad=8),
+           dict(bf16=False, B=3, N=257, heads=7, nseg=2, q_softmax=1, lq=True, pad=8), dict(bf16=True, B=1, N=513, heads=8, nseg=2, q_softmax=1, lq=True, pad=8)]
+    for a in lin:
+        assert a in R.linattn_args()
+        c = R.linattn_case(**a)
+        assert ("empty_segment" in R.seg_paths(c.N, c.nseg, c.bf16)) == (c.N == 10)
+        ctx, out = T._run_linattn(c)
+        assert torch.equal(ctx, c.want_ctx) and torch.equal(out, c.want_out), c.id
+    report("linattn paths: empty segments, ragged N, 7 / 8 heads, strided labels (fp32 and bf16)", fail)
+    vq = [(80, 3, 600, True, 16, True), (160, 3, 600, False, 16, True), (80, 3, 657, True, 4, True), (160, 1, 33, True, 4, False)]
+    for a in vq:
+        assert a in R.vq_args()
+        Cc, B, N, skip, nseg, st = a
+        assert ("empty_block" in R.vq_paths(N, nseg)) == (nseg == 16) and "ragged_tile" in R.vq_paths(N, nseg)
+        c, want = R.vq_case(Cc, B, N, skip), R.vq_expect(R.vq_case(Cc, B, N, skip), nseg)
+        ctx, wfold, y, ws = T._run_vq(c, nseg, st)
+        assert torch.equal(ctx, want.ctx) and torch.equal(wfold, want.wfold) and torch.equal(y, want.y) and (ws is None or torch.equal(ws.double(), want.stats)), a
+    report("vq_attn paths: C 80 / 160, an empty block, one block over six ragged groups, stats_ws NULL", fail)
+
+
 def _partials(stored, parts):
     """(sum, sumsq) of ``parts`` chunks of each sample of a device tensor as fp32 [B][parts][2], placed 24 bytes into a NaN-filled allocation:
     the base is 8-byte but not 16-byte aligned and anything read beyond the buffer is NaN (tests/gn_partials_ref.py:guarded)."""
@@ -471,6 +498,10 @@ def main():
         sweep_perform(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
         sys.exit(1 if fail else 0)
+    if "--only-linattn-paths" in sys.argv:
+        sweep_linattn_paths(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
     if "--only-arranger" in sys.argv:
         sweep_arranger(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
@@ -555,6 +586,8 @@ def main():
     sweep_master(fail)
     # 6) GroupNorm from raw partials in every kernel that reduces them, the depthwise families, the chains without ds_gn_finalize
     sweep_gn_partials(fail)
+    # 7) the plain linear-attention files on the paths of tests/test_hip_linattn_paths.py
+    sweep_linattn_paths(fail)
     if fail:
         print("BOUNDS VIOLATIONS", fail)
         sys.exit(1)
