@@ -6,12 +6,13 @@
 //   ds_text_attention   softmax_k(q . k d^-0.5 + mask_k) v per (sample, head, query), bidirectional, from the stacked [B S][3H] q|k|v rows
 //   ds_text_tail        the pooler's tanh, the projection's ReLU, and x / max(||x||_2, eps) per row
 #include "common.hpp"
+#include "norm_parts.hpp"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ embeddings
 // one block per token.  Position id: pad + (number of non-pad tokens up to and including this one), pad for a pad token; a function of
-// input_ids alone.  The LayerNorm is add_layernorm_kernel's (misc.hip): two passes, double partial sums, a tree over the 256 threads.
+// input_ids alone.  The LayerNorm is add_layernorm_kernel's (misc.hip), layernorm_row: two passes, double partial sums, a tree over the 256 threads.
 // A row's bits depend on its own ids up to s only, never on S or B.
 __global__ __launch_bounds__(256) void text_embed_kernel(const int64_t* ids, int S, int pad, const float* word, int V, const float* pos, int P,
                                                          const float* type0, const float* gamma, const float* beta, int H, float eps, float* out) {
@@ -21,12 +22,7 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int64_t* ids, int
     const int64_t* row = ids + (size_t)b * S;
     int c = 0;
     for (int i = tid; i <= s; i += 256) c += row[i] != pad;
-    cnt[tid] = c;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) cnt[tid] += cnt[tid + o];
-        __syncthreads();
-    }
+    block_tree_sum256(cnt, c);
     const int64_t id = row[s];
     const int pid = id != pad ? pad + cnt[0] : pad;
     float* ob = out + ((size_t)b * S + s) * H;
@@ -36,30 +32,8 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int64_t* ids, int
     }
     const float* wr = word + (size_t)id * H;
     const float* pr = pos + (size_t)pid * H;
-    double sum = 0.0;
-    for (int i = tid; i < H; i += 256) sum += (double)((wr[i] + pr[i]) + type0[i]);
     __syncthreads();
-    red[tid] = sum;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    const float mean = (float)(red[0] / H);
-    __syncthreads();
-    double q = 0.0;
-    for (int i = tid; i < H; i += 256) {
-        const float d = ((wr[i] + pr[i]) + type0[i]) - mean;
-        q += (double)d * d;
-    }
-    red[tid] = q;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    const float rstd = 1.0f / sqrtf((float)(red[0] / H) + eps);
-    for (int i = tid; i < H; i += 256) ob[i] = (((wr[i] + pr[i]) + type0[i]) - mean) * rstd * gamma[i] + beta[i];
+    layernorm_row([&](int i) { return (wr[i] + pr[i]) + type0[i]; }, H, gamma, beta, eps, ob, red);
 }
 
 // ------------------------------------------------------------------------------------------------ attention
@@ -181,12 +155,7 @@ __global__ __launch_bounds__(256) void text_l2_normalize_kernel(const float* x, 
     const float* xr = x + (size_t)blockIdx.x * D;
     double q = 0.0;
     for (int i = tid; i < D; i += 256) q += (double)xr[i] * xr[i];
-    red[tid] = q;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
+    block_tree_sum256(red, q);
     const float norm = fmaxf((float)sqrt(red[0]), eps);
     for (int i = tid; i < D; i += 256) out[(size_t)blockIdx.x * D + i] = xr[i] / norm;
 }

@@ -358,6 +358,23 @@ __device__ __forceinline__ void block_stats_write(float s1, float s2, float* red
     block_stats_write(s1, s2, red, dst, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6));
 }
 
+// The GroupNorm finish, the one copy: float64 (sum, sum of squares) over `count` elements -> a = rstd and am = rstd * mean, what gn_ab
+// holds.  A kernel's gn_part form equals its gn_ab form bit for bit (tests/test_hip_gn_partials.py) because every reducer ends here.
+__device__ __forceinline__ void gn_rstd_pair(double s1, double s2, double count, float eps, float& a, float& am) {
+    const double mean = s1 / count;
+    double var = s2 / count - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const double rstd = 1.0 / sqrt(var + (double)eps);
+    a = (float)rstd;
+    am = (float)(rstd * mean);
+}
+// ... for one wave whose lanes hold the sums in pieces
+__device__ __forceinline__ void gn_wave_finish(double s1, double s2, double count, float eps, float& a, float& am) {
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    gn_rstd_pair(s1, s2, count, eps, a, am);
+}
+
 // Two-phase form of gn_from_partials for prologues that have other loads to issue: gn_partials_issue() requests up to
 // 4 x 64 partial pairs (8-byte loads, no wait), gn_partials_finish() reduces them in float64 (and walks any remaining ones).
 struct GnPartialLoads { float2 v[4]; };
@@ -398,14 +415,7 @@ __device__ __forceinline__ void gn_partials_finish(const GnPartialLoads& g, cons
         s1 += (double)DS_LD(float, pp + 2 * i, DS_BX_GNPART);
         s2 += (double)DS_LD(float, pp + 2 * i + 1, DS_BX_GNPART);
     }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + (double)eps);
-    a = (float)rstd;
-    am = (float)(rstd * mean);
+    gn_wave_finish(s1, s2, count, eps, a, am);
 }
 
 // GroupNorm(1,C) statistics straight from the producer's (sum, sumsq) partials: one wave, float64, no LDS.
@@ -420,14 +430,7 @@ __device__ __forceinline__ void gn_from_partials(const float* part, int parts, d
         s1 += (double)DS_LD(float, pp + 2 * i, bx);
         s2 += (double)DS_LD(float, pp + 2 * i + 1, bx);
     }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + (double)eps);
-    a = (float)rstd;
-    am = (float)(rstd * mean);
+    gn_wave_finish(s1, s2, count, eps, a, am);
 }
 
 // ---- shared by the attention kernels, both tiers (attn_fused.hip + attn_out2.hpp, vq_attn.hip, attn_x3.hip; PARTF also linattn.hip) -----------

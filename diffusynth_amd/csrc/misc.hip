@@ -3,6 +3,7 @@
 #include <stdarg.h>
 
 #include "common.hpp"
+#include "norm_parts.hpp"
 
 // ------------------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -50,7 +51,8 @@ extern "C" int ds_bounds_fetch_conv_halo3_hp(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_conv_quad(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_conv_quad_split(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_conv_smalln(ds_bounds_rec*, int);
-extern "C" int ds_bounds_fetch_dwconv_gn(ds_bounds_rec*, int);
+extern "C" int ds_bounds_fetch_dwconv7(ds_bounds_rec*, int);
+extern "C" int ds_bounds_fetch_groupnorm(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_attn_fused(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_attn_x3(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_linattn(ds_bounds_rec*, int);
@@ -75,7 +77,7 @@ extern "C" int ds_bounds_report(char* buf, int n, int reset) {
                                    "resample_poly", "mix_notes_shaped", "mask_layers", "mask_prefilter", "mask_zoom", "master_gain", "master_limit", "pv_formant"};
     static const char* bnames[] = {"src0", "src1", "weights", "out", "res", "bias", "fold_t1", "fold_t2", "gn_ab", "gn_part", "stats_part",
                                    "aux0", "aux1", "aux2", "aux3"};
-    int (*fetch[])(ds_bounds_rec*, int) = {ds_bounds_fetch_conv_igemm, ds_bounds_fetch_conv_splitk, ds_bounds_fetch_conv_halo3, ds_bounds_fetch_conv_halo3_hp, ds_bounds_fetch_conv_quad, ds_bounds_fetch_conv_quad_split, ds_bounds_fetch_conv_smalln, ds_bounds_fetch_dwconv_gn,
+    int (*fetch[])(ds_bounds_rec*, int) = {ds_bounds_fetch_conv_igemm, ds_bounds_fetch_conv_splitk, ds_bounds_fetch_conv_halo3, ds_bounds_fetch_conv_halo3_hp, ds_bounds_fetch_conv_quad, ds_bounds_fetch_conv_quad_split, ds_bounds_fetch_conv_smalln, ds_bounds_fetch_dwconv7, ds_bounds_fetch_groupnorm,
                                            ds_bounds_fetch_attn_fused, ds_bounds_fetch_attn_x3, ds_bounds_fetch_linattn, ds_bounds_fetch_conv1x1_x3, ds_bounds_fetch_conv7x7_c4, ds_bounds_fetch_convt4x4_c80, ds_bounds_fetch_conv3x3_c80, ds_bounds_fetch_conv3x3_f32_n4, ds_bounds_fetch_vq_attn,
                                            ds_bounds_fetch_ui_images, ds_bounds_fetch_arranger, ds_bounds_fetch_pitch, ds_bounds_fetch_resample_poly, ds_bounds_fetch_inpaint_mask, ds_bounds_fetch_master};
     int hits = 0, pos = 0;
@@ -194,39 +196,13 @@ __global__ void nhwc_to_nchw_kernel(const T* x, int C, int Cs, int HW, float* ou
     }
 }
 
-}  // namespace
-
-namespace {
-// one block per row: two-pass (mean, then centred variance) in fp32 with double partial sums
+// one block per row: layernorm_row (norm_parts.hpp) over a[i] + r[i]
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const float* a, const float* r, const float* gamma, const float* beta, int D,
                                                             float eps, float* out) {
     __shared__ double red[256];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* ab = a + (size_t)b * D;
-    const float* rb = r + (size_t)b * D;
-    double s = 0.0;
-    for (int i = tid; i < D; i += 256) s += (double)(ab[i] + rb[i]);
-    red[tid] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    const float mean = (float)(red[0] / D);
-    __syncthreads();
-    double q = 0.0;
-    for (int i = tid; i < D; i += 256) {
-        const float d = (ab[i] + rb[i]) - mean;
-        q += (double)d * d;
-    }
-    red[tid] = q;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    const float rstd = 1.0f / sqrtf((float)(red[0] / D) + eps);
-    for (int i = tid; i < D; i += 256) out[(size_t)b * D + i] = ((ab[i] + rb[i]) - mean) * rstd * gamma[i] + beta[i];
+    const float* ab = a + (size_t)blockIdx.x * D;
+    const float* rb = r + (size_t)blockIdx.x * D;
+    layernorm_row([&](int i) { return ab[i] + rb[i]; }, D, gamma, beta, eps, out + (size_t)blockIdx.x * D, red);
 }
 }  // namespace
 

@@ -554,7 +554,7 @@ def ceil_div(a, b):
 
 
 # (tag, dtype, (C0, C1), (H, W), matrix-core weights, out_split, strip, family, (tile rows, tile columns, channels per block) or None)
-# Tile kernels (dwconv_gn.hip: a block holds 2048 / NV pixels of NV channel vectors; columns 8 / 16 / 32 by lt_twl): bf16 and fp32 NV = 4
+# Tile kernels (dwconv7.hip: a block holds 2048 / NV pixels of NV channel vectors; columns 8 / 16 / 32 by lt_twl): bf16 and fp32 NV = 4
 # 512 pixels = 64 x 8 (W <= 8), 32 x 16 (W <= 16), 16 x 32; fp32 NV = 8 256 pixels = 32 x 8 (W <= 8), 16 x 16.
 DW_ROWS = [("direct", L.DS_BF16, (40, 0), (10, 9), False, 0, 0, "direct", None),
            ("direct", L.DS_F32, (20, 0), (10, 9), False, 0, 0, "direct", None),

@@ -413,6 +413,32 @@ def test_gn_stats_and_apply(dt, G, act):
     assert rel_err(h.from_nhwc(out), want) < (1e-5 if dt == L.DS_F32 else 1e-2)
 
 
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("G", [1, 4])
+def test_gn_apply_generic_kernel(dt, G):
+    """More than 256 channel vectors per pixel (C / 4 = C / 8 = 257): ds_gn_apply takes the element-wise gn_apply_kernel, not the table
+    kernel.  SiLU, channel bias and residual; the reference in float64."""
+    h = H()
+    B, Cc, Hh, Ww = 2, 1028 if dt == L.DS_F32 else 2056, 1, 5
+    x = synth_input("k_gng_x", (B, Cc, Hh, Ww)) * 1.5 + 0.3
+    r = synth_input("k_gng_r", (B, Cc, Hh, Ww))
+    cb = synth_input("k_gng_cb", (B, Cc))
+    g = 1 + 0.2 * synth_input("k_gng_g", (Cc,))
+    be = 0.3 * synth_input("k_gng_b", (Cc,))
+    xd, rd = h.to_nhwc(x, dt), h.to_nhwc(r, dt)
+    y = F.silu(F.group_norm(h.from_nhwc(xd).double(), G, g.double(), be.double(), 1e-5))
+    want = y + cb.double()[:, :, None, None] + h.from_nhwc(rd).double()
+    ab = torch.empty(B, G, 2, device="cuda")
+    L.call("ds_gn_stats", xd.data_ptr(), dt, B, Hh * Ww, Cc, G, 1e-5, ab.data_ptr(), L.current_stream())
+    out = torch.empty_like(xd)
+    gd, bd, cbd = g.cuda(), be.cuda(), cb.cuda().contiguous()
+    p = L.GnApplyParams(x=xd.data_ptr(), res=rd.data_ptr(), out=out.data_ptr(), gn_ab=ab.data_ptr(), gamma=gd.data_ptr(),
+                        beta=bd.data_ptr(), cbias=cbd.data_ptr(), cb_stride=Cc, B=B, HW=Hh * Ww, C=Cc, G=G, act=L.ACT_SILU, dtype=dt)
+    L.call("ds_gn_apply", C.byref(p), L.current_stream())
+    h.sync()
+    assert rel_err(h.from_nhwc(out), want) < (1e-5 if dt == L.DS_F32 else 1e-2)
+
+
 # ----------------------------------------------------------------------------------------- attention
 def _attention(dt, qkv_nchw, heads, nseg, lq=None, lk=None, lv=None, q_softmax=1, scale=32 ** -0.5):
     h = H()

@@ -389,7 +389,105 @@ def conv_c80_cases():
                     yield "convt4x4_c80 cin=%d B=%d HxW=%dx%d %s bias=%d" % (cin, B, H, W, form, b is not None), dict(out=out, stats_ws=ws)
 
 
-FAMILIES = {"attn_bf16": attn_bf16_cases, "row_kernels": row_kernels_cases, "conv_c80": conv_c80_cases}
+def norms_cases():
+    """Every entry point of groupnorm.hip on each path its launcher takes, and the LayerNorm / L2-norm rows of misc.hip and clap_text.hip at
+    row lengths around the 256 threads of their tree sum.  Outputs start from a fixed pattern, so an unwritten element shows in the digest."""
+    import torch
+    from diffusynth_amd import _lib as L
+    lib, st = L.load(), L.current_stream()
+    TDT = {L.DS_F32: torch.float32, L.DS_BF16: torch.bfloat16}
+    NAME = {L.DS_F32: "fp32", L.DS_BF16: "bf16"}
+    g = torch.Generator().manual_seed(2718)
+
+    def pat(dtype, *shape):
+        n = 1
+        for d in shape:
+            n *= d
+        return ((torch.arange(n, dtype=torch.float32, device="cuda") % 97) * 0.5 - 7.0).reshape(shape).to(dtype)
+
+    def image(dt, B, HW, Cc):
+        return (_rand(g, B, HW, Cc) * 1.5 + 0.3).to(TDT[dt]).cuda()
+
+    def partials(x, n):
+        """n equal (sum, sum of squares) partials per sample of x [B][HW][C]"""
+        xf = x.float().reshape(x.shape[0], -1)
+        return torch.stack([xf.sum(1), (xf * xf).sum(1)], 1)[:, None, :].repeat(1, n, 1).div(float(n)).contiguous()
+
+    # ---- ds_gn_finalize: fewer partials than threads, one per thread, a ragged second trip, several trips; a constant image (variance ~ 0: the clamp)
+    for parts, const in ((1, False), (64, False), (257, False), (600, False), (64, True)):
+        x = torch.full((3, parts, 64), 0.7) if const else _rand(g, 3, parts, 64) * 1.3 + 0.2
+        part = torch.stack([x.sum(2), (x * x).sum(2)], 2).contiguous().cuda()
+        ab = pat(torch.float32, 3, 2)
+        L.call("ds_gn_finalize", part.data_ptr(), 3, parts, float(parts * 64), 1e-5, ab.data_ptr(), st)
+        yield "gn_finalize B=3 parts=%d%s" % (parts, " constant" if const else ""), dict(ab=ab)
+
+    # ---- statistics
+    for dt, (Cc, G, HW) in itertools.product((L.DS_F32, L.DS_BF16), ((96, 1, 60), (96, 8, 60), (160, 16, 7))):
+        x, ab = image(dt, 2, HW, Cc), pat(torch.float32, 2, G, 2)
+        L.call("ds_gn_stats", x.data_ptr(), dt, 2, HW, Cc, G, 1e-6, ab.data_ptr(), st)
+        yield "gn_stats %s C=%d G=%d HW=%d" % (NAME[dt], Cc, G, HW), dict(ab=ab)
+    for (Cc, dt, Gs), HW in itertools.product(((80, L.DS_BF16, (1, 16)), (96, L.DS_F32, (1, 8)), (160, L.DS_BF16, (1, 16))), (7, 60, 1500)):
+        x = image(dt, 2, HW, Cc)
+        nws = lib.ds_gn_stats_ws_floats(2, HW, Cc)
+        for G in Gs:
+            ws, ab, ab2 = pat(torch.float32, nws), pat(torch.float32, 2, G, 2), pat(torch.float32, 2, G, 2)
+            L.call("ds_gn_stats_stream", x.data_ptr(), dt, 2, HW, Cc, G, 1e-6, ws.data_ptr(), ab.data_ptr(), st)
+            L.call("ds_gn_stats_finish", ws.data_ptr(), 2, nws // (2 * Cc * 2), Cc, G, HW, 1e-6, ab2.data_ptr(), st)
+            yield "gn_stats_stream + finish %s C=%d G=%d HW=%d" % (NAME[dt], Cc, G, HW), dict(ws=ws, ab=ab, ab_finish=ab2)
+
+    # ---- ds_gn_apply, one block of cases per path of its launcher
+    def apply(dt, B, HW, Cc, G, act, cbias, res, part):
+        x, r, out = image(dt, B, HW, Cc), image(dt, B, HW, Cc), pat(TDT[dt], B, HW, Cc)
+        gamma, beta, cb = (_rand(g, Cc) * 0.2 + 1.0).cuda(), (_rand(g, Cc) * 0.3).cuda(), _rand(g, B, Cc + 4).cuda()
+        p = L.GnApplyParams(x=x.data_ptr(), res=r.data_ptr() if res else None, out=out.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(),
+                            cbias=cb.data_ptr() if cbias else None, cb_stride=Cc + 4, B=B, HW=HW, C=Cc, G=G, act=act, dtype=dt)
+        if part:
+            gp = partials(x, 5).cuda()
+            p.gn_part, p.gn_parts, p.gn_count, p.gn_eps = gp.data_ptr(), 5, float(HW * Cc), 1e-5
+        else:
+            ab = torch.empty(B, G, 2, device="cuda")
+            L.call("ds_gn_stats", x.data_ptr(), dt, B, HW, Cc, G, 1e-5, ab.data_ptr(), st)
+            p.gn_ab = ab.data_ptr()
+        L.call("ds_gn_apply", C.byref(p), st)
+        torch.cuda.synchronize()                                  # (the inputs die with this frame)
+        return ("%s C=%d G=%d HW=%d act=%d cbias=%d res=%d" % (NAME[dt], Cc, G, HW, act, cbias, res)), dict(out=out)
+
+    for Cc, res, HW in itertools.product((96, 192, 384, 768), (False, True), (3, 130)):
+        label, bufs = apply(L.DS_BF16, 3, HW, Cc, 1, L.ACT_NONE, False, res, True)
+        yield "gn_apply lazy-fast " + label, bufs
+    for (dt, Cc, act, cbias), HW in itertools.product(((L.DS_F32, 96, L.ACT_NONE, False), (L.DS_BF16, 96, L.ACT_SILU, False),
+                                                       (L.DS_BF16, 96, L.ACT_NONE, True), (L.DS_BF16, 80, L.ACT_NONE, False)), (3, 130)):
+        label, bufs = apply(dt, 3, HW, Cc, 1, act, cbias, True, True)
+        yield "gn_apply lazy " + label, bufs
+    for dt, G, act, cbias, res in itertools.product((L.DS_F32, L.DS_BF16), (1, 8), (L.ACT_NONE, L.ACT_GELU, L.ACT_SILU, L.ACT_RELU), (False, True), (False, True)):
+        label, bufs = apply(dt, 3, 60, 96, G, act, cbias, res, False)
+        yield "gn_apply table " + label, bufs
+    for dt, G in itertools.product((L.DS_F32, L.DS_BF16), (1, 4)):
+        label, bufs = apply(dt, 2, 5, 1028 if dt == L.DS_F32 else 2056, G, L.ACT_SILU, True, True, False)
+        yield "gn_apply generic " + label, bufs
+
+    # ---- the LayerNorm and L2-norm rows
+    for D in (1, 255, 256, 257, 768):
+        a, r, out = (_rand(g, 3, D) * 1.2 + 0.1).cuda(), _rand(g, 3, D).cuda(), pat(torch.float32, 3, D)
+        gamma, beta = (_rand(g, D) * 0.2 + 1.0).cuda(), (_rand(g, D) * 0.3).cuda()
+        L.call("ds_add_layernorm", a.data_ptr(), r.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 3, D, 1e-5, out.data_ptr(), st)
+        yield "add_layernorm B=3 D=%d" % D, dict(out=out)
+    ids = torch.tensor([[0, 9, 1, 23, 2, 1, 1], [0, 48, 17, 5, 31, 12, 2]], dtype=torch.int64).cuda()      # pad = 1: one inside, two at the end
+    for Hd in (5, 768):
+        word, pos, type0 = _rand(g, 50, Hd).cuda(), _rand(g, 16, Hd).cuda(), _rand(g, Hd).cuda()
+        gamma, beta, out = (_rand(g, Hd) * 0.2 + 1.0).cuda(), (_rand(g, Hd) * 0.3).cuda(), pat(torch.float32, 2, 7, Hd)
+        L.call("ds_text_embed", ids.data_ptr(), 2, 7, 1, word.data_ptr(), 50, pos.data_ptr(), 16, type0.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+               Hd, 1e-5, out.data_ptr(), st)
+        yield "text_embed B=2 S=7 H=%d" % Hd, dict(out=out)
+    for D in (1, 257, 512):
+        x, out = _rand(g, 3, D), pat(torch.float32, 3, D)
+        x[1] = 0                                                  # an all-zero row stays zero
+        x = x.cuda()
+        L.call("ds_text_tail", x.data_ptr(), 3, D, L.TAIL["DS_TAIL_L2NORM"], 1e-12, out.data_ptr(), st)
+        yield "text_tail l2norm B=3 D=%d" % D, dict(out=out)
+
+
+FAMILIES = {"attn_bf16": attn_bf16_cases, "row_kernels": row_kernels_cases, "conv_c80": conv_c80_cases, "norms": norms_cases}
 
 
 def child(family):
