@@ -311,6 +311,12 @@ int ds_attn_fused_segments_gen(int B, int N, int C, int gen);
 /* which generation the two passes would run for p, for plan inspection (no launch): bit 0 = the context pass runs the second generation,
  * bit 1 = the output pass does */
 int ds_attn_fused_generations(const ds_attn_fused_params* p);
+/* Limits of both passes (tests/test_hip_attn_paths.py runs each): nseg is any count >= 1.  The pixels are cut into ceil(units / nseg) units per
+ * segment (units: 32-pixel tiles; 64-pixel groups in the first generation at C = 96, N >= 4096); a count above the number of units leaves
+ * the surplus segments empty — they write the neutral partial (max -inf, sum 0, context 0) and the combine gives them weight 0 — so `part`
+ * is always ds_linattn_part_floats(B, 4, nseg) and every one of its partials is written.  ds_attn_fused_segments(_gen) look at B alone:
+ * a caller with a batch_hint passes the hint as B.  Every block of the output pass has at least one tile, so every stats_part slot is
+ * written by a block with work.  label_q rows are lq_stride floats apart and only their first 128 are read. */
 
 /* ---------------------------------------------------------------- fused LinearAttention of the VQGAN (bf16 tier; csrc/vq_attn.hip)
  * VQGAN.py:246-272 (heads = 1, dim_head = 32, softmax over n on k only): q enters linearly, so after the context the block is one 1x1
@@ -381,6 +387,11 @@ int ds_attn_x3_stats_parts(const ds_attn_x3_params* p);
 int ds_attn_x3_segments(int B, int N, int C);
 size_t ds_attn_x3_qplane_bytes(int B, int N);
 size_t ds_attn_x3_mfold_bytes(int B, int C);
+/* Limits (tests/test_hip_attn_paths.py): nseg is any count >= 1, as for ds_attn_fused_params — surplus segments are empty and weigh 0 in
+ * the combine; a count that is no multiple of 8 leaves the last block's surplus waves without a partial to write.  At C = 192 / 384 the q
+ * projection is a launch of its own that cuts the tiles by a count taken from B (one round of blocks), never from batch_hint or nseg: it
+ * decides which wave projects which tile and no stored bit, the q planes being per tile.  Form B reads stats_part with the slot count
+ * of its own first pass (ds_attn_x3_stats_parts), every slot of which that pass has written. */
 
 /* ---------------------------------------------------------------- diagnostics
  * libdiffusynth_hip_bounds.so (tools/build_variants.py bounds; -DDS_BOUNDS=1) checks every global access of the

@@ -183,6 +183,28 @@ def sweep_linattn_paths(fail):
     report("vq_attn paths: C 80 / 160, an empty block, one block over six ragged groups, stats_ws NULL", fail)
 
 
+def sweep_attn_paths(fail):
+    """The fused attention of both tiers at eight exact cases of tests/attn_ref.py, through the C ABI and compared bit for bit as in
+    tests/test_hip_attn_paths.py: bf16 first generation with empty segments (nseg 65 over nine groups), 64-pixel groups with a ragged second
+    tile (N = 4129) walked by one block per sample (batch_hint 512), the 384-channel context pass with two heads per block, second-generation
+    waves past nseg and without a tile, gen = 0 across its threshold; split precision at C = 96 (fused q + Z) and C = 192 / 384 (q planes),
+    form B with out_planes, nseg 65 over nine tiles."""
+    import attn_ref as R
+    import test_hip_attn_paths as T
+    want = [dict(C=96, B=2, N=257, gen=1, nseg=65), dict(C=96, B=1, N=4129, gen=1, nseg=65, hint=512, wide=False), dict(C=384, B=1, N=1057, gen=2, nseg=8, wide=False),
+            dict(C=192, B=2, N=33, gen=2, nseg=2), dict(C=96, B=2, N=129, gen=0, nseg="lib", hint=96)]
+    cases = R.gpu_cases()
+    for w in want:
+        k = next(k for k in cases if all(k[n] == v for n, v in w.items()))
+        T.test_attn_fused_exact(k)
+    report("attn_fused paths: empty segments, T = 2 ragged, one block per sample, C = 384 second generation, waves without a tile, gen 0", fail)
+    x3 = R.x3_gpu_cases()
+    for w in (dict(C=96, N=1057, flavour="wlo"), dict(C=192, N=257, nseg=65), dict(C=384, N=33)):
+        k = next(k for k in x3 if all(k[n] == v for n, v in w.items()))
+        T.test_attn_x3_exact(k)
+    report("attn_x3 paths: fused q + Z, q planes, form B with out_planes, nseg above the tile count", fail)
+
+
 def _partials(stored, parts):
     """(sum, sumsq) of ``parts`` chunks of each sample of a device tensor as fp32 [B][parts][2], placed 24 bytes into a NaN-filled allocation:
     the base is 8-byte but not 16-byte aligned and anything read beyond the buffer is NaN (tests/gn_partials_ref.py:guarded)."""
@@ -502,6 +524,10 @@ def main():
         sweep_linattn_paths(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
         sys.exit(1 if fail else 0)
+    if "--only-attn-paths" in sys.argv:
+        sweep_attn_paths(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
     if "--only-arranger" in sys.argv:
         sweep_arranger(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
@@ -588,6 +614,7 @@ def main():
     sweep_gn_partials(fail)
     # 7) the plain linear-attention files on the paths of tests/test_hip_linattn_paths.py
     sweep_linattn_paths(fail)
+    sweep_attn_paths(fail)
     if fail:
         print("BOUNDS VIOLATIONS", fail)
         sys.exit(1)
