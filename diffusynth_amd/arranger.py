@@ -14,6 +14,8 @@ open note of its pitch, the tempo map integrated, velocity as level and the refe
 the real note-off, both applied inside the mix (ds_mix_notes_shaped).
 Opt-in (`master=Mastering(...)`, off by default): an RMS gain and a peak-hold look-ahead limiter behind the mix (ds_master_gain,
 ds_master_limit; include/diffusynth_hip.h has the arithmetic), once per render, in arrange / get_music once on the sum of the tracks.
+With Mastering(target_lufs=...) the gain is the one that takes the mix's K-weighted gated loudness (BS.1770) to the target instead
+(ds_loudness, ds_loudness_gain between the two; diffusynth_amd/loudness.py).
 Opt-in (`formant=Formant(...)`, off by default): every link of a chain keeps the note's spectral envelope where the source had it
 (ds_pv_formant between ds_pv_vocode and ds_pv_istft: cepstral envelope, warped ratio, one more launch per level), so a note shifted two
 octaves up is still the same instrument.  Beyond the reference; defined in include/diffusynth_hip.h.
@@ -33,6 +35,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .loudness import check_sample_rate as _lu_rate, energy_of as _lu_energy, measure as _lu_measure, result as _lu_result     # (the package's
+# attribute `loudness` is the function of that name, not the module)
 
 N_FFT, HOP = 4096, 1024
 _NO_GPU = "diffusynth_amd arranger runs on MI355X only (%s); no CPU fallback"
@@ -552,25 +556,34 @@ def tempo_map_of(tracks):
     return sorted(out, key=lambda tt: tt[0])
 
 
-# ---------------------------------------------------------------------------------------------------- mastering: RMS gain, limiter
+# ---------------------------------------------------------------------------------------------------- mastering: gain, limiter
 @dataclasses.dataclass(frozen=True, kw_only=True)
 class Mastering:
     """The stage behind a mix (master(), Track.render(master=...), DiffSynth(master=...)): a gain that takes the signal to target_rms (at
     most max_gain; None: no gain), then a limiter that keeps |y| <= ceiling: the gain a sample needs is held for `hold` seconds behind it,
     reached `lookahead` seconds ahead of it and smoothed by a moving average of 2 lookahead + 1 samples, so it never exceeds what any sample
     needs (include/diffusynth_hip.h).  Times are floored to samples as int(t * sample_rate).  The defaults are choices, not
-    measurements: the reference's tools.rms_normalize default, 20 dB, -1 dBFS, 5 ms and 50 ms."""
-    target_rms: float = 0.1
+    measurements: the reference's tools.rms_normalize default, 20 dB, -1 dBFS, 5 ms and 50 ms.
+
+    target_lufs (in [-70, 0]; target_rms must then be None) makes the gain the one that takes the signal's K-weighted gated loudness
+    (BS.1770: loudness()) to that many LUFS, at most max_gain; a signal with nothing to measure keeps a gain of 1."""
+    target_rms: float | None = 0.1
     max_gain: float = 10.0
     ceiling: float = 10 ** (-1 / 20)
     lookahead: float = 0.005
     hold: float = 0.05
+    target_lufs: float | None = None
 
     def __post_init__(self):
         for f in dataclasses.fields(self):
             v = getattr(self, f.name)
-            if not (_finite_number(v) or (f.name == "target_rms" and v is None)):
+            if not (_finite_number(v) or (f.name in ("target_rms", "target_lufs") and v is None)):
                 raise ValueError(f"Mastering: {f.name} must be a finite number, not {v!r}")
+        if self.target_lufs is not None:
+            if self.target_rms is not None:
+                raise ValueError(f"Mastering: target_lufs {self.target_lufs!r} and target_rms {self.target_rms!r} are both set: one gain, so target_rms must be None beside a target_lufs")
+            if not -70.0 <= self.target_lufs <= 0.0:
+                raise ValueError(f"Mastering: target_lufs {self.target_lufs!r} outside [-70, 0]")
         for name in ("target_rms", "max_gain"):                 # (the kernels take them as fp32)
             v = getattr(self, name)
             if v is not None and not (v > 0 and 0 < float(np.float32(v)) < math.inf):
@@ -586,6 +599,8 @@ class Mastering:
         """(A, R): lookahead and hold in samples, floored; ValueError above the kernels' caps."""
         if not isinstance(sample_rate, (int, np.integer)) or isinstance(sample_rate, (bool, np.bool_)) or sample_rate <= 0:
             raise ValueError(f"master: sample_rate must be a positive int, not {sample_rate!r}")
+        if self.target_lufs is not None:
+            _lu_rate(sample_rate, "master (target_lufs)")
         a, r = int(self.lookahead * int(sample_rate)), int(self.hold * int(sample_rate))
         if a > _MS["DS_MS_MAX_LOOKAHEAD"]:
             raise ValueError(f"master: lookahead {self.lookahead} s is {a} samples at {sample_rate} Hz (at most {_MS['DS_MS_MAX_LOOKAHEAD']})")
@@ -606,32 +621,47 @@ def _check_master(master):
     raise ValueError(f"master: None or a Mastering, not {master!r}")
 
 
-@torch.no_grad()
-def master(signals, mastering=Mastering(), *, sample_rate=16000, pcm16=False, return_stats=False):
-    """Gain and limiter (Mastering) for one 1-D CUDA tensor, a (B, L) tensor or a list of 1-D tensors of different lengths, each signal by
-    itself -> the same container, fp32, or int16 = rint(y * 32767) with pcm16=True; with return_stats=True (result, MasterStats).
-    One table upload, ds_master_gain and ds_master_limit, no device -> host copy.  A signal's result is the same bits alone and in a batch."""
-    if not isinstance(mastering, Mastering):
-        raise ValueError(f"master: mastering must be a Mastering, not {mastering!r}")
-    a, r = mastering.samples(sample_rate)
+def _signals_of(signals, who):
+    """(fp32 contiguous 1-D CUDA tensors, lengths, single, was_tensor) of a 1-D tensor, a (B, L) tensor or a list of 1-D tensors; every
+    ValueError comes before the device is asked for."""
     single = isinstance(signals, torch.Tensor) and signals.dim() == 1
     was_tensor = isinstance(signals, torch.Tensor) and not single
     if was_tensor and signals.dim() != 2:
-        raise ValueError("master: signals: expected a 1-D tensor, a (B, L) tensor or a list of 1-D tensors")
-    sigs = [signals] if single else list(signals)
+        raise ValueError(f"{who}: signals: expected a 1-D tensor, a (B, L) tensor or a list of 1-D tensors")
+    try:
+        sigs = [signals] if single else list(signals)
+    except TypeError:
+        raise ValueError(f"{who}: signals: expected a 1-D tensor, a (B, L) tensor or a list of 1-D tensors") from None
     if not sigs:
-        raise ValueError("master: signals: no signals")
+        raise ValueError(f"{who}: signals: no signals")
     for s in sigs:
         if not isinstance(s, torch.Tensor) or s.dim() != 1:
-            raise ValueError("master: signals: expected a 1-D tensor, a (B, L) tensor or a list of 1-D tensors")
+            raise ValueError(f"{who}: signals: expected a 1-D tensor, a (B, L) tensor or a list of 1-D tensors")
         if s.numel() < 1:
-            raise ValueError("master: signals: an empty signal")
+            raise ValueError(f"{who}: signals: an empty signal")
         if s.numel() > _MS["DS_MS_MAX_LEN"]:
-            raise ValueError(f"master: signals: a signal of {s.numel()} samples (at most 2^24 = {_MS['DS_MS_MAX_LEN']})")
+            raise ValueError(f"{who}: signals: a signal of {s.numel()} samples (at most 2^24 = {_MS['DS_MS_MAX_LEN']})")
     for s in sigs:
-        _require_cuda(s, "master")
+        _require_cuda(s, who)
     sigs = [s.detach().float().contiguous() for s in sigs]
-    lengths = [s.numel() for s in sigs]
+    return sigs, [s.numel() for s in sigs], single, was_tensor
+
+
+@torch.no_grad()
+def master(signals, mastering=Mastering(), *, sample_rate=16000, pcm16=False, return_stats=False, return_loudness=False):
+    """Gain and limiter (Mastering) for one 1-D CUDA tensor, a (B, L) tensor or a list of 1-D tensors of different lengths, each signal by
+    itself -> the same container, fp32, or int16 = rint(y * 32767) with pcm16=True; with return_stats=True (result, MasterStats).
+    One table upload, ds_master_gain and ds_master_limit, no device -> host copy.  A signal's result is the same bits alone and in a batch.
+    With a target_lufs: ds_master_gain (no target: rms, peak), ds_loudness, ds_loudness_gain, ds_master_limit; MasterStats.gain is the
+    gain applied.  return_loudness=True appends the Loudness of the INPUT to the return value (it is measured for that where the
+    Mastering has no target_lufs)."""
+    if not isinstance(mastering, Mastering):
+        raise ValueError(f"master: mastering must be a Mastering, not {mastering!r}")
+    a, r = mastering.samples(sample_rate)
+    lufs = mastering.target_lufs
+    if return_loudness:
+        _lu_rate(sample_rate, "master (return_loudness)")
+    sigs, lengths, single, was_tensor = _signals_of(signals, "master")
     n, max_len = len(sigs), max(lengths)
     tab = _flat_table(lengths)
     x = sigs[0] if n == 1 else torch.cat(sigs)
@@ -646,6 +676,12 @@ def master(signals, mastering=Mastering(), *, sample_rate=16000, pcm16=False, re
     st = L.current_stream()
     L.call("ds_master_gain", x.data_ptr(), dtab.data_ptr(), n, max_len, x.numel(), target, float(np.float32(mastering.max_gain)), ws.data_ptr(),
            stats.data_ptr(), limited.data_ptr(), st)
+    loud = None
+    if lufs is not None or return_loudness:
+        lu, cnt, _ = _lu_measure(x, dtab, lengths, int(sample_rate))
+        loud = _lu_result(lu, cnt)
+        if lufs is not None:
+            L.call("ds_loudness_gain", lu.data_ptr(), n, _lu_energy(lufs), float(np.float32(mastering.max_gain)), stats.data_ptr(), st)
     L.call("ds_master_limit", x.data_ptr(), dtab.data_ptr(), n, max_len, x.numel(), float(np.float32(mastering.ceiling)), a, r, stats.data_ptr(),
            limited.data_ptr(), out.data_ptr(), L.ptr(pcm), st)
     res = pcm if pcm16 else out
@@ -653,16 +689,21 @@ def master(signals, mastering=Mastering(), *, sample_rate=16000, pcm16=False, re
         res = res.view(n, lengths[0])
     elif not single:
         res = [res[o:o + m] for o, m in zip(tab[:, _PV["DS_PV_XOFF"]].tolist(), lengths)]
-    if not return_stats:
-        return res
-    return res, MasterStats(*(stats[:, _MS[k]] for k in ("DS_MS_GAIN", "DS_MS_RMS", "DS_MS_PEAK", "DS_MS_MIN_GAIN")), limited)
+    ret = (res,)
+    if return_stats:
+        ret += (MasterStats(*(stats[:, _MS[k]] for k in ("DS_MS_GAIN", "DS_MS_RMS", "DS_MS_PEAK", "DS_MS_MIN_GAIN")), limited),)
+    if return_loudness:
+        ret += (loud,)
+    return ret[0] if len(ret) == 1 else ret
 
 
 def _mastered(track, mastering, sample_rate, pcm16=False):
-    """(track or its mastered form, MasterStats or None); an empty track has nothing to master."""
+    """(track or its mastered form, MasterStats or None, Loudness or None); an empty track has nothing to master."""
     if mastering is None or track.numel() == 0:
-        return (track.to(torch.int16) if pcm16 else track), None
-    return master(track, mastering, sample_rate=sample_rate, pcm16=pcm16, return_stats=True)
+        return (track.to(torch.int16) if pcm16 else track), None, None
+    if mastering.target_lufs is None:
+        return (*master(track, mastering, sample_rate=sample_rate, pcm16=pcm16, return_stats=True), None)
+    return master(track, mastering, sample_rate=sample_rate, pcm16=pcm16, return_stats=True, return_loudness=True)
 
 
 # ---------------------------------------------------------------------------------------------------- tuned mode
@@ -862,6 +903,8 @@ class Track:
 
     last_master = None         # MasterStats of the last mastered render
 
+    last_loudness = None       # Loudness of the last render's mix, where that render was mastered to a LUFS target (else None)
+
     @torch.no_grad()
     def render(self, note_fn, sample_rate=16000, return_tensor=True, notes=None, *, tune=None, perform=None, master=None, formant=None):
         """synthesize_track on the device.  note_fn(velocity, duration_sec) -> numpy array or tensor on either device, called once per distinct
@@ -880,7 +923,8 @@ class Track:
         Normalisation, the chains and tune= are the same and compose with it.
 
         master (a Mastering) adds one stage behind the mix: master(track, mastering, sample_rate=sample_rate), bit for bit; last_master
-        holds its MasterStats.  None (the default) is the render without it.
+        holds its MasterStats, last_loudness the mix's Loudness where the Mastering has a target_lufs (else None).  None (the default) is
+        the render without it.
 
         formant (a Formant) changes the chains alone: every link keeps the note's spectral envelope in place (pitch_shift_chain(formant=)).
         It composes with tune, perform and master; None (the default) is the render without it."""
@@ -902,8 +946,9 @@ class Track:
                 track = self._mix_reference(sched, n, normed, shape, formant)
             else:
                 track = self._mix_tuned(sched, n, normed, _source_pitches(tune, keys, normed, sample_rate), shape, formant)
+        self.last_loudness = None
         if master is not None:
-            track, self.last_master = _mastered(track, master, sample_rate)
+            track, self.last_master, self.last_loudness = _mastered(track, master, sample_rate)
         return track if return_tensor else track.cpu().numpy()
 
     def _collect(self, note_fn, sample_rate, notes, perform=None):
@@ -977,6 +1022,7 @@ class DiffSynth:
         self.master = _check_master(master)          # master()'s stage behind the sum of the tracks of arrange / get_music
         self.formant = _check_formant(formant)       # Track.render's formant=, for every track of arrange / get_music
         self.last_master = None                      # MasterStats of the last mastered arrange (None: it was not mastered)
+        self.last_loudness = None                    # Loudness of the last arrange's sum (None: it was not mastered to a LUFS target)
         self.last_batcher = None
         self.last_pitches = None                     # {(instrument name, duration_sec): MIDI pitch or nan} of the last tuned arrange
 
@@ -1070,7 +1116,7 @@ class DiffSynth:
         full = torch.zeros(max(a.numel() for a in audios), dtype=torch.float32, device=audios[0].device)
         for a in audios:                           # the reference's order: full_audio += pad(audio), track by track
             full[:a.numel()] += a
-        full, self.last_master = _mastered(full, master, sample_rate, pcm16)
+        full, self.last_master, self.last_loudness = _mastered(full, master, sample_rate, pcm16)
         return full
 
     def _arrange_detected(self, tracks, instrument_names, per_track, sample_rate, perform=None, formant=None):

@@ -1190,6 +1190,74 @@ int ds_master_gain(const float* x, const int32_t* tab, int n_signals, int max_le
 int ds_master_limit(const float* x, const int32_t* tab, int n_signals, int max_len, long long total_samples, float ceiling, int lookahead,
                     int hold, float* stats, int32_t* limited, float* out, int16_t* pcm, void* stream);
 
+/* ---------------------------------------------------------------- loudness: K-weighted gated loudness, BS.1770 (csrc/loudness.hip)
+ * One mono signal x[0..N) in fp32 at an integer rate fs >= 8000, for the ragged batch of the mastering stage (row s of tab: XOFF, LEN,
+ * 1 <= LEN <= DS_MS_MAX_LEN; and DS_LU_TAB_BOFF where the block energies are wanted).  Everything below is in float64.
+ *   K-weighting  two biquads, re-derived for fs from the analogue prototypes in the form libebur128 and pyloudnorm use, computed by the
+ *                host once:
+ *                stage 1 (shelf)      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196,
+ *                                     K = tan(pi f0 / fs), Vh = 10^(G / 20), Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2,
+ *                                     b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0],
+ *                                     a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0];
+ *                stage 2 (high-pass)  f0 = 38.13547087602444, Q = 0.5003270373238773, K = tan(pi f0 / fs), d = 1 + K / Q + K^2,
+ *                                     b = [1, -2, 1], a = [1, 2 (K^2 - 1) / d, (1 - K / Q + K^2) / d].
+ *                At 48 kHz these are the standard's table to its 14 published digits.  y = x through stage 1, then stage 2, from zero
+ *                state (transposed direct form II, as scipy.signal.lfilter).
+ *   blocks       h = (fs + 5) / 10 samples (integer division: libebur128's 100 ms);  q_i = sum of y[n]^2 over [i h, (i + 1) h);
+ *                block j covers 4 h samples from j h:  z_j = ((q_j + q_j+1) + (q_j+2 + q_j+3)) / (4 h);  nb = max(0, N / h - 3) blocks,
+ *                only those that lie wholly inside the signal;  l_j = -0.691 + 10 log10 z_j.
+ *   gates        both decided in the energy domain, no logarithm takes part in a decision:  z_abs = 10^((-70 + 0.691) / 10) (the host's);
+ *                J1 = {j : z_j > z_abs};  z_rel = 0.1 mean(z_j, j in J1) (0 where J1 is empty);  J2 = {j in J1 : z_j > z_rel};
+ *                Z = mean(z_j, j in J2);  integrated loudness L = -0.691 + 10 log10 Z;  the relative threshold in LUFS is
+ *                -0.691 + 10 log10 z_rel;  the momentary maximum is max l_j over ALL blocks.  J2 empty (no block, or none above -70):
+ *                Z = 0 and L = -inf;  every logarithm of 0 is -inf.
+ *   sums         float64 in a fixed order that depends on N and fs alone; no float atomics: a signal has the same bits alone and inside
+ *                any batch.
+ *   gain         zt = 10^((target_lufs + 0.691) / 10) (the host's, float64);  gL = fp32(min(sqrt(zt / Z), max_gain)), IEEE division and
+ *                square root, so gL is exact given Z;  Z = 0: gL = 1.0 exactly (nothing measurable, nothing changed).
+ *
+ * ds_loudness.  coef: DS_LU_NCOEF float64 values in HOST memory (they travel as a kernel argument):  stage 1's b at DS_LU_C_B1 (3) and
+ * a[1], a[2] at DS_LU_C_A1, stage 2's at DS_LU_C_B2 / DS_LU_C_A2, then 4 x 4 row-major powers of the one-sample zero-input transition M of
+ * the state (s1[0], s1[1], s2[0], s2[1]) of the transposed form,
+ *     M = [[-a1[1], 1, 0, 0], [-a1[2], 0, 0, 0], [b2[1] - a2[1] b2[0], 0, -a2[1], 1], [b2[2] - a2[2] b2[0], 0, -a2[2], 0]]:
+ * with Lc = ceil(h / DS_LU_THREADS) | 1 (odd), nc = ceil(h / Lc) and Lt = h - (nc - 1) Lc:  M^Lt at DS_LU_C_PTAIL, M^h at DS_LU_C_PHOP and
+ * M^(Lc 2^k), k = 0 .. DS_LU_SCAN_STEPS - 1, at DS_LU_C_PSCAN + 16 k.  The recursion is linear, so it is cut exactly: a hop is a block, a
+ * thread runs one chunk of Lc samples (the last one Lt) from zero state, a scan with the M^(Lc 2^k) carries the end states along the hop, one
+ * wave per signal carries the hops' end states along the signal with M^h, and every chunk runs again from its true start state and adds its
+ * squares.  This is the algebraic carry, not a warm-up: nothing is truncated.  Four launches (hops, carry, hops, gates); a batch in which no
+ * signal has four hops takes the last one only.
+ * ws: ds_loudness_ws_bytes(n_signals, max_len, h) bytes (0: bad arguments), 8-byte aligned, need not be initialised.
+ * lu [n_signals][DS_LU_NS] float64: ENERGY = Z, INTEGRATED, MOMENTARY_MAX, THRESHOLD.  cnt [n_signals][3] int32: nb, |J1|, |J2|.
+ * blocks (may be NULL): float64 [total_blocks], z_j of signal s at blocks[tab[s][DS_LU_TAB_BOFF] + j], j < nb.
+ * DS_LU_MIN_HOP <= h <= DS_LU_MAX_HOP, z_abs >= 0 and finite, every coef finite, else DS_EINVAL.  Every lu / cnt entry of a fitting row and
+ * exactly nb entries of its blocks are written, and nothing outside them; a row that does not fit total_samples (or, with blocks, whose
+ * blocks do not fit total_blocks) or has LEN outside [1, max_len] reads and writes nothing.
+ *
+ * ds_loudness_gain: stats[s][DS_MS_GAIN] = gL from lu[s][DS_LU_ENERGY], behind a ds_master_gain call made with no RMS target; it touches
+ * nothing else of stats.  zt and max_gain positive and finite, else DS_EINVAL. */
+#define DS_LU_ENERGY 0
+#define DS_LU_INTEGRATED 1
+#define DS_LU_MOMENTARY_MAX 2
+#define DS_LU_THRESHOLD 3
+#define DS_LU_NS 4
+#define DS_LU_TAB_BOFF 2
+#define DS_LU_THREADS 256
+#define DS_LU_MIN_HOP 800
+#define DS_LU_MAX_HOP 19200
+#define DS_LU_C_B1 0
+#define DS_LU_C_A1 3
+#define DS_LU_C_B2 5
+#define DS_LU_C_A2 8
+#define DS_LU_C_PTAIL 16
+#define DS_LU_C_PHOP 32
+#define DS_LU_C_PSCAN 48
+#define DS_LU_SCAN_STEPS 8
+#define DS_LU_NCOEF 176
+size_t ds_loudness_ws_bytes(int n_signals, int max_len, int h);
+int ds_loudness(const float* x, const int32_t* tab, int n_signals, int max_len, long long total_samples, const double* coef, int h, double z_abs,
+                void* ws, double* lu, int32_t* cnt, double* blocks, long long total_blocks, void* stream);
+int ds_loudness_gain(const double* lu, int n_signals, double zt, float max_gain, float* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

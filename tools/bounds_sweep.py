@@ -156,6 +156,24 @@ def sweep_master(fail):
     report("master (2, L) batch, 2^20 + 4099 samples", fail)
 
 
+def sweep_loudness(fail):
+    """The loudness meter (csrc/loudness.hip): ragged batches on both sides of four hops at three rates (three chunkings of a hop), with and
+    without the block energies, a long carry chain, and master() to a LUFS target."""
+    import importlib
+    from diffusynth_amd import arranger as A
+    LM = importlib.import_module("diffusynth_amd.loudness")
+    for fs in (16000, 11025, 48000):
+        h = LM.hop(fs)
+        sigs = [synth_input("bs_lu%d_%d" % (fs, n), (n,)).cuda() for n in (1, 4 * h - 1, 4 * h, 5 * h + 1, 9 * h + 77)]
+        LM.loudness(sigs, fs)
+        LM.loudness(sigs[::-1], fs, return_blocks=True)
+    report("loudness ragged batch of 5 at 16, 11.025 and 48 kHz, with and without the block energies", fail)
+    long = synth_input("bs_lu_long", (2 ** 20 + 3001,)).cuda()
+    LM.loudness(torch.stack([long, -long]), 16000, return_blocks=True)
+    A.master([long, long[:7000], long[:100]], A.Mastering(target_rms=None, target_lufs=-16.0), return_stats=True, return_loudness=True)
+    report("loudness (2, L) batch of 2^20 + 3001 samples, master() to a LUFS target", fail)
+
+
 def sweep_linattn_paths(fail):
     """The plain linear-attention files at eight exact cases of tests/linattn_ref.py, through the C ABI (this build compiles attn_out_kernel<float>
     without its row-transposition path, and nothing else here calls ds_vq_attn_* directly): empty segments (N = 10 in 7), ragged N, 7 and 8 heads,
@@ -516,6 +534,10 @@ def main():
         sweep_master(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
         sys.exit(1 if fail else 0)
+    if "--only-loudness" in sys.argv:
+        sweep_loudness(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
     if "--only-perform" in sys.argv:
         sweep_perform(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
@@ -610,6 +632,7 @@ def main():
     sweep_pitch(fail)
     sweep_ingest(fail)
     sweep_master(fail)
+    sweep_loudness(fail)
     # 6) GroupNorm from raw partials in every kernel that reduces them, the depthwise families, the chains without ds_gn_finalize
     sweep_gn_partials(fail)
     # 7) the plain linear-attention files on the paths of tests/test_hip_linattn_paths.py
