@@ -30,6 +30,8 @@
 //                samples.  With fp32 notes this is bit for bit numpy's float32 += float64.
 // ds_mix_notes_shaped  the same walk and store with every sample weighted first: w = gain x ADSR envelope in closed form from the row's
 //                segment lengths, rounded to fp32 once, then fl(w x) and the fp32 sum in event order (velocity and gate of the performed mode).
+//                The two forms differ on an event that overhangs the track (start + length > track_len): ds_mix_notes mixes it clipped at the
+//                track's end, ds_mix_notes_shaped skips it.  arranger.mix_notes refuses such an event for both, so neither is reached.
 #include "common.hpp"
 
 namespace {
@@ -485,6 +487,7 @@ __global__ __launch_bounds__(256) void mix_notes_kernel(const float* notes, long
 inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 constexpr long long MAX_ELEMS = (1ll << 31) - 1;      // the table's offsets are int32
+constexpr long long STFT_MAX_SAMPLES = (1ll << 30) - N_FFT / 2;       // ld_zero: byte counts and byte offsets of 32 bits
 
 }  // namespace
 
@@ -493,6 +496,10 @@ extern "C" int ds_pv_stft(const float* x, const int32_t* tab, int n_signals, int
     DS_REQUIRE(x && tab && spec && n_signals > 0 && max_frames > 0 && total_samples > 0 && total_frames > 0,
                "pv_stft: bad args (n_signals=%d max_frames=%d total_samples=%lld total_frames=%lld)", n_signals, max_frames, total_samples, total_frames);
     DS_REQUIRE(n_signals <= 65535 && total_samples <= MAX_ELEMS && total_frames * NBINS <= MAX_ELEMS, "pv_stft: at most 65535 signals and 2^31 - 1 elements per buffer");
+    // ld_zero's range check is a buffer descriptor of len * 4 bytes and a byte offset of i * 4, both 32-bit words: a frame reaches
+    // i = len + 2047, and from (len + 2047) * 4 = 2^32 on the offset wraps back into the signal instead of reading the zero padding
+    DS_REQUIRE(total_samples <= STFT_MAX_SAMPLES, "pv_stft: at most 2^30 - 2048 samples (total_samples=%lld): the zero padding is the range check of a 32-bit byte offset",
+               total_samples);
     if (!al4(x) || !al4(tab) || !al8(spec)) DS_FAIL(DS_EALIGN, "pv_stft: x / tab must be 4-byte, spec 8-byte aligned");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #if DS_BOUNDS
