@@ -12,5 +12,6 @@ from .clap_text import ClapTextTower  # noqa: E402,F401
 from .pitch import PitchEstimate, estimate_pitch, yin  # noqa: E402,F401
 from .arranger import Formant, Mastering, MasterStats, Performance, adsr_envelope, master, tempo_map_of  # noqa: E402,F401
 from .loudness import Loudness, kweighting, loudness  # noqa: E402,F401
+from .true_peak import TruePeak, true_peak, true_peak_coefficients  # noqa: E402,F401
 from .ingest import adjust_audio_length, resample_poly, uploads_to_stft  # noqa: E402,F401
 from .inpaint_mask import latent_mask_from_layers, zoomed_size  # noqa: E402,F401

@@ -65,6 +65,7 @@ PITCH_MAX_FRAMES = _parse_defines(_HEADER_TEXT, "DS_PITCH_")["DS_PITCH_MAX_FRAME
 RP = _parse_defines(_HEADER_TEXT, "DS_RP_")     # ds_resample_poly signal table (field indices and row width), DS_RP_MAX_TAPS / _SPAN / _BLK
 IM = _parse_defines(_HEADER_TEXT, "DS_IM_")     # inpaint mask table (field indices and row width), DS_IM_RUN_IN
 MS = _parse_defines(_HEADER_TEXT, "DS_MS_")     # mastering: stats row (field indices and width), DS_MS_TILE, the caps, the reduction's chunking
+TP = _parse_defines(_HEADER_TEXT, "DS_TP_")     # true peak: the tile, the interpolator's phases and taps
 LU = _parse_defines(_HEADER_TEXT, "DS_LU_")     # loudness: results row, the table's block-offset field, hop limits, the coefficient layout
 TAIL = _parse_defines(_HEADER_TEXT, "DS_TAIL_")     # ds_text_tail: op codes
 ConvParams = _STRUCTS["ds_conv_params"]
@@ -217,6 +218,9 @@ _PROTOS = {  # name: (restype, argtypes); restype int => checked
     "ds_loudness_ws_bytes": (_SZ, [_I, _I, _I]),
     "ds_loudness": (C.c_int, [_P, _P, _I, _I, C.c_longlong, _P, _I, _D, _P, _P, _P, _P, C.c_longlong, _P]),
     "ds_loudness_gain": (C.c_int, [_P, _I, _D, _F, _P, _P]),
+    "ds_true_peak_ws_bytes": (_SZ, [_I, _I]),
+    "ds_true_peak": (C.c_int, [_P, _P, _I, _I, C.c_longlong, _P, _P, _P, _P, _P]),
+    "ds_master_limit_tp": (C.c_int, [_P, _P, _P, _I, _I, C.c_longlong, _F, _I, _I, _P, _P, _P, _P, _P]),
     "ds_bounds_report": (C.c_int, [C.c_char_p, _I, _I]),
 }
 _UNCHECKED = {"ds_conv3x3_f32_n4_weight_floats", "ds_bounds_report", "ds_abi_version", "ds_conv_stats_parts", "ds_conv1x1_x3_stats_parts", "ds_conv_tile_bn", "ds_dwconv_stats_parts", "ds_attn_fused_stats_parts", "ds_attn_fused_generations", "ds_attn_fused_segments", "ds_attn_fused_segments_gen", "ds_attn_x3_stats_parts", "ds_attn_x3_segments", "ds_vq_attn_segments", "ds_conv3x3_c80_stats_slots", "ds_convt4x4_c80_stats_slots"}

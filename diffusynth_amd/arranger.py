@@ -15,7 +15,8 @@ the real note-off, both applied inside the mix (ds_mix_notes_shaped).
 Opt-in (`master=Mastering(...)`, off by default): an RMS gain and a peak-hold look-ahead limiter behind the mix (ds_master_gain,
 ds_master_limit; include/diffusynth_hip.h has the arithmetic), once per render, in arrange / get_music once on the sum of the tracks.
 With Mastering(target_lufs=...) the gain is the one that takes the mix's K-weighted gated loudness (BS.1770) to the target instead
-(ds_loudness, ds_loudness_gain between the two; diffusynth_amd/loudness.py).
+(ds_loudness, ds_loudness_gain between the two; diffusynth_amd/loudness.py).  With Mastering(true_peak=True) the ceiling is a true-peak
+ceiling: the limiter's detector is the 4x interpolated envelope of the mix (ds_true_peak, ds_master_limit_tp; diffusynth_amd/true_peak.py).
 Opt-in (`formant=Formant(...)`, off by default): every link of a chain keeps the note's spectral envelope where the source had it
 (ds_pv_formant between ds_pv_vocode and ds_pv_istft: cepstral envelope, warped ratio, one more launch per level), so a note shifted two
 octaves up is still the same instrument.  Beyond the reference; defined in include/diffusynth_hip.h.
@@ -37,6 +38,7 @@ import torch
 from . import _lib as L
 from .loudness import check_sample_rate as _lu_rate, energy_of as _lu_energy, measure as _lu_measure, result as _lu_result     # (the package's
 # attribute `loudness` is the function of that name, not the module)
+from .true_peak import TruePeak, measure as _tp_measure                                                                         # (likewise `true_peak`)
 
 N_FFT, HOP = 4096, 1024
 _NO_GPU = "diffusynth_amd arranger runs on MI355X only (%s); no CPU fallback"
@@ -566,16 +568,28 @@ class Mastering:
     measurements: the reference's tools.rms_normalize default, 20 dB, -1 dBFS, 5 ms and 50 ms.
 
     target_lufs (in [-70, 0]; target_rms must then be None) makes the gain the one that takes the signal's K-weighted gated loudness
-    (BS.1770: loudness()) to that many LUFS, at most max_gain; a signal with nothing to measure keeps a gain of 1."""
+    (BS.1770: loudness()) to that many LUFS, at most max_gain; a signal with nothing to measure keeps a gain of 1.
+
+    true_peak=True (only True or False) makes the ceiling a true-peak ceiling (dBTP): the limiter's detector becomes the envelope of the
+    4x interpolated input (true_peak()) instead of the samples' magnitudes.  The sample peak is still held to the ceiling
+    exactly.  The true peak of the result is not bounded exactly, because a gain that varies in time does not commute with the
+    interpolator: it rests on the look-ahead, whose smoothing keeps the gain slow against the interpolator's 12 samples.  At the
+    defaults the measured overshoot on the test signals of DESIGN §7r is below 0.01 dB; with lookahead=0 the gain steps from sample to
+    sample and the bound does not hold (1.6 dB over on hard-clipped noise)."""
     target_rms: float | None = 0.1
     max_gain: float = 10.0
     ceiling: float = 10 ** (-1 / 20)
     lookahead: float = 0.005
     hold: float = 0.05
     target_lufs: float | None = None
+    true_peak: bool = False
 
     def __post_init__(self):
+        if not isinstance(self.true_peak, (bool, np.bool_)):
+            raise ValueError(f"Mastering: true_peak must be True or False, not {self.true_peak!r}")
         for f in dataclasses.fields(self):
+            if f.name == "true_peak":
+                continue
             v = getattr(self, f.name)
             if not (_finite_number(v) or (f.name in ("target_rms", "target_lufs") and v is None)):
                 raise ValueError(f"Mastering: {f.name} must be a finite number, not {v!r}")
@@ -648,15 +662,21 @@ def _signals_of(signals, who):
 
 
 @torch.no_grad()
-def master(signals, mastering=Mastering(), *, sample_rate=16000, pcm16=False, return_stats=False, return_loudness=False):
+def master(signals, mastering=Mastering(), *, sample_rate=16000, pcm16=False, return_stats=False, return_loudness=False, return_true_peak=False):
     """Gain and limiter (Mastering) for one 1-D CUDA tensor, a (B, L) tensor or a list of 1-D tensors of different lengths, each signal by
     itself -> the same container, fp32, or int16 = rint(y * 32767) with pcm16=True; with return_stats=True (result, MasterStats).
     One table upload, ds_master_gain and ds_master_limit, no device -> host copy.  A signal's result is the same bits alone and in a batch.
     With a target_lufs: ds_master_gain (no target: rms, peak), ds_loudness, ds_loudness_gain, ds_master_limit; MasterStats.gain is the
     gain applied.  return_loudness=True appends the Loudness of the INPUT to the return value (it is measured for that where the
-    Mastering has no target_lufs)."""
+    Mastering has no target_lufs).
+    With true_peak=True: ds_master_gain, the LUFS pair where a target is set, ds_true_peak with the envelope of the input, then
+    ds_master_limit_tp.  return_true_peak=True appends TruePeak(input, output) last, both fp32 device tensors: output from one more
+    ds_true_peak on the result, input from one on x where the Mastering did not already make it.  With pcm16=True, output is the true
+    peak of the fp32 result BEFORE it is quantised to int16 (the true peak of the int16 samples is not measured)."""
     if not isinstance(mastering, Mastering):
         raise ValueError(f"master: mastering must be a Mastering, not {mastering!r}")
+    if not isinstance(return_true_peak, (bool, np.bool_)):
+        raise ValueError(f"master: return_true_peak must be True or False, not {return_true_peak!r}")
     a, r = mastering.samples(sample_rate)
     lufs = mastering.target_lufs
     if return_loudness:
@@ -682,8 +702,17 @@ def master(signals, mastering=Mastering(), *, sample_rate=16000, pcm16=False, re
         loud = _lu_result(lu, cnt)
         if lufs is not None:
             L.call("ds_loudness_gain", lu.data_ptr(), n, _lu_energy(lufs), float(np.float32(mastering.max_gain)), stats.data_ptr(), st)
-    L.call("ds_master_limit", x.data_ptr(), dtab.data_ptr(), n, max_len, x.numel(), float(np.float32(mastering.ceiling)), a, r, stats.data_ptr(),
-           limited.data_ptr(), out.data_ptr(), L.ptr(pcm), st)
+    tp_in = None
+    if mastering.true_peak:
+        tp_in, env = _tp_measure(x, dtab, lengths, True)
+        L.call("ds_master_limit_tp", x.data_ptr(), env.data_ptr(), dtab.data_ptr(), n, max_len, x.numel(), float(np.float32(mastering.ceiling)), a, r,
+               stats.data_ptr(), limited.data_ptr(), out.data_ptr(), L.ptr(pcm), st)
+    else:
+        L.call("ds_master_limit", x.data_ptr(), dtab.data_ptr(), n, max_len, x.numel(), float(np.float32(mastering.ceiling)), a, r, stats.data_ptr(),
+               limited.data_ptr(), out.data_ptr(), L.ptr(pcm), st)
+    peaks = None
+    if return_true_peak:
+        peaks = TruePeak(_tp_measure(x, dtab, lengths)[0] if tp_in is None else tp_in, _tp_measure(out, dtab, lengths)[0])
     res = pcm if pcm16 else out
     if was_tensor:
         res = res.view(n, lengths[0])
@@ -694,16 +723,18 @@ def master(signals, mastering=Mastering(), *, sample_rate=16000, pcm16=False, re
         ret += (MasterStats(*(stats[:, _MS[k]] for k in ("DS_MS_GAIN", "DS_MS_RMS", "DS_MS_PEAK", "DS_MS_MIN_GAIN")), limited),)
     if return_loudness:
         ret += (loud,)
+    if return_true_peak:
+        ret += (peaks,)
     return ret[0] if len(ret) == 1 else ret
 
 
 def _mastered(track, mastering, sample_rate, pcm16=False):
-    """(track or its mastered form, MasterStats or None, Loudness or None); an empty track has nothing to master."""
+    """(track or its mastered form, MasterStats or None, Loudness or None, TruePeak or None); an empty track has nothing to master."""
     if mastering is None or track.numel() == 0:
-        return (track.to(torch.int16) if pcm16 else track), None, None
-    if mastering.target_lufs is None:
-        return (*master(track, mastering, sample_rate=sample_rate, pcm16=pcm16, return_stats=True), None)
-    return master(track, mastering, sample_rate=sample_rate, pcm16=pcm16, return_stats=True, return_loudness=True)
+        return (track.to(torch.int16) if pcm16 else track), None, None, None
+    lufs, tp = mastering.target_lufs is not None, mastering.true_peak
+    ret = master(track, mastering, sample_rate=sample_rate, pcm16=pcm16, return_stats=True, return_loudness=lufs, return_true_peak=tp)
+    return ret[0], ret[1], (ret[2] if lufs else None), (ret[-1] if tp else None)
 
 
 # ---------------------------------------------------------------------------------------------------- tuned mode
@@ -904,6 +935,7 @@ class Track:
     last_master = None         # MasterStats of the last mastered render
 
     last_loudness = None       # Loudness of the last render's mix, where that render was mastered to a LUFS target (else None)
+    last_true_peak = None      # TruePeak of the last render's mix, where that render's Mastering has true_peak=True (else None)
 
     @torch.no_grad()
     def render(self, note_fn, sample_rate=16000, return_tensor=True, notes=None, *, tune=None, perform=None, master=None, formant=None):
@@ -923,8 +955,8 @@ class Track:
         Normalisation, the chains and tune= are the same and compose with it.
 
         master (a Mastering) adds one stage behind the mix: master(track, mastering, sample_rate=sample_rate), bit for bit; last_master
-        holds its MasterStats, last_loudness the mix's Loudness where the Mastering has a target_lufs (else None).  None (the default) is
-        the render without it.
+        holds its MasterStats, last_loudness the mix's Loudness where the Mastering has a target_lufs (else None), last_true_peak its
+        TruePeak where the Mastering has true_peak=True (else None).  None (the default) is the render without it.
 
         formant (a Formant) changes the chains alone: every link keeps the note's spectral envelope in place (pitch_shift_chain(formant=)).
         It composes with tune, perform and master; None (the default) is the render without it."""
@@ -947,8 +979,9 @@ class Track:
             else:
                 track = self._mix_tuned(sched, n, normed, _source_pitches(tune, keys, normed, sample_rate), shape, formant)
         self.last_loudness = None
+        self.last_true_peak = None
         if master is not None:
-            track, self.last_master, self.last_loudness = _mastered(track, master, sample_rate)
+            track, self.last_master, self.last_loudness, self.last_true_peak = _mastered(track, master, sample_rate)
         return track if return_tensor else track.cpu().numpy()
 
     def _collect(self, note_fn, sample_rate, notes, perform=None):
@@ -1023,6 +1056,7 @@ class DiffSynth:
         self.formant = _check_formant(formant)       # Track.render's formant=, for every track of arrange / get_music
         self.last_master = None                      # MasterStats of the last mastered arrange (None: it was not mastered)
         self.last_loudness = None                    # Loudness of the last arrange's sum (None: it was not mastered to a LUFS target)
+        self.last_true_peak = None                   # TruePeak of the last arrange's sum (None: its Mastering had no true_peak=True)
         self.last_batcher = None
         self.last_pitches = None                     # {(instrument name, duration_sec): MIDI pitch or nan} of the last tuned arrange
 
@@ -1096,7 +1130,7 @@ class DiffSynth:
         the constructor's) as in Track.render, for tracks built with pairing="midi"; it composes with every form of tune.
         master (default: the constructor's; None: off) runs master()'s stage ONCE, on the sum of the tracks, which is then
         master(plain sum, mastering, sample_rate=sample_rate) bit for bit; pcm16=True returns its int16 form (it needs a master: the raw sum
-        has no bound); last_master holds the MasterStats, or None.  formant (default: the constructor's; None: off) as in Track.render, for
+        has no bound); last_master holds the MasterStats, or None (last_loudness, last_true_peak as in Track.render).  formant (default: the constructor's; None: off) as in Track.render, for
         the chains of every track."""
         formant = self.formant if formant is _UNSET else _check_formant(formant)
         tune = self.tune if tune is _UNSET else _check_tune(tune)
@@ -1116,7 +1150,7 @@ class DiffSynth:
         full = torch.zeros(max(a.numel() for a in audios), dtype=torch.float32, device=audios[0].device)
         for a in audios:                           # the reference's order: full_audio += pad(audio), track by track
             full[:a.numel()] += a
-        full, self.last_master, self.last_loudness = _mastered(full, master, sample_rate, pcm16)
+        full, self.last_master, self.last_loudness, self.last_true_peak = _mastered(full, master, sample_rate, pcm16)
         return full
 
     def _arrange_detected(self, tracks, instrument_names, per_track, sample_rate, perform=None, formant=None):

@@ -161,7 +161,7 @@ enum { DS_K_CONV_IGEMM = 1, DS_K_CONV_HALO, DS_K_SPLITK_REDUCE, DS_K_DWCONV_MFMA
        DS_K_ATTN_OUT, DS_K_GN_APPLY, DS_K_LINATTN, DS_K_CONV7X7_C4, DS_K_CONVT4X4_C80, DS_K_CONV3X3_C80, DS_K_CONV3X3_F32_N4, DS_K_VQ_ATTN_CTX, DS_K_VQ_ATTN_APPLY,
        DS_K_STFT_IMAGES, DS_K_LATENT_IMAGE, DS_K_PV_STFT, DS_K_PV_VOCODE, DS_K_PV_ISTFT, DS_K_RESAMPLE_SINC, DS_K_PEAK_NORMALIZE, DS_K_MIX_NOTES, DS_K_YIN_FRAMES, DS_K_PITCH_MEDIAN,
        DS_K_RESAMPLE_POLY, DS_K_MIX_NOTES_SHAPED, DS_K_MASK_LAYERS, DS_K_MASK_PREFILTER, DS_K_MASK_ZOOM, DS_K_MASTER_GAIN, DS_K_MASTER_LIMIT, DS_K_PV_FORMANT,
-       DS_K_LOUDNESS, DS_K_LOUDNESS_GAIN };
+       DS_K_LOUDNESS, DS_K_LOUDNESS_GAIN, DS_K_TRUE_PEAK, DS_K_MASTER_LIMIT_TP };
 
 // ---- element traits ---------------------------------------------------------------------------------
 template <typename T> struct ElemTr;

@@ -13,6 +13,8 @@
 //                  g = fp32(sum of ms[i .. i + 2 A] in float64 / (2 A + 1)), y = clamp(fl(g fl(gL x))), the stores, and the block's
 //                  (min g, #{g < 1}) through one integer atomic each per wave that limited anything.
 //                  A minimum does not depend on order and the float64 sum is exact inside the stated range: the bits are the definition's.
+// ds_master_limit_tp  the same kernel with step 2's detector read from env, the true-peak envelope of x (csrc/true_peak.hip): one more
+//                  template argument, the same LDS and grid.
 #include "common.hpp"
 
 #pragma clang fp contract(off)
@@ -119,8 +121,10 @@ __global__ __launch_bounds__(MS_T) void master_finish_kernel(const int32_t* tab,
 }
 
 // ------------------------------------------------------------------------------------------------ limiter
-__global__ __launch_bounds__(MS_T) void master_limit_kernel(const float* x, const int32_t* tab, long long total_samples, float c, int A, int R, float* stats,
-                                                            int32_t* limited, float* out, int16_t* pcm) {
+// ENV: the detector of step 2 is fl(gL env[n]), the true-peak envelope of x (ds_true_peak), instead of |fl(gL x[n])|
+template <bool ENV>
+__global__ __launch_bounds__(MS_T) void master_limit_kernel(const float* x, const float* env, const int32_t* tab, long long total_samples, float c, int A, int R,
+                                                            float* stats, int32_t* limited, float* out, int16_t* pcm) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int s = blockIdx.y, tid = threadIdx.x;
     const MsRow row = ms_row(tab, s);
@@ -143,7 +147,7 @@ __global__ __launch_bounds__(MS_T) void master_limit_kernel(const float* x, cons
         const int i = tid + q * MS_T, n = base + i;
         float r = 1.0f;
         if (i < nr && n >= 0 && n < row.len) {
-            const float au = fabsf(gl * DS_LD(float, xg + n, DS_BX_SRC0));
+            const float au = ENV ? gl * DS_LD(float, env + row.xoff + n, DS_BX_SRC1) : fabsf(gl * DS_LD(float, xg + n, DS_BX_SRC0));
             if (au > c) r = __fdiv_rn(c, au);
         }
         if (i < nr) rs[i] = r;
@@ -249,23 +253,29 @@ extern "C" int ds_master_gain(const float* x, const int32_t* tab, int n_signals,
     return DS_OK;
 }
 
-extern "C" int ds_master_limit(const float* x, const int32_t* tab, int n_signals, int max_len, long long total_samples, float ceiling, int lookahead,
-                               int hold, float* stats, int32_t* limited, float* out, int16_t* pcm, void* stream) {
-    DS_REQUIRE(x && tab && stats && limited && out && n_signals > 0 && max_len > 0 && total_samples > 0,
-               "master_limit: bad args (n_signals=%d max_len=%d total_samples=%lld)", n_signals, max_len, total_samples);
+namespace {
+
+// ds_master_limit (env == nullptr) and ds_master_limit_tp: one set of checks, one launch
+template <bool ENV>
+int master_limit_launch(const char* who, int kernel_id, const float* x, const float* env, const int32_t* tab, int n_signals, int max_len, long long total_samples,
+                        float ceiling, int lookahead, int hold, float* stats, int32_t* limited, float* out, int16_t* pcm, void* stream) {
+    DS_REQUIRE(x && (!ENV || env) && tab && stats && limited && out && n_signals > 0 && max_len > 0 && total_samples > 0,
+               "%s: bad args (n_signals=%d max_len=%d total_samples=%lld)", who, n_signals, max_len, total_samples);
     DS_REQUIRE(n_signals <= 65535 && max_len <= DS_MS_MAX_LEN && total_samples <= MAX_ELEMS,
-               "master_limit: at most 65535 signals of %d samples and 2^31 - 1 - %d samples in all", DS_MS_MAX_LEN, TILE);
+               "%s: at most 65535 signals of %d samples and 2^31 - 1 - %d samples in all", who, DS_MS_MAX_LEN, TILE);
     DS_REQUIRE(lookahead >= 0 && lookahead <= MAX_A && hold >= lookahead && hold <= MAX_R,
-               "master_limit: 0 <= lookahead <= %d and lookahead <= hold <= %d samples (lookahead=%d hold=%d)", MAX_A, MAX_R, lookahead, hold);
-    DS_REQUIRE(ceiling > 0.f && ceiling <= 1.f, "master_limit: the ceiling must be inside (0, 1] (ceiling=%g)", (double)ceiling);
-    DS_REQUIRE((const void*)out != (const void*)x, "master_limit: out may not be x (a tile reads its neighbours' inputs)");
-    if (!al(x, 4) || !al(tab, 4) || !al(stats, 4) || !al(limited, 4) || !al(out, 4) || !al(pcm, 2))
-        DS_FAIL(DS_EALIGN, "master_limit: x / tab / stats / limited / out 4-byte, pcm 2-byte aligned");
+               "%s: 0 <= lookahead <= %d and lookahead <= hold <= %d samples (lookahead=%d hold=%d)", who, MAX_A, MAX_R, lookahead, hold);
+    DS_REQUIRE(ceiling > 0.f && ceiling <= 1.f, "%s: the ceiling must be inside (0, 1] (ceiling=%g)", who, (double)ceiling);
+    DS_REQUIRE((const void*)out != (const void*)x && (!ENV || (const void*)out != (const void*)env),
+               "%s: out may not be x%s (a tile reads its neighbours' inputs)", who, ENV ? " or env" : "");
+    if (!al(x, 4) || !al(env, 4) || !al(tab, 4) || !al(stats, 4) || !al(limited, 4) || !al(out, 4) || !al(pcm, 2))
+        DS_FAIL(DS_EALIGN, "%s: x /%s tab / stats / limited / out 4-byte, pcm 2-byte aligned", who, ENV ? " env /" : "");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #if DS_BOUNDS
     {
-        DsBxHost h(DS_K_MASTER_LIMIT);
+        DsBxHost h(kernel_id);
         h.set(DS_BX_SRC0, x, total_samples * 4);
+        h.set(DS_BX_SRC1, env, total_samples * 4);
         h.set(DS_BX_AUX0, tab, (long long)n_signals * DS_PV_NI * 4);
         h.set(DS_BX_STATS, stats, (long long)n_signals * DS_MS_NS * 4);
         h.set(DS_BX_AUX3, limited, (long long)n_signals * 4);
@@ -273,13 +283,29 @@ extern "C" int ds_master_limit(const float* x, const int32_t* tab, int n_signals
         h.set(DS_BX_RES, pcm, total_samples * 2);
         h.publish(st);
     }
+#else
+    (void)kernel_id;
 #endif
-    DS_SET_MAX_LDS(master_limit_kernel, MS_MAX_LDS, "master_limit");
+    DS_SET_MAX_LDS(master_limit_kernel<ENV>, MS_MAX_LDS, who);
     const size_t lds = 4 * ((size_t)TILE + hold + 3 * lookahead) + 4 * ((size_t)TILE + 2 * lookahead);
-    hipLaunchKernelGGL(master_limit_kernel, dim3((max_len + TILE - 1) / TILE, n_signals), dim3(MS_T), lds, st, x, tab, total_samples, ceiling, lookahead, hold,
-                       stats, limited, out, pcm);
-    DS_CHECK_LAUNCH("master_limit");
+    hipLaunchKernelGGL(master_limit_kernel<ENV>, dim3((max_len + TILE - 1) / TILE, n_signals), dim3(MS_T), lds, st, x, env, tab, total_samples, ceiling, lookahead,
+                       hold, stats, limited, out, pcm);
+    DS_CHECK_LAUNCH(who);
     return DS_OK;
+}
+
+}  // namespace
+
+extern "C" int ds_master_limit(const float* x, const int32_t* tab, int n_signals, int max_len, long long total_samples, float ceiling, int lookahead,
+                               int hold, float* stats, int32_t* limited, float* out, int16_t* pcm, void* stream) {
+    return master_limit_launch<false>("master_limit", DS_K_MASTER_LIMIT, x, nullptr, tab, n_signals, max_len, total_samples, ceiling, lookahead, hold, stats, limited,
+                                      out, pcm, stream);
+}
+
+extern "C" int ds_master_limit_tp(const float* x, const float* env, const int32_t* tab, int n_signals, int max_len, long long total_samples, float ceiling,
+                                  int lookahead, int hold, float* stats, int32_t* limited, float* out, int16_t* pcm, void* stream) {
+    return master_limit_launch<true>("master_limit_tp", DS_K_MASTER_LIMIT_TP, x, env, tab, n_signals, max_len, total_samples, ceiling, lookahead, hold, stats,
+                                     limited, out, pcm, stream);
 }
 
 #if DS_BOUNDS

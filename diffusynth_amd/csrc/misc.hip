@@ -69,6 +69,7 @@ extern "C" int ds_bounds_fetch_resample_poly(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_inpaint_mask(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_master(ds_bounds_rec*, int);
 extern "C" int ds_bounds_fetch_loudness(ds_bounds_rec*, int);
+extern "C" int ds_bounds_fetch_true_peak(ds_bounds_rec*, int);
 #endif
 extern "C" int ds_bounds_report(char* buf, int n, int reset) {
 #if DS_BOUNDS
@@ -76,12 +77,12 @@ extern "C" int ds_bounds_report(char* buf, int n, int reset) {
                                    "attn_fused_ctx", "attn_fused_out", "gn_apply", "linattn", "conv7x7_c4", "convt4x4_c80", "conv3x3_c80", "conv3x3_f32_n4", "vq_attn_ctx", "vq_attn_apply",
                                    "stft_images", "latent_image", "pv_stft", "pv_vocode", "pv_istft", "resample_sinc", "peak_normalize", "mix_notes", "yin_frames", "pitch_median",
                                    "resample_poly", "mix_notes_shaped", "mask_layers", "mask_prefilter", "mask_zoom", "master_gain", "master_limit", "pv_formant",
-                                   "loudness", "loudness_gain"};
+                                   "loudness", "loudness_gain", "true_peak", "master_limit_tp"};
     static const char* bnames[] = {"src0", "src1", "weights", "out", "res", "bias", "fold_t1", "fold_t2", "gn_ab", "gn_part", "stats_part",
                                    "aux0", "aux1", "aux2", "aux3"};
     int (*fetch[])(ds_bounds_rec*, int) = {ds_bounds_fetch_conv_igemm, ds_bounds_fetch_conv_splitk, ds_bounds_fetch_conv_halo3, ds_bounds_fetch_conv_halo3_hp, ds_bounds_fetch_conv_quad, ds_bounds_fetch_conv_quad_split, ds_bounds_fetch_conv_smalln, ds_bounds_fetch_dwconv7, ds_bounds_fetch_groupnorm,
                                            ds_bounds_fetch_attn_fused, ds_bounds_fetch_attn_x3, ds_bounds_fetch_linattn, ds_bounds_fetch_conv1x1_x3, ds_bounds_fetch_conv7x7_c4, ds_bounds_fetch_convt4x4_c80, ds_bounds_fetch_conv3x3_c80, ds_bounds_fetch_conv3x3_f32_n4, ds_bounds_fetch_vq_attn,
-                                           ds_bounds_fetch_ui_images, ds_bounds_fetch_arranger, ds_bounds_fetch_pitch, ds_bounds_fetch_resample_poly, ds_bounds_fetch_inpaint_mask, ds_bounds_fetch_master, ds_bounds_fetch_loudness};
+                                           ds_bounds_fetch_ui_images, ds_bounds_fetch_arranger, ds_bounds_fetch_pitch, ds_bounds_fetch_resample_poly, ds_bounds_fetch_inpaint_mask, ds_bounds_fetch_master, ds_bounds_fetch_loudness, ds_bounds_fetch_true_peak};
     int hits = 0, pos = 0;
     if (buf && n > 0) buf[0] = 0;
     for (auto f : fetch) {

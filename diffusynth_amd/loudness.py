@@ -3,7 +3,7 @@ tensors, each signal by itself, with ds_loudness (include/diffusynth_hip.h, "lou
 master() uses the same measurement for Mastering(target_lufs=...).
 
 The host's part is the coefficients: kweighting() re-derives the two biquads for the sample rate in float64, and _coefficients() adds the
-powers of the recursion's one-sample transition matrix that the kernels' exact carry needs.  Mono only; no true peak, no loudness range."""
+powers of the recursion's one-sample transition matrix that the kernels' exact carry needs.  Mono only; no loudness range (true peak: diffusynth_amd/true_peak.py)."""
 import collections
 import functools
 import itertools

@@ -1258,6 +1258,46 @@ int ds_loudness(const float* x, const int32_t* tab, int n_signals, int max_len, 
                 void* ws, double* lu, int32_t* cnt, double* blocks, long long total_blocks, void* stream);
 int ds_loudness_gain(const double* lu, int n_signals, double zt, float max_gain, float* stats, void* stream);
 
+/* ---------------------------------------------------------------- true peak: 4x meter and limiter detector, BS.1770 Annex 2 (csrc/true_peak.hip)
+ * One mono signal x[0..N) in fp32, x = 0 outside [0, N), for the ragged batch of the mastering stage (row s of tab: XOFF, LEN).  The
+ * oversampling factor is 4 at every rate.
+ *   interpolator  libebur128's 49-tap, Hann-windowed sinc, restated without its delay:
+ *                 c(d) = sinc(d / 4) (1 + cos(2 pi d / 48)) / 2 for integer |d| <= 24, sinc(t) = sin(pi t) / (pi t), c(0) = 1.
+ *                 c(4 k) = 0 for k != 0: the phase at the sample instants is the identity and is never computed.
+ *                 h[p][k] = fp32(c(4 (5 - k) + p)), p = 1, 2, 3, k = 0 .. 11, computed by the host in float64 and rounded once:
+ *                 DS_TP_NCOEF = 36 fp32 values in HOST memory, row p - 1 at coef + (p - 1) DS_TP_TAPS (they travel as a kernel argument).
+ *                 h[3][k] = h[1][11 - k], and h[2] is symmetric.
+ *   inter-sample  v_p(n) = sum over k = 0 .. 11 of (double)h[p][k] (double)x[n - 5 + k], for n = -1 .. N - 1: the waveform at time
+ *                 n + p / 4.  Every product is exact in float64; the sum runs in ascending k, one rounding per add, no product is
+ *                 contracted into an FMA.  iv(n) = max over p of |v_p(n)|.
+ *   envelope      e[n] = fp32(max(|x[n]|, iv(n - 1), iv(n))): the largest magnitude of the interpolated waveform on the open interval
+ *                 (n - 1, n + 1).  The rounding is monotone, so it commutes with the maximum.
+ *   true peak     TP = max e[n] over 0 <= n < N, fp32.  dBTP = 20 log10 TP is the caller's to compute.
+ *   limiter       ds_master_limit_tp: step 2 of the mastering stage becomes r[n] = fl(c / d[n]) where d[n] = fl(gL e[n]) > c, else 1, with
+ *                 e the envelope of the INPUT x; steps 3-7 are unchanged and on u = fl(gL x).  e[n] >= |x[n]|, so d[n] >= |u[n]|, and
+ *                 g <= r still bounds the SAMPLE peak by c; the bits still have one right answer.  The detector gives no exact bound on the
+ *                 output's true peak (a time-varying gain does not commute with the interpolator): that is measured, not promised
+ *                 (DESIGN 7r).
+ * Non-finite samples are not checked (their effect on the values is unspecified); nothing is read or written out of bounds.
+ *
+ * ds_true_peak: grid (tiles of DS_TP_TILE samples, signal).  A block of tile [t0, t0 + T) stages x over [t0 - 6, t0 + T + 6) in LDS, computes
+ * iv(n), t0 - 1 <= n <= t0 + T - 1, into a second LDS tile, and after one barrier e[n]; the block's maximum goes to ws and one block per
+ * signal takes the maximum of its tiles' (a maximum has no order: tp[s] is the same bits alone and inside any batch).  env may be NULL (the
+ * meter alone); it may not alias x.  ws: ds_true_peak_ws_bytes(n_signals, max_len) bytes (0: bad arguments), 4-byte aligned, need not be
+ * initialised.  Every coef finite, else DS_EINVAL.  tp[s] and, with env, every e[n] of a fitting row are written and nothing else; a row
+ * that does not fit total_samples or has LEN outside [1, max_len] reads and writes nothing.
+ * ds_master_limit_tp: ds_master_limit with env, the [total_samples] fp32 envelope that ds_true_peak wrote for the same x and tab, as the
+ * detector; the same checks, LDS and grid; out may alias neither x nor env. */
+#define DS_TP_TILE 2048
+#define DS_TP_PHASES 3
+#define DS_TP_TAPS 12
+#define DS_TP_NCOEF 36
+size_t ds_true_peak_ws_bytes(int n_signals, int max_len);
+int ds_true_peak(const float* x, const int32_t* tab, int n_signals, int max_len, long long total_samples, const float* coef, float* env, void* ws,
+                 float* tp, void* stream);
+int ds_master_limit_tp(const float* x, const float* env, const int32_t* tab, int n_signals, int max_len, long long total_samples, float ceiling,
+                       int lookahead, int hold, float* stats, int32_t* limited, float* out, int16_t* pcm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,30 @@ def sweep_loudness(fail):
     report("loudness (2, L) batch of 2^20 + 3001 samples, master() to a LUFS target", fail)
 
 
+def sweep_true_peak(fail):
+    """The true-peak meter and the limiter that takes its envelope (csrc/true_peak.hip, ds_master_limit_tp): ragged batches on both sides of
+    the interpolator's reach and of a tile, with and without the envelope, a (B, L) batch, a long signal, and master() with true_peak=True
+    at no look-ahead, the defaults and the caps, with the int16 output and on a long signal.  No LUFS target here: it would add only
+    csrc/loudness.hip's kernels, which sweep_loudness covers, and a ds_loudness call behind a ds_loudness_gain call of the same process
+    reports that translation unit's older extent table on one XCD ("found, not fixed")."""
+    import diffusynth_amd
+    from diffusynth_amd import arranger as A
+    T = L.TP["DS_TP_TILE"]
+    sigs = [3.0 * synth_input("bs_tp%d" % n, (n,)).cuda() for n in (1, 2, 5, 6, 7, 11, 12, 13, T - 1, T, T + 1, 2 * T + 13, 20001)]
+    diffusynth_amd.true_peak(sigs)
+    diffusynth_amd.true_peak(sigs[::-1], return_envelope=True)
+    report("true_peak ragged batch of 13, with and without the envelope", fail)
+    long = synth_input("bs_tp_long", (2 ** 20 + 3001,)).cuda()
+    diffusynth_amd.true_peak(torch.stack([long, -long]), return_envelope=True)
+    report("true_peak (2, L) batch of 2^20 + 3001 samples", fail)
+    for look, hold in ((0.0, 0.0), (0.005, 0.05), (1024.5 / 16000, 8192.5 / 16000)):
+        m = A.Mastering(lookahead=look, hold=hold, true_peak=True)
+        A.master(sigs, m, return_stats=True, return_true_peak=True)
+        A.master(sigs[::-1], m, pcm16=True)
+    A.master([long, long[:7000], long[:100]], A.Mastering(true_peak=True), return_stats=True, return_true_peak=True)
+    report("master(true_peak=True) ragged batch of 13 at three (lookahead, hold) pairs, fp32 and int16, and 2^20 + 3001 samples", fail)
+
+
 def sweep_linattn_paths(fail):
     """The plain linear-attention files at eight exact cases of tests/linattn_ref.py, through the C ABI (this build compiles attn_out_kernel<float>
     without its row-transposition path, and nothing else here calls ds_vq_attn_* directly): empty segments (N = 10 in 7), ragged N, 7 and 8 heads,
@@ -538,6 +562,10 @@ def main():
         sweep_loudness(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
         sys.exit(1 if fail else 0)
+    if "--only-true-peak" in sys.argv:
+        sweep_true_peak(fail)
+        print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
+        sys.exit(1 if fail else 0)
     if "--only-perform" in sys.argv:
         sweep_perform(fail)
         print("BOUNDS VIOLATIONS %s" % fail if fail else "BOUNDS OK")
@@ -633,6 +661,7 @@ def main():
     sweep_ingest(fail)
     sweep_master(fail)
     sweep_loudness(fail)
+    sweep_true_peak(fail)
     # 6) GroupNorm from raw partials in every kernel that reduces them, the depthwise families, the chains without ds_gn_finalize
     sweep_gn_partials(fail)
     # 7) the plain linear-attention files on the paths of tests/test_hip_linattn_paths.py
